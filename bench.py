@@ -7,6 +7,7 @@ incl. the fake-pool generation, Adam updates and BatchNorm moving-average update
 (synthetic, seeded) are resident in HBM before the timed region.  Metric: paired 2-D slices per second, whole job.
 
     python bench.py [--gpus N] [--steps K] [--warmup W]         # N > 1: starts its N ranks itself (child torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                       # + the last timed step's losses and (sampled) weights as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Extra fields of the JSON line:
@@ -25,6 +26,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -275,6 +277,46 @@ def cpu_baseline(H, decoder, B, limit_s=240):
                           % (H, H, B, limit_s, type(exc).__name__)}
 
 
+DUMP_WEIGHT_BYTES = 48 << 20       # --dump-outputs: the weight sample stays under this (the losses add a few hundred bytes)
+
+
+def component_models(model):
+    """every nn.Model of a model wrapper, shared sub-models once, in attribute order"""
+    from multimodal_segmentation_amd import nn
+    out = []
+    for v in vars(model).values():
+        for m in (v if isinstance(v, (list, tuple)) else [v]):
+            if isinstance(m, nn.Model):
+                for o in m.owned_models():
+                    if all(o is not x for x in out):
+                        out.append(o)
+    return out
+
+
+def dump_outputs(out_dir, model, losses, n_before, steps):
+    """--dump-outputs: what the LAST timed step computed, as a caller of the executor's train_batch receives it -- every loss the
+    step recorded (loss_<name>.npy, float64, in recording order; device scalars and trainer totals are read with .item()) and the model state the step left behind: per component model its
+    trainable arena followed by its state arena (BatchNorm moving statistics), weights_<model>.npy, float32.  When all weights
+    together exceed the size budget (DAFNet: ~215 MB), every model contributes the same fraction of its elements at sorted
+    positions drawn from a generator seeded with the model's name: the same positions from run to run and from build to build."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in losses.items():
+        per = (len(v) - n_before[k]) // steps          # entries one step appends under this name
+        if per:
+            np.save(os.path.join(out_dir, 'loss_%s.npy' % k), np.array([float(x.item() if hasattr(x, 'item') else x) for x in v[len(v) - per:]], np.float64))
+    models = component_models(model)
+    frac = min(1.0, DUMP_WEIGHT_BYTES / 4.0 / sum(m.arena.numel() + m.state_arena.numel() for m in models))
+    for m in models:
+        w = np.concatenate([m.arena.cpu().numpy(), m.state_arena.cpu().numpy()]).astype(np.float32)
+        if frac < 1.0:
+            idx = np.random.RandomState(zlib.crc32(m.name.encode())).choice(w.size, int(w.size * frac), replace=False)
+            w = w[np.sort(idx)]
+        np.save(os.path.join(out_dir, 'weights_%s.npy' % m.name), w)
+    _progress('outputs of the last timed step written to %s' % out_dir)
+
+
 def launch_ranks(n, dry_run=False):
     """start `python -m torch.distributed.run --nproc-per-node n bench.py <same arguments>` as a CHILD process (this parent has not
     touched the GPU and never replaces itself); -> the child's return code.  `dry_run`: print the command and the environment it
@@ -286,6 +328,11 @@ def launch_ranks(n, dry_run=False):
     port = s.getsockname()[1]
     s.close()
     argv = [a for a in sys.argv[1:] if a != '--dry-run']
+    for i, a in enumerate(argv):            # the ranks start in the repository root: a relative dump directory is made absolute
+        if a == '--dump-outputs' and i + 1 < len(argv):
+            argv[i + 1] = os.path.abspath(argv[i + 1])
+        elif a.startswith('--dump-outputs='):
+            argv[i] = '--dump-outputs=' + os.path.abspath(a.split('=', 1)[1])
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(n), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__)] + argv
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
@@ -342,7 +389,11 @@ def main():
     ap.add_argument('--conv-timer-stride', type=int, default=7, help='time every n-th convolution launch with HIP events')
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--dry-run', action='store_true', help='with --gpus N > 1: print the launcher command instead of starting the ranks')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed region, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_measure(args.size, args.decoder, args.batch)))
         return
@@ -414,7 +465,10 @@ def main():
         # work during the first (eager) warm-up iteration; the durations come from the committed rocprofv3 trace of this command
         args.conv_timer_stride = 1 << 30
         DTYPE_NAME[args.dtype] += ', trainer steps replayed from hipGraphs'
-    cfg['folder'] = '/tmp/mmseg_bench'
+    # the run folder of the config: empty and private, so that model.build() finds no checkpoint to load (the inputs of the run are
+    # then the seeded ones whatever an earlier run left behind; the benchmark writes nothing there)
+    run_folder = tempfile.TemporaryDirectory(prefix='mmseg_bench_')
+    cfg['folder'] = run_folder.name
     conf = EasyDict(cfg)
 
     _progress('building model')
@@ -461,6 +515,7 @@ def main():
     _progress('timed region')
     timer.enabled = not args.graphs
     dp.counters(reset=True)
+    n_before = {k: len(v) for k, v in losses.items()}
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ex.train_batch(losses)
@@ -468,6 +523,8 @@ def main():
     dt = time.perf_counter() - t0
     timer.enabled = False
     _progress('timed region done: %.1f ms/step' % (1000.0 * dt / args.steps))
+    if args.dump_outputs and rank == 0:           # before the informational multi-stream region trains on
+        dump_outputs(args.dump_outputs, model, losses, n_before, args.steps)
     if args.conv_breakdown and rank == 0:
         torch.cuda.synchronize()
         timer.breakdown(args.steps)

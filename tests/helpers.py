@@ -1,9 +1,26 @@
 """Shared helpers of the model-level tests: tiny configs, seeded synthetic batches, product -> oracle
 parameter export."""
+import atexit
+import os
+import shutil
+import tempfile
+
 import numpy as np
 import torch
 
 from multimodal_segmentation_amd.utils.config import EasyDict
+
+
+_SCRATCH = []
+
+
+def scratch_dir():
+    """a private directory of this process for run folders (removed at exit): a fixed name under /tmp could hold another
+    user's or an earlier run's checkpoints, which model.build() would load"""
+    if not _SCRATCH:
+        _SCRATCH.append(tempfile.mkdtemp(prefix='mmseg_test_'))
+        atexit.register(shutil.rmtree, _SCRATCH[0], True)
+    return _SCRATCH[0]
 
 
 def make_conf(config_module, H, W=None, **overrides):
@@ -17,7 +34,7 @@ def make_conf(config_module, H, W=None, **overrides):
     if 'd_image_params' in conf:
         conf['d_image_params']['input_shape'] = shp
     conf['n_pairs'] = 1
-    conf['folder'] = '/tmp/mmseg_test_' + conf['folder']
+    conf['folder'] = os.path.join(scratch_dir(), conf['folder'])
     conf.update(overrides)
     return EasyDict(conf)
 

@@ -120,14 +120,14 @@ def test_balancer_predict_and_validation_weights(device):
 
 
 @pytest.mark.gpu
-def test_automated_pairing_executor_epoch():
+def test_automated_pairing_executor_epoch(tmp_path):
     """data containers -> expand_pairs -> rotated 3-channel batches -> automated trainers -> discriminators -> validation"""
     import shutil
     nn.set_default_device('cuda:0')
     from multimodal_segmentation_amd.model_executors.dafnet_executor import DAFNetExecutor
     conf = Hh.make_conf(dafnet_config_chaos, 64, batch_size=4, epochs=1, slices_per_volume=3, automatedpairing=True,
                         n_pairs=3, l_mix=0.5)
-    conf.folder = '/tmp/mmseg_test_auto_epoch'
+    conf.folder = str(tmp_path / 'auto_epoch')
     shutil.rmtree(conf.folder, ignore_errors=True)
     model = DAFNet(conf)
     model.build()

@@ -158,11 +158,11 @@ def _check_results_csv(model, orc, data, conf):
     shutil.rmtree(conf.folder, ignore_errors=True)
 
 
-def test_dafnet_inference_paths(device):
+def test_dafnet_inference_paths(device, tmp_path):
     from multimodal_segmentation_amd.models.dafnet import DAFNet
     from multimodal_segmentation_amd.model_executors.dafnet_executor import DAFNetExecutor
     conf = Hh.make_conf(dafnet_config_chaos, H, batch_size=2, test_dataset='chaos', slices_per_volume=2)
-    conf.folder = '/tmp/mmseg_test_eval_dafnet_' + device
+    conf.folder = str(tmp_path / ('eval_dafnet_' + device))
     model = DAFNet(conf)
     model.build()
     _liven(model, model._generator_models())
@@ -183,11 +183,11 @@ def test_dafnet_inference_paths(device):
     assert 0.0 < want['val_loss'] < 1.0
 
 
-def test_mmsdnet_inference_paths(device):
+def test_mmsdnet_inference_paths(device, tmp_path):
     from multimodal_segmentation_amd.models.mmsdnet import MMSDNet
     from multimodal_segmentation_amd.model_executors.mmsdnet_executor import MMSDNetExecutor
     conf = Hh.make_conf(mmsdnet_config_chaos, H, batch_size=2, test_dataset='chaos', slices_per_volume=2)
-    conf.folder = '/tmp/mmseg_test_eval_mmsdnet_' + device
+    conf.folder = str(tmp_path / ('eval_mmsdnet_' + device))
     shutil.rmtree(conf.folder, ignore_errors=True)
     model = MMSDNet(conf)
     model.build()

@@ -66,12 +66,12 @@ def test_dice_metric_and_early_stopping():
 
 
 @pytest.mark.gpu
-def test_train_two_epochs_then_test_writes_reference_layout():
+def test_train_two_epochs_then_test_writes_reference_layout(tmp_path):
     nn.set_default_device('cuda:0')
     from multimodal_segmentation_amd.models.dafnet import DAFNet
     from multimodal_segmentation_amd.model_executors.dafnet_executor import DAFNetExecutor
     conf = Hh.make_conf(dafnet_config_chaos, 64, batch_size=4, epochs=2, slices_per_volume=2, test_dataset='chaos')
-    conf.folder = '/tmp/mmseg_test_train_loop'
+    conf.folder = str(tmp_path / 'train_loop')
     shutil.rmtree(conf.folder, ignore_errors=True)
     model = DAFNet(conf)
     model.build()
@@ -97,14 +97,14 @@ def test_train_two_epochs_then_test_writes_reference_layout():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('nmod', [2, 3])
-def test_mmsdnet_train_epoch_then_test(nmod):
+def test_mmsdnet_train_epoch_then_test(nmod, tmp_path):
     nn.set_default_device('cuda:0')
     from multimodal_segmentation_amd.configuration import mmsdnet_config_chaos, mmsdnet3_config_chaos
     from multimodal_segmentation_amd.models.mmsdnet import MMSDNet
     from multimodal_segmentation_amd.model_executors.mmsdnet_executor import MMSDNetExecutor
     conf = Hh.make_conf(mmsdnet_config_chaos if nmod == 2 else mmsdnet3_config_chaos, 64, batch_size=4, epochs=1,
                         slices_per_volume=2, test_dataset='chaos')
-    conf.folder = '/tmp/mmseg_test_train_loop_mmsdnet%d' % nmod
+    conf.folder = str(tmp_path / ('train_loop_mmsdnet%d' % nmod))
     shutil.rmtree(conf.folder, ignore_errors=True)
     model = MMSDNet(conf)
     model.build()
@@ -126,7 +126,7 @@ def test_mmsdnet_train_epoch_then_test(nmod):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('dtype', ['fp32', 'bf16', 'fp16'])
-def test_training_learns_on_the_synthetic_split(dtype):
+def test_training_learns_on_the_synthetic_split(dtype, tmp_path):
     """six short epochs (84 iterations, lr 1e-4, augmentation on): the supervised segmentation loss falls by > 10 % and the
     validation Dice loss of the SWA clones improves"""
     nn.set_default_device('cuda:0')
@@ -134,7 +134,7 @@ def test_training_learns_on_the_synthetic_split(dtype):
     from multimodal_segmentation_amd.model_executors.dafnet_executor import DAFNetExecutor
     conf = Hh.make_conf(dafnet_config_chaos, 64, batch_size=4, epochs=6, slices_per_volume=4, test_dataset='chaos',
                         compute_dtype=dtype)
-    conf.folder = '/tmp/mmseg_test_learns_' + dtype
+    conf.folder = str(tmp_path / ('learns_' + dtype))
     shutil.rmtree(conf.folder, ignore_errors=True)
     model = DAFNet(conf)
     model.build()
