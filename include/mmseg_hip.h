@@ -287,6 +287,14 @@ int mmseg_tps_warp_bwd(const float* vol, const float* loc, const float* Mb, cons
  *      .flow of model_executors/base_executor.py:37-78,103-110 = scipy affine_transform(order=1, mode='nearest') ---- */
 int mmseg_affine_gather(const float* data, const int* rows, const float* mat, float* out, int B, int H, int W, int C, int order,
                         void* stream);
+/* the whole ImageDataGenerator pixel surface of get_datagen_params() (model_executors/base_executor.py:37-78,103-110; keras 2.1.6
+ * random_transform): per-sample 2x3 fp64 matrix mat [B,6] (rotation, shift, shear, zoom about the centre, flips folded in),
+ * fill_mode 0 nearest / 1 constant (cval) / 2 reflect / 3 wrap with scipy.ndimage's boundary rules, order 0 or 1; shift [B,C]
+ * or NULL: random_channel_shift, out = clip(x_c + shift[b][c], min, max of the transformed sample).  rows NULL = identity;
+ * data holds N slices.  ws: mmseg_augment_workspace_floats(B, H, W, C) floats (only read with a shift). */
+long mmseg_augment_workspace_floats(int B, int H, int W, int C);
+int mmseg_augment_gather(const float* data, const int* rows, const double* mat, const float* shift, float* out, float* ws, int N,
+                         int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream);
 
 /* ---- losses (csrc/loss.hip): costs.py:43-85,129-136, keras mae/mse, costs.ypred ---------------------------- */
 int mmseg_segloss_workspace_floats(int B);

@@ -1,6 +1,7 @@
 """Base class of the executors (reference model_executors/base_executor.py): batch alignment, the background
 ("residual") mask channel, and the augmenting data generators (keras ImageDataGenerator with +-20 degree rotations,
-base_executor.py:37-78,103-110 -> utils/augment.RotationFlow: shuffle, gather and rotate on the device)."""
+base_executor.py:37-78,103-110 -> utils/augment.RotationFlow: shuffle, gather and rotate on the device; any other pixel
+augmentation of the dict -> utils/augment.AugmentFlow)."""
 import logging
 
 import numpy as np
@@ -34,27 +35,38 @@ class Executor(object):
         return dict(horizontal_flip=False, vertical_flip=False, rotation_range=20., width_shift_range=0, height_shift_range=0,
                     zoom_range=0)
 
+    def datagen_params(self):
+        """get_datagen_params() with the build-defined conf.datagen_params (a dict) merged over it, validated"""
+        from ..utils.augment import check_datagen_params
+        p = dict(self.get_datagen_params())
+        extra = self.conf.get('datagen_params', None)
+        if extra:
+            if not isinstance(extra, dict):
+                raise ValueError('conf.datagen_params must be a dict, got %r' % (extra,))
+            p.update(extra)
+        return check_datagen_params(p)
+
     def get_data_generator(self, train_images=None, train_labels=None):
-        """Iterator over (images..., labels...) batches, all shuffled and rotated identically (base_executor.py:37-78: one
-        keras flow per array with a shared seed, zipped).  A single array yields bare batches instead of 1-tuples."""
-        from ..utils.augment import RotationFlow
+        """Iterator over (images..., labels...) batches, all shuffled and augmented as keras does (base_executor.py:37-78: one
+        keras flow per array with a shared seed, zipped).  A single array yields bare batches instead of 1-tuples.
+        RotationFlow when the dict sets nothing but rotation_range (the reference's default), AugmentFlow otherwise."""
+        from ..utils.augment import AugmentFlow, RotationFlow, rotation_only
         arrays = []
         for group in (train_images, train_labels):
             if group is not None:
                 arrays += list(group) if isinstance(group, (list, tuple)) else [group]
         if not arrays:
             raise Exception('No data to iterate.')
-        p = self.get_datagen_params()
-        unsupported = [k for k in ('horizontal_flip', 'vertical_flip', 'width_shift_range', 'height_shift_range', 'zoom_range')
-                       if p.get(k)]
-        if unsupported:
-            raise NotImplementedError('augmentations not on the device path: %s' % unsupported)
+        p = self.datagen_params()
         # data parallel: rank r reseeds the global numpy stream with conf.seed + 7919 r (+ batch index), so shuffles, rotation
         # angles and the z / pool-index draws that follow a batch differ between replicas; rank 0 follows the reference stream
         from ..parallel import dp
-        return RotationFlow(arrays, self.conf.batch_size, self.conf.seed + 7919 * dp.rank(), self.device,
-                            rotation_range=p['rotation_range'],
-                            order=self.conf.get('augment_interpolation_order', 1))
+        seed = self.conf.seed + 7919 * dp.rank()
+        order = self.conf.get('augment_interpolation_order', 1)
+        if rotation_only(p):
+            return RotationFlow(arrays, self.conf.batch_size, seed, self.device, rotation_range=p.get('rotation_range', 0.),
+                                order=order)
+        return AugmentFlow(arrays, self.conf.batch_size, seed, self.device, p, order=order)
 
     def validate(self, epoch_loss):
         pass

@@ -1498,6 +1498,26 @@ def affine_gather(data, rows, mat, order=1):
     return out
 
 
+FILL_MODES = ('nearest', 'constant', 'reflect', 'wrap')
+
+
+def augment_gather(data, rows, mat, shift=None, order=1, fill_mode='nearest', cval=0.):
+    """out[b] = resample of data[rows[b]] with the fp64 2x3 matrix mat[b] in (row, col) coordinates, scipy.ndimage boundary rule
+    `fill_mode` (FILL_MODES; 'constant' fills with cval), order 0/1; with shift [B,C] then keras' random_channel_shift
+    clip(x_c + shift[b,c], min(x), max(x)) over the transformed sample (csrc/augment.hip).  No gradient (input pipeline)."""
+    if fill_mode not in FILL_MODES:
+        raise ValueError('fill_mode must be one of %s, got %r' % (FILL_MODES, fill_mode))
+    B, (Nd, H, W, C) = mat.shape[0], data.shape
+    out = _new((B, H, W, C), data)
+    ws = None
+    if shift is not None:
+        shift = _c(shift)
+        ws = _ws('augment', N.call('mmseg_augment_workspace_floats', B, H, W, C), data.device)
+    N.call('mmseg_augment_gather', data, rows, _c(mat), shift, out, ws, Nd, B, H, W, C, int(order), FILL_MODES.index(fill_mode),
+           float(cval))
+    return out
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

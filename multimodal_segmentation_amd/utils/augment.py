@@ -15,6 +15,9 @@ source, unverifiable here -- see DESIGN.md) does, for batch number k of one iter
 leaving the global RNG in the same state -- which matters, because the executors draw z samples and pool indices from
 the global RNG right after `next(gen)`), keeps the arrays resident in HBM and produces the rotated batch with one
 `mmseg_affine_gather` launch per array.
+
+`AugmentFlow` does the same for every other pixel key of ImageDataGenerator (shift, shear, zoom, flips, channel shift, fill
+modes; `KerasTransformStream` is keras' full random_transform draw sequence) with one `mmseg_augment_gather` launch per array.
 """
 import numpy as np
 import torch
@@ -77,6 +80,206 @@ class RotationFlow(object):
         rows_d = nn.host_to_device(rows, self.device, np.int32)
         mat_d = nn.host_to_device(rotation_matrices(thetas, self.H, self.W), self.device, np.float32)
         out = tuple(ops.affine_gather(a, rows_d, mat_d, self.order) for a in self.arrays)
+        return out if len(out) > 1 else out[0]
+
+    next = __next__
+
+
+# ---- the full ImageDataGenerator pixel surface ----------------------------------------------------------------------------------
+# keys of keras 2.1.6 ImageDataGenerator(**d) that this pipeline implements (the reference's dict, base_executor.py:103-110, sets
+# the first six); brightness_range (PIL), the feature/sample-wise statistics, zca_whitening, rescale and preprocessing_function
+# are not on the device path
+DATAGEN_KEYS = ('rotation_range', 'width_shift_range', 'height_shift_range', 'shear_range', 'zoom_range', 'channel_shift_range',
+                'fill_mode', 'cval', 'horizontal_flip', 'vertical_flip')
+
+
+# keras arguments outside the device path: accepted only at a value that switches them off
+_OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center', 'featurewise_std_normalization',
+                  'samplewise_std_normalization', 'zca_whitening', 'zca_epsilon', 'rescale', 'preprocessing_function', 'data_format')
+
+
+def check_datagen_params(params):
+    """ValueError with a clear message for a dict the device pipeline cannot honour exactly; returns the dict."""
+    for k, v in params.items():
+        if k in DATAGEN_KEYS:
+            continue
+        if k in _OFF_PATH_KEYS:
+            if k == 'zca_epsilon' or v is None or v is False or (k == 'data_format' and v == 'channels_last') or \
+                    (not isinstance(v, str) and np.isscalar(v) and v == 0):
+                continue
+            raise ValueError('datagen parameter %s=%r is not supported on the device augmentation path (supported: %s)'
+                             % (k, v, ', '.join(DATAGEN_KEYS)))
+        raise ValueError('unknown datagen parameter %r (supported: %s)' % (k, ', '.join(DATAGEN_KEYS)))
+    for k in ('width_shift_range', 'height_shift_range'):
+        v = params.get(k, 0.)
+        if isinstance(v, bool) or not np.isscalar(v) or isinstance(v, str) or \
+                (isinstance(v, (int, np.integer)) and v != 0):
+            raise ValueError('%s must be a float (keras 2.1.6: below 1 a fraction of the extent, otherwise pixels), got %r'
+                             % (k, v))
+    for k in ('rotation_range', 'shear_range', 'channel_shift_range', 'cval'):
+        v = params.get(k, 0.)
+        if isinstance(v, bool) or not np.isscalar(v) or isinstance(v, str):
+            raise ValueError('%s must be a number, got %r' % (k, v))
+    zoom_bounds(params.get('zoom_range', 0.))
+    fm = params.get('fill_mode', 'nearest')
+    if fm not in ops.FILL_MODES:
+        raise ValueError('fill_mode must be one of %s, got %r' % (', '.join(ops.FILL_MODES), fm))
+    return params
+
+
+def rotation_only(params):
+    """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges"""
+    return params.get('fill_mode', 'nearest') == 'nearest' and not any(
+        params.get(k) for k in ('width_shift_range', 'height_shift_range', 'shear_range', 'channel_shift_range',
+                                'horizontal_flip', 'vertical_flip')) and zoom_bounds(params.get('zoom_range', 0.) or 0.) == (1., 1.)
+
+
+def zoom_bounds(zoom_range):
+    """keras: a scalar z -> [1 - z, 1 + z], a pair -> itself"""
+    if np.isscalar(zoom_range) and not isinstance(zoom_range, str):
+        return 1. - zoom_range, 1. + zoom_range
+    if isinstance(zoom_range, (list, tuple, np.ndarray)) and len(zoom_range) == 2:
+        return float(zoom_range[0]), float(zoom_range[1])
+    raise ValueError('zoom_range should be a float or a tuple or list of two floats, got %r' % (zoom_range,))
+
+
+class KerasTransformStream(object):
+    """keras 2.1.6 NumpyArrayIterator(shuffle=True, seed=s) + random_transform of ImageDataGenerator(**params) for arrays of
+    [N, H, W, C]: per batch the rows, and per sample the resampling matrix (fp64 [B, 6], flips folded in), the flip flags and
+    the channel shifts ([B, C] or None).  Per sample keras draws, each only when its key is non-zero: theta, tx, ty, shear,
+    (zx, zy), one channel shift per channel, the horizontal flip, the vertical flip -- all from the GLOBAL numpy RNG."""
+
+    def __init__(self, n, batch_size, seed, params, H, W, C):
+        self.n, self.batch_size, self.seed = int(n), int(batch_size), seed
+        self.H, self.W, self.C = int(H), int(W), int(C)
+        p = params
+        self.rotation = float(p.get('rotation_range', 0.) or 0.)
+        self.hshift = float(p.get('height_shift_range', 0.) or 0.)
+        self.wshift = float(p.get('width_shift_range', 0.) or 0.)
+        self.shear = float(p.get('shear_range', 0.) or 0.)
+        self.zoom = zoom_bounds(p.get('zoom_range', 0.) or 0.)
+        self.channel_shift = float(p.get('channel_shift_range', 0.) or 0.)
+        self.hflip, self.vflip = bool(p.get('horizontal_flip', False)), bool(p.get('vertical_flip', False))
+        self.total_batches_seen = 0
+        self.batch_index = 0
+        self.order = None
+
+    def _rows(self):
+        if self.seed is not None:
+            np.random.seed(self.seed + self.total_batches_seen)
+        if self.batch_index == 0:
+            self.order = np.random.permutation(self.n)
+        start = (self.batch_index * self.batch_size) % self.n
+        self.batch_index = self.batch_index + 1 if self.n > start + self.batch_size else 0
+        self.total_batches_seen += 1
+        return self.order[start:start + self.batch_size]
+
+    def _transform(self):
+        """one sample: (3x3 fp64 matrix or None, channel shifts or None, hflip, vflip), in keras' draw order"""
+        H, W = self.H, self.W
+        theta = np.deg2rad(np.random.uniform(-self.rotation, self.rotation)) if self.rotation else 0
+        tx = ty = 0
+        if self.hshift:
+            tx = np.random.uniform(-self.hshift, self.hshift)
+            if self.hshift < 1:
+                tx *= H
+        if self.wshift:
+            ty = np.random.uniform(-self.wshift, self.wshift)
+            if self.wshift < 1:
+                ty *= W
+        shear = np.deg2rad(np.random.uniform(-self.shear, self.shear)) if self.shear else 0
+        if self.zoom[0] == 1 and self.zoom[1] == 1:
+            zx, zy = 1, 1
+        else:
+            zx, zy = np.random.uniform(self.zoom[0], self.zoom[1], 2)
+        m = None
+        if theta != 0:
+            m = np.array([[np.cos(theta), -np.sin(theta), 0], [np.sin(theta), np.cos(theta), 0], [0, 0, 1]])
+        if tx != 0 or ty != 0:
+            t = np.array([[1, 0, tx], [0, 1, ty], [0, 0, 1]])
+            m = t if m is None else np.dot(m, t)
+        if shear != 0:
+            t = np.array([[1, -np.sin(shear), 0], [0, np.cos(shear), 0], [0, 0, 1]])
+            m = t if m is None else np.dot(m, t)
+        if zx != 1 or zy != 1:
+            t = np.array([[zx, 0, 0], [0, zy, 0], [0, 0, 1]])
+            m = t if m is None else np.dot(m, t)
+        if m is not None:                                  # transform_matrix_offset_center
+            ox, oy = float(H) / 2 + 0.5, float(W) / 2 + 0.5
+            m = np.dot(np.dot(np.array([[1, 0, ox], [0, 1, oy], [0, 0, 1]]), m), np.array([[1, 0, -ox], [0, 1, -oy], [0, 0, 1]]))
+        shifts = None
+        if self.channel_shift != 0:
+            shifts = [np.random.uniform(-self.channel_shift, self.channel_shift) for _ in range(self.C)]
+        hf = bool(self.hflip and np.random.random() < 0.5)
+        vf = bool(self.vflip and np.random.random() < 0.5)
+        return m, shifts, hf, vf
+
+    def next(self):
+        """-> rows [B], mats fp64 [B, 6], hflips [B], vflips [B], shifts fp64 [B, C] or None"""
+        rows = self._rows()
+        B, H, W = len(rows), self.H, self.W
+        mats = np.zeros((B, 6), np.float64)
+        hfl, vfl = np.zeros(B, bool), np.zeros(B, bool)
+        shifts = np.zeros((B, self.C), np.float64) if self.channel_shift != 0 else None
+        for i in range(B):
+            m, sh, hfl[i], vfl[i] = self._transform()
+            m = np.eye(3) if m is None else m
+            # flips act on the transformed sample: out[r, c] = t[H-1-r, W-1-c] -> right factors of the matrix (integer entries: exact)
+            if hfl[i]:
+                m = np.dot(m, np.array([[1, 0, 0], [0, -1, W - 1], [0, 0, 1]]))
+            if vfl[i]:
+                m = np.dot(m, np.array([[-1, 0, H - 1], [0, 1, 0], [0, 0, 1]]))
+            mats[i] = m[:2].reshape(6)
+            if sh is not None:
+                shifts[i] = sh
+        return rows, mats, hfl, vfl, shifts
+
+
+class AugmentFlow(object):
+    """RotationFlow for the whole ImageDataGenerator(**params) pixel surface: iterator over aligned arrays [N,H,W,C_i] -> tuple
+    of augmented device batches (a single array yields a bare tensor).
+
+    Keras gives every array its own iterator, reseeded with seed + k, and random_transform draws one channel shift PER CHANNEL:
+    with channel_shift_range != 0 an image (C = 1) and its masks (C = num_masks) consume different numbers of draws and, from the
+    second sample of a batch on, get different geometry and flips (the shuffle, the first draw after the reseed, stays shared).
+    So one KerasTransformStream runs per distinct channel count (a single one when channel_shift_range == 0), and the stream of
+    the LAST array in zip order runs last: the global RNG is left where keras' zipped next() leaves it."""
+
+    def __init__(self, arrays, batch_size, seed, device, params, order=1):
+        self.device = torch.device(device)
+        self.arrays = [a if isinstance(a, torch.Tensor) else
+                       torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device) for a in arrays]
+        n = self.arrays[0].shape[0]
+        assert all(a.shape[0] == n for a in self.arrays), [tuple(a.shape) for a in self.arrays]
+        assert all(a.dim() == 4 for a in self.arrays), [tuple(a.shape) for a in self.arrays]
+        self.H, self.W = int(self.arrays[0].shape[1]), int(self.arrays[0].shape[2])
+        self.fill_mode, self.cval = params.get('fill_mode', 'nearest'), float(params.get('cval', 0.))
+        if self.fill_mode not in ops.FILL_MODES:
+            raise ValueError('fill_mode must be one of %s, got %r' % (ops.FILL_MODES, self.fill_mode))
+        per_channel = float(params.get('channel_shift_range', 0.) or 0.) != 0
+        chans = [int(a.shape[3]) for a in self.arrays]
+        self.keys = [c if per_channel else 0 for c in chans]
+        last = self.keys[-1]
+        distinct = []
+        for k in self.keys:
+            if k not in distinct and k != last:
+                distinct.append(k)
+        self.streams = [(k, KerasTransformStream(n, batch_size, seed, params, self.H, self.W, k or 1)) for k in distinct + [last]]
+        self.order = order
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        rows_d, mats, shifts = None, {}, {}
+        for k, s in self.streams:
+            rows, m, _, _, sh = s.next()
+            if rows_d is None:
+                rows_d = nn.host_to_device(rows, self.device, np.int32)
+            mats[k] = nn.host_to_device(m, self.device, np.float64)
+            shifts[k] = None if sh is None else nn.host_to_device(sh, self.device, np.float32)
+        out = tuple(ops.augment_gather(a, rows_d, mats[k], shifts[k], self.order, self.fill_mode, self.cval)
+                    for a, k in zip(self.arrays, self.keys))
         return out if len(out) > 1 else out[0]
 
     next = __next__
