@@ -308,6 +308,9 @@ int mmseg_segloss_finalize(const float* stats, float* loss, float* coef, int B, 
                            float lambda_bce, void* stream);
 int mmseg_segloss_grad(const float* pred, const float* target, const float* coef, float* dpred, int B, long HW, int C, int nm,
                        float scale, int use_bce, void* stream);
+/* build-defined (dynamic loss scale, see mmseg_unscale_check8): the same gradient with the factor scale * scale_dev[0] */
+int mmseg_segloss_grad_s(const float* pred, const float* target, const float* coef, float* dpred, int B, long HW, int C, int nm,
+                         float scale, const float* scale_dev, int use_bce, void* stream);
 /* ---- in-graph per-sample loss terms of the automated-pairing trainers (csrc/pairloss.hip): model_components/balancer.py:33-38
  *      (pair dice), costs.py:24-26 (mae_single_input), costs.py:43-49,88-108,138-143 (combined dice + swapped-argument
  *      per-batch cross-entropy), keras Multiply/Add of models/dafnet.py:290-312 (row dot) ------------------------------ */
@@ -332,6 +335,9 @@ int mmseg_diffloss_workspace_floats(void);
 /* mode 0: mean|p-t|, 1: mean (p-t)^2, 2: mean p ; t == NULL -> constant target tconst */
 int mmseg_diffloss(const float* p, const float* t, float tconst, long n, int mode, float* loss, float* ws, void* stream);
 int mmseg_diffloss_grad(const float* p, const float* t, float tconst, long n, int mode, float scale, float* dp, void* stream);
+/* build-defined (dynamic loss scale): the same gradient with the factor scale * scale_dev[0] */
+int mmseg_diffloss_grad_s(const float* p, const float* t, float tconst, long n, int mode, float scale, const float* scale_dev, float* dp,
+                          void* stream);
 
 /* ---- optimiser / regulariser (csrc/optim.hip) ---------------------------------------------------------- */
 /* Keras 2.1.6 Adam step over a flat arena (models/dafnet.py:93,114,155,161) */
@@ -349,6 +355,27 @@ int mmseg_spectral_fwd4(const float* w0, const float* w1, const float* w2, const
                         int K2, int N2, int K3, int N3, float alpha, void* stream);
 int mmseg_spectral_grad4(const float* w0, const float* w1, const float* w2, const float* w3, const float* sgn, float* dw0, float* dw1,
                          float* dw2, float* dw3, int n, long n0, long n1, long n2, long n3, float scale, void* stream);
+/* build-defined (dynamic loss scale): the same accumulation with the factor scale * scale_dev[0] */
+int mmseg_spectral_grad4_s(const float* w0, const float* w1, const float* w2, const float* w3, const float* sgn, float* dw0, float* dw1,
+                           float* dw2, float* dw3, int n, long n0, long n1, long n2, long n3, float scale, const float* scale_dev,
+                           void* stream);
+
+/* ---- dynamic loss scaling (csrc/optim.hip): build-defined, the reference trains in fp32 and has none ------------------------------
+ * torch.cuda.amp.GradScaler semantics with power-of-two factors, all state in device memory (no host read during a step, so a step
+ * may be captured into a hipGraph): scale[1] (fp32, a power of two) and st[4] (int32) = {found_inf, growth counter, skipped steps,
+ * Adam iterations}.  One step: the seed gradients use the _s entry points above with scale_dev = scale; mmseg_unscale_check8 over
+ * the trainer's gradient arenas; mmseg_adam_guarded per arena; mmseg_loss_scale_update. */
+/* g_i *= 1 / scale[0] for the first `count` (1..8) arenas (16-byte aligned, any length); st[0] = 1 if any element was +-inf or NaN
+ * (exponent bits all ones).  st[0] is only ever set here, never cleared. */
+int mmseg_unscale_check8(float* g0, float* g1, float* g2, float* g3, float* g4, float* g5, float* g6, float* g7, long n0, long n1,
+                         long n2, long n3, long n4, long n5, long n6, long n7, int count, const float* scale, int* st, void* stream);
+/* mmseg_adam_p's update (models/dafnet.py:93,114,155,161) with lr_t = lr_table[min(st[3] + 1, table_len) - 1] (the host writes
+ * lr_table[j] = lr_t(j + 1) in fp64-then-fp32, its last entry equal to lr); p, m, v untouched when st[0] is set */
+int mmseg_adam_guarded(float* p, const float* g, float* m, float* v, long n, const float* lr_table, int table_len, const int* st,
+                       float b1, float b2, float eps, void* stream);
+/* end of a step (one thread): st[0] set -> scale = max(scale / 2, 1), st[1] = 0, st[2] += 1; else st[3] += 1, st[1] += 1 and at
+ * growth_interval scale *= 2 (at most 2^127), st[1] = 0.  Clears st[0]. */
+int mmseg_loss_scale_update(float* scale, int* st, int growth_interval, void* stream);
 
 #ifdef __cplusplus
 }

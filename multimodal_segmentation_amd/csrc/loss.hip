@@ -122,6 +122,23 @@ __global__ void segloss_grad_kernel(const float* __restrict__ pred, const float*
         (void)pred;
     }
 }
+// the _s entry point: the host factor times scale_dev[0], the dynamic loss scale (a power of two: the product is the fp32 rounding of
+// weight * scale, as with a host-side static scale).  Its own kernel, so that segloss_grad_kernel of the static path stays as it was.
+__global__ void segloss_grad_s_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ coef,
+                                      float* __restrict__ dpred, int B, long HW, int C, int nm, float scale_host,
+                                      const float* __restrict__ scale_dev, int use_bce) {
+    const float scale = scale_host * scale_dev[0];
+    const long n = (long)B * HW * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int c = i % C; const int b = i / (HW * C);
+        const float t = target[i];
+        float g = 0.f;
+        if (c < nm) g += coef[2 * b] * t + coef[2 * b + 1];
+        if (use_bce) g += coef[2 * B + c] * logf(t + 1e-12f) + coef[2 * B + C + c];
+        dpred[i] = g * scale;
+        (void)pred;
+    }
+}
 
 // ---- mean |p - t|, mean (p - t)^2, mean p ----------------------------------------------------------------
 // mode 0: mae, 1: mse, 2: mean(p).  target == nullptr -> constant tconst
@@ -146,6 +163,19 @@ __global__ void diffloss_final_kernel(const float* __restrict__ part, int nblk, 
 // keras/TF: d|d|/dd = sign(d) (0 at 0)
 __global__ void diffloss_grad_kernel(const float* __restrict__ p, const float* __restrict__ t, float tconst, long n, int mode,
                                      float scale, float* __restrict__ dp) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float d = p[i] - (t ? t[i] : tconst);
+        float g;
+        if (mode == 0) g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        else if (mode == 1) g = 2.f * d;
+        else g = 1.f;
+        dp[i] = g * scale;
+    }
+}
+// the _s entry point's kernel (see segloss_grad_s_kernel)
+__global__ void diffloss_grad_s_kernel(const float* __restrict__ p, const float* __restrict__ t, float tconst, long n, int mode,
+                                       float scale_host, const float* __restrict__ scale_dev, float* __restrict__ dp) {
+    const float scale = scale_host * scale_dev[0];
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const float d = p[i] - (t ? t[i] : tconst);
         float g;
@@ -187,6 +217,14 @@ int mmseg_segloss_grad(const float* pred, const float* target, const float* coef
     hipLaunchKernelGGL(segloss_grad_kernel, dim3(lgrid(n) * 4), dim3(256), 0, (hipStream_t)stream, pred, target, coef, dpred, B, HW, C, nm, scale, use_bce);
     return MMSEG_CHECK_LAUNCH();
 }
+int mmseg_segloss_grad_s(const float* pred, const float* target, const float* coef, float* dpred, int B, long HW, int C, int nm,
+                         float scale, const float* scale_dev, int use_bce, void* stream) {
+    if (scale_dev == nullptr) return (int)hipErrorInvalidValue;
+    const long n = (long)B * HW * C;
+    hipLaunchKernelGGL(segloss_grad_s_kernel, dim3(lgrid(n) * 4), dim3(256), 0, (hipStream_t)stream, pred, target, coef, dpred, B, HW, C,
+                       nm, scale, scale_dev, use_bce);
+    return MMSEG_CHECK_LAUNCH();
+}
 
 int mmseg_diffloss_workspace_floats(void) { return 1024; }
 int mmseg_diffloss(const float* p, const float* t, float tconst, long n, int mode, float* loss, float* ws, void* stream) {
@@ -198,6 +236,13 @@ int mmseg_diffloss(const float* p, const float* t, float tconst, long n, int mod
 }
 int mmseg_diffloss_grad(const float* p, const float* t, float tconst, long n, int mode, float scale, float* dp, void* stream) {
     hipLaunchKernelGGL(diffloss_grad_kernel, dim3(lgrid(n) * 4), dim3(256), 0, (hipStream_t)stream, p, t, tconst, n, mode, scale, dp);
+    return MMSEG_CHECK_LAUNCH();
+}
+int mmseg_diffloss_grad_s(const float* p, const float* t, float tconst, long n, int mode, float scale, const float* scale_dev, float* dp,
+                          void* stream) {
+    if (scale_dev == nullptr) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(diffloss_grad_s_kernel, dim3(lgrid(n) * 4), dim3(256), 0, (hipStream_t)stream, p, t, tconst, n, mode, scale, scale_dev,
+                       dp);
     return MMSEG_CHECK_LAUNCH();
 }
 

@@ -31,6 +31,102 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     }
 }
 
+// ---- dynamic loss scaling (conf.loss_scale = 'dynamic', build-defined; torch.cuda.amp.GradScaler semantics) --------------------
+// Device state of one trainer: scale[1] (a power of two) and st[4] = {found_inf, growth counter, skipped steps, Adam iterations}.
+// A step: the seeds multiply their host weights by scale[0] (loss.hip, spec_grad_multi_s_kernel) -> unscale_check_kernel over the
+// trainer's gradient arenas (g *= 1/scale, found_inf |= any non-finite element) -> adam_guarded_kernel per arena (no write at all
+// when found_inf) -> loss_scale_update_kernel (backoff or growth, counters, flag cleared).  No host read anywhere in the step.
+#define LS_MAXA 8
+#define LS_BLOCK 256
+struct UnscaleBatch { float* g[LS_MAXA]; long n[LS_MAXA]; int blk0[LS_MAXA + 1]; };
+// all-ones exponent = +-inf or NaN; a bit test, so that no floating-point mode can fold the check away
+__device__ __forceinline__ bool nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__global__ __launch_bounds__(LS_BLOCK) void unscale_check_kernel(UnscaleBatch b, int na, const float* __restrict__ scale,
+                                                                 int* __restrict__ st) {
+    __shared__ int red[LS_BLOCK / 64];
+    int z = 0;                                             // the arena of this block: blocks [blk0[z], blk0[z+1]) cover arena z
+    while (z + 1 < na && (int)blockIdx.x >= b.blk0[z + 1]) ++z;
+    const int nb = b.blk0[z + 1] - b.blk0[z], bi = (int)blockIdx.x - b.blk0[z];
+    float* __restrict__ g = b.g[z];
+    const long n = b.n[z], n4 = n >> 2;
+    const float inv = 1.f / scale[0];                      // exact: the scale is a power of two
+    bool bad = false;
+    for (long i = (long)bi * LS_BLOCK + threadIdx.x; i < n4; i += (long)nb * LS_BLOCK) {
+        f32x4 x = reinterpret_cast<f32x4*>(g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            bad |= nonfinite_bits(x[e]);
+            x[e] = x[e] * inv;
+        }
+        reinterpret_cast<f32x4*>(g)[i] = x;
+    }
+    if (bi == 0 && (long)threadIdx.x < n - n4 * 4) {      // the 1-3 elements past the last full f32x4
+        const long i = n4 * 4 + threadIdx.x;
+        const float x = g[i];
+        bad |= nonfinite_bits(x);
+        g[i] = x * inv;
+    }
+    const unsigned long long w = __ballot(bad);            // wave -> one bit per wave in LDS -> at most one store per block
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w != 0ull;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int any = 0;
+#pragma unroll
+        for (int k = 0; k < LS_BLOCK / 64; ++k) any |= red[k];
+        if (any) st[0] = 1;                                // every writer stores the same value: no atomic needed
+    }
+}
+// Adam with the step skipped when st[0] (found_inf) is set; lr_t(k) of iteration k = st[3] + 1 from the host-written table
+// lr_table[j] = lr_t(j + 1), j < table_len (the last entry is lr itself: every later iteration uses it)
+__global__ void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                    long n4, long n, const float* __restrict__ lr_table, int table_len, const int* __restrict__ st,
+                                    float b1, float b2, float eps) {
+    if (st[0]) return;
+    const int k = st[3] + 1;
+    const int j = k < 1 ? 0 : (k < table_len ? k : table_len) - 1;      // (the count only grows from 0; clamped all the same)
+    const float lr_t = lr_table[j];
+    // the update of adam_kernel, statement for statement (bitwise equal results: tests/test_dynamic_loss_scale.py)
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i], pp = reinterpret_cast<f32x4*>(p)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            mm[e] = b1 * mm[e] + (1.f - b1) * gg[e];
+            vv[e] = b2 * vv[e] + (1.f - b2) * gg[e] * gg[e];
+            pp[e] = pp[e] - lr_t * mm[e] / (sqrtf(vv[e]) + eps);
+        }
+        reinterpret_cast<f32x4*>(m)[i] = mm; reinterpret_cast<f32x4*>(v)[i] = vv; reinterpret_cast<f32x4*>(p)[i] = pp;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (long i = n4 * 4; i < n; ++i) {
+            m[i] = b1 * m[i] + (1.f - b1) * g[i];
+            v[i] = b2 * v[i] + (1.f - b2) * g[i] * g[i];
+            p[i] = p[i] - lr_t * m[i] / (sqrtf(v[i]) + eps);
+        }
+    }
+}
+// the largest finite power of two: growth stops there
+#define LS_SCALE_MAX 1.7014118346046923e38f
+__global__ void loss_scale_update_kernel(float* __restrict__ scale, int* __restrict__ st, int growth_interval) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st[0]) {                                           // skipped step: back off (never below 1), restart the growth count
+        const float s = scale[0] * 0.5f;
+        scale[0] = s < 1.f ? 1.f : s;
+        st[1] = 0;
+        st[2] += 1;
+    } else {                                               // applied step: one more Adam iteration, grow after `growth_interval`
+        st[3] += 1;
+        const int c = st[1] + 1;
+        if (c >= growth_interval) {
+            if (scale[0] < LS_SCALE_MAX) scale[0] = scale[0] * 2.f;
+            st[1] = 0;
+        } else {
+            st[1] = c;
+        }
+    }
+    st[0] = 0;
+}
+
 // ---- power iteration pieces ---------------------------------------------------------------------------
 #define SPEC_KS 32
 // part[ks][n] = sum_{k in slice} W[k][n] * u[k]
@@ -196,6 +292,36 @@ __global__ void spec_grad_multi_kernel(SpecGradBatch b, const float* __restrict_
         dw[i] += x > 0.f ? s : (x < 0.f ? -s : 0.f);
     }
 }
+// the same with the factor scale * scale_dev[0] (the dynamic loss scale; a power of two, so the product is exact)
+__global__ void spec_grad_multi_s_kernel(SpecGradBatch b, const float* __restrict__ sgn, float scale, const float* __restrict__ scale_dev) {
+    const int z = blockIdx.y;
+    const float s = sgn[z] * (scale * scale_dev[0]);
+    const float* w = b.w[z];
+    float* dw = b.dw[z];
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < b.n[z]; i += (long)gridDim.x * blockDim.x) {
+        const float x = w[i];
+        dw[i] += x > 0.f ? s : (x < 0.f ? -s : 0.f);
+    }
+}
+
+static int spectral_grad4_s(const float* w0, const float* w1, const float* w2, const float* w3, const float* sgn, float* dw0, float* dw1,
+                            float* dw2, float* dw3, int n, long n0, long n1, long n2, long n3, float scale, const float* scale_dev, void* stream) {
+    if (n < 1 || n > SPEC_MAXP) return (int)hipErrorInvalidValue;
+    SpecGradBatch b;
+    const float* ws_[4] = {w0, w1, w2, w3};
+    float* ds_[4] = {dw0, dw1, dw2, dw3};
+    const long ns[4] = {n0, n1, n2, n3};
+    long mx = 0;
+    for (int i = 0; i < SPEC_MAXP; ++i) {
+        const int j = i < n ? i : 0;
+        b.w[i] = ws_[j]; b.dw[i] = ds_[j]; b.n[i] = i < n ? ns[i] : 0;
+        if (b.n[i] > mx) mx = b.n[i];
+    }
+    long blocks = (mx + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(spec_grad_multi_s_kernel, dim3((unsigned)blocks, n), dim3(256), 0, (hipStream_t)stream, b, sgn, scale, scale_dev);
+    return MMSEG_CHECK_LAUNCH();
+}
 
 extern "C" {
 
@@ -213,6 +339,50 @@ int mmseg_adam_p(float* p, const float* g, float* m, float* v, long n, const flo
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, n, 0.f, lr_t, b1, b2, eps);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// ---- dynamic loss scaling ----
+// g_i *= 1 / scale[0] over up to 8 arenas in one launch; st[0] = 1 if any element of any arena is +-inf or NaN (never cleared here).
+// Arenas must be 16-byte aligned (the f32x4 body); any length (the 1-3 tail elements are handled by the arena's first block).
+int mmseg_unscale_check8(float* g0, float* g1, float* g2, float* g3, float* g4, float* g5, float* g6, float* g7, long n0, long n1,
+                         long n2, long n3, long n4, long n5, long n6, long n7, int count, const float* scale, int* st, void* stream) {
+    if (count < 1 || count > LS_MAXA || scale == nullptr || st == nullptr) return (int)hipErrorInvalidValue;
+    float* gs[LS_MAXA] = {g0, g1, g2, g3, g4, g5, g6, g7};
+    const long ns[LS_MAXA] = {n0, n1, n2, n3, n4, n5, n6, n7};
+    UnscaleBatch b;
+    int blocks = 0;
+    for (int i = 0; i < LS_MAXA; ++i) {
+        b.blk0[i] = blocks;
+        b.g[i] = i < count ? gs[i] : gs[0];
+        b.n[i] = i < count ? ns[i] : 0;
+        if (i >= count) continue;
+        if (ns[i] < 0 || (ns[i] > 0 && (gs[i] == nullptr || ((uintptr_t)gs[i] & 15)))) return (int)hipErrorInvalidValue;
+        long nb = (ns[i] / 4 + LS_BLOCK - 1) / LS_BLOCK;   // one f32x4 per thread and pass; the largest arena loops
+        if (nb > 2048) nb = 2048;
+        if (nb < 1) nb = 1;
+        blocks += (int)nb;
+    }
+    b.blk0[LS_MAXA] = blocks;
+    hipLaunchKernelGGL(unscale_check_kernel, dim3((unsigned)blocks), dim3(LS_BLOCK), 0, (hipStream_t)stream, b, count, scale, st);
+    return MMSEG_CHECK_LAUNCH();
+}
+// mmseg_adam_p's update, skipped entirely (p, m, v untouched) when st[0] is set; lr_t = lr_table[min(st[3] + 1, table_len) - 1]
+int mmseg_adam_guarded(float* p, const float* g, float* m, float* v, long n, const float* lr_table, int table_len, const int* st,
+                       float b1, float b2, float eps, void* stream) {
+    if (lr_table == nullptr || st == nullptr || table_len < 1) return (int)hipErrorInvalidValue;
+    long blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(adam_guarded_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n / 4, n, lr_table,
+                       table_len, st, b1, b2, eps);
+    return MMSEG_CHECK_LAUNCH();
+}
+// end of a step: st[0] set -> scale = max(scale / 2, 1), growth count 0, skipped + 1; else iterations + 1, growth count + 1 and at
+// growth_interval scale * 2 (up to 2^127) and count 0.  st[0] cleared.
+int mmseg_loss_scale_update(float* scale, int* st, int growth_interval, void* stream) {
+    if (scale == nullptr || st == nullptr || growth_interval < 1) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scale, st, growth_interval);
     return MMSEG_CHECK_LAUNCH();
 }
 
@@ -295,6 +465,13 @@ int mmseg_spectral_grad4(const float* w0, const float* w1, const float* w2, cons
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(spec_grad_multi_kernel, dim3((unsigned)blocks, n), dim3(256), 0, (hipStream_t)stream, b, sgn, scale);
     return MMSEG_CHECK_LAUNCH();
+}
+// the same with the factor scale * scale_dev[0] (dynamic loss scale in device memory)
+int mmseg_spectral_grad4_s(const float* w0, const float* w1, const float* w2, const float* w3, const float* sgn, float* dw0, float* dw1,
+                           float* dw2, float* dw3, int n, long n0, long n1, long n2, long n3, float scale, const float* scale_dev,
+                           void* stream) {
+    if (scale_dev == nullptr) return (int)hipErrorInvalidValue;
+    return spectral_grad4_s(w0, w1, w2, w3, sgn, dw0, dw1, dw2, dw3, n, n0, n1, n2, n3, scale, scale_dev, stream);
 }
 int mmseg_spectral_grad(const float* w, const float* sgn, float scale, long n, float* dw, void* stream) {
     long blocks = (n + 255) / 256;

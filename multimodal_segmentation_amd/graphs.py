@@ -12,7 +12,9 @@ step lives in device memory the recorded kernels read:
     inference passes, are recorded the same way: `GraphedCall`);
   * values the step draws on the host (the noise of the sampling layer, `host_draw`) -> static buffers refilled from the same host
     generators in the same order, so a replayed run consumes exactly the random streams of an eager run;
-  * Adam's bias-corrected step size lr_t        -> one device float (`mmseg_adam_p`), written before the replay.
+  * Adam's bias-corrected step size lr_t        -> one device float (`mmseg_adam_p`), written before the replay;
+  * the dynamic loss scale (conf.loss_scale = 'dynamic', loss_scaler.py) -> already device state: the scale, the skip flag, the
+    counters and the Adam iteration count that indexes a device table of lr_t are read and updated by the recorded kernels.
 
 Python-side effects of a step (optimiser iteration count, weight / BatchNorm-state version counters that invalidate cached weight
 images) are repeated by the replay wrapper.  Results are bit-identical to the eager path (`tests/test_graph_capture.py`).
@@ -175,7 +177,8 @@ class FitGraph(object):
                 self._fill(b, x)
         for d in self.draws:                          # this step's host draws, in the order the step asks for them
             FitGraph._fill(d.buf, d.fn())
-        lr_dev = t.optimizer.begin_device_step(dev)   # iteration count + 1, lr_t of this step into the device scalar
+        # iteration count + 1, lr_t of this step into the device scalar; with the dynamic loss scale both live on the device already
+        lr_dev = t.optimizer.begin_device_step(dev) if t.scaler is None else None
         if self.graph is None:
             from . import ops as _ops
             _ops.bump_weight_version()               # every cached weight image is recomputed INSIDE the recording

@@ -189,6 +189,7 @@ class DAFNetExecutor(Executor):
             for swa_m in self.get_swa_models():
                 swa_m.on_epoch_end(self.epoch)
             self.validate(epoch_loss)
+            self.log_loss_scalers()
             for n in loss_names:
                 total_loss[n].append(np.mean([_f(v) for v in epoch_loss[n]]) if epoch_loss[n] else float('nan'))
             logs = {l: total_loss[l][-1] for l in loss_names}
@@ -205,6 +206,15 @@ class DAFNetExecutor(Executor):
                 self.save_models()
                 break
         return total_loss
+
+    def log_loss_scalers(self):
+        """conf.loss_scale = 'dynamic': each trainer's loss scale and skipped-step count, once per epoch (reads the device state:
+        one synchronisation per epoch, none inside the steps).  -> {trainer name: (scale, skipped steps)}"""
+        out = {}
+        for name, sc in self.model.loss_scalers():
+            out[name] = (sc.scale(), sc.skipped_steps())
+            log.info('Epoch %d: %s loss scale %g, %d skipped steps' % (self.epoch, name, out[name][0], out[name][1]))
+        return out
 
     def save_models(self, postfix=''):
         """Checkpoints hold the SWA clones, one file per component under <folder>/models/ (dafnet_executor.py:286-301)"""

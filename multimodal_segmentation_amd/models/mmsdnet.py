@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .. import costs, nn, ops
+from .. import costs, loss_scaler, nn, ops
 from ..model_components import anatomy_encoder, anatomy_fuser, modality_encoder, segmentor, decoder
 from ..utils.rng import global_rng
 from .basenet import BaseNet
@@ -59,16 +59,22 @@ class MMSDNet(BaseNet):
         from ..parallel import dp
         dp.set_sync_bn(self.conf.get('sync_bn', False))
 
+    _TRAINERS = ('supervised_trainer', 'unsupervised_trainer', 'Z_Regressor', 'D_Mask_trainer', 'D_Image1_trainer', 'D_Image2_trainer')
+
     def apply_loss_scale(self):
         """fp16 compute: static loss scale (conf.loss_scale, default 1024) on every trainer, so that small gradients survive
-        the rounding of the data-gradient operands to fp16; bf16 / fp32 have fp32's exponent range and need none."""
-        scale = float(self.conf.get('loss_scale', 1024.0)) if self.conf.get('compute_dtype', 'fp32') == 'fp16' else 1.0
-        for name in ('supervised_trainer', 'unsupervised_trainer', 'Z_Regressor', 'D_Mask_trainer', 'D_Image1_trainer',
-                     'D_Image2_trainer'):
+        the rounding of the data-gradient operands to fp16; bf16 / fp32 have fp32's exponent range and need none.
+        conf.loss_scale = 'dynamic' (build-defined; conf.loss_scale_init, a power of two, default 1024; conf.loss_scale_growth_interval,
+        default 2000): every trainer gets a device-resident loss_scaler.LossScaler instead (skips steps with non-finite gradients)."""
+        dynamic = loss_scaler.parse_conf(self.conf)          # (validated in every compute mode; only fp16 uses it)
+        fp16 = self.conf.get('compute_dtype', 'fp32') == 'fp16'
+        scale = float(self.conf.get('loss_scale', 1024.0)) if fp16 and dynamic is None else 1.0
+        for name in self._TRAINERS:
             t = getattr(self, name, None)
             if t is not None:
                 t.precision = getattr(self, '_precision', None)
                 t.loss_scale = scale
+                t.scaler = loss_scaler.LossScaler(t.optimizer, t.device, *dynamic) if fp16 and dynamic is not None else None
                 # conf.hip_graphs (build-defined, default False): record each trainer step into a hipGraph and replay it (graphs.py)
                 t.use_graph = bool(self.conf.get('hip_graphs', False))
         for m in self._generator_models() + [d for d in (getattr(self, 'D_Mask', None), getattr(self, 'D_Image1', None),
@@ -81,6 +87,15 @@ class MMSDNet(BaseNet):
         self.build_generators()
         self.apply_loss_scale()
         self.load_models()
+
+    def loss_scalers(self):
+        """[(trainer name, LossScaler)] of the dynamic loss scale; empty in every other mode"""
+        out = []
+        for name in self._TRAINERS:
+            t = getattr(self, name, None)
+            if t is not None and getattr(t, 'scaler', None) is not None:
+                out.append((name, t.scaler))
+        return out
 
     # ---- checkpoint: one file for the whole supervised trainer (mmsdnet.py:42-60) --------------------------------
     def _all_component_models(self):

@@ -42,6 +42,9 @@ class Trainer(object):
         # static loss scale (fp16 compute mode): every seed gradient is multiplied by it, the gradient arenas are divided by it
         # before the optimiser step; 1.0 = off
         self.loss_scale = 1.0
+        # conf.loss_scale = 'dynamic' (fp16): a loss_scaler.LossScaler owning the device-resident scale, the skipped-step logic and
+        # this trainer's Adam iteration count; the seeds are then multiplied by its device scale (loss_scale stays 1.0).  None = static
+        self.scaler = None
         # (compute_dtype, 16-bit activation storage) of the model wrapper this trainer belongs to: every fit / predict runs inside
         # ops.precision_scope(self.precision); None = whatever the library is set to
         self.precision = None
@@ -57,17 +60,18 @@ class Trainer(object):
 
     def _loss_and_grad(self, spec, pred, target):
         gs = spec.weight * self.loss_scale            # scale of the returned gradient only; the loss value is unscaled
+        sd = self.scaler.scale_dev if self.scaler is not None else None     # dynamic: times the device scale
         if spec.kind == 'dice_bce':
             return ops.seg_loss(pred, target, self.num_masks, 0.01, gs, class_sum_hook=dp.class_sum_hook(),
-                                n_pix_global=pred.numel() // pred.shape[-1] * dp.world_size())
+                                n_pix_global=pred.numel() // pred.shape[-1] * dp.world_size(), scale_dev=sd)
         if spec.kind == 'dice':
-            return ops.seg_loss(pred, target, self.num_masks, 0.0, gs)
+            return ops.seg_loss(pred, target, self.num_masks, 0.0, gs, scale_dev=sd)
         if spec.kind == 'mse':
-            return ops.diff_loss(pred, target, 'mse', gs)
+            return ops.diff_loss(pred, target, 'mse', gs, scale_dev=sd)
         if spec.kind == 'mae':
-            return ops.diff_loss(pred, target, 'mae', gs)
+            return ops.diff_loss(pred, target, 'mae', gs, scale_dev=sd)
         if spec.kind == 'ypred':
-            return ops.diff_loss(pred, 0.0, 'mean', gs)
+            return ops.diff_loss(pred, 0.0, 'mean', gs, scale_dev=sd)
         raise ValueError(spec.kind)
 
     def _prep_target(self, t, pred):
@@ -117,13 +121,20 @@ class Trainer(object):
                 hist.record(spec.name + '_loss', loss)
             torch.autograd.backward(outs, grads)
         for d in self.regularised:
-            for loss in d.regulariser_losses(accumulate_grad=d in self.train_models, grad_scale=self.loss_scale):
+            kw = {} if self.scaler is None else {'grad_scale_dev': self.scaler.scale_dev}
+            for loss in d.regulariser_losses(accumulate_grad=d in self.train_models, grad_scale=self.loss_scale, **kw):
                 terms.append((1.0, loss))
         dp.finish(tracker)
-        if self.loss_scale != 1.0:
-            for m in self.train_models:
-                ops.axpby(m.grad_arena, m.grad_arena, 1.0 / self.loss_scale, 0.0, out=m.grad_arena)
-        self.optimizer.step(self.train_models, lr_dev=lr_dev)
+        if self.scaler is not None:
+            # dynamic loss scale: unscale + non-finite check AFTER the all-reduce (every rank sees the same arenas and skips together),
+            # then Adam guarded by the device flag and the scaler update -- no host read
+            self.scaler.unscale_(self.train_models)
+            self.scaler.step(self.train_models)
+        else:
+            if self.loss_scale != 1.0:
+                for m in self.train_models:
+                    ops.axpby(m.grad_arena, m.grad_arena, 1.0 / self.loss_scale, 0.0, out=m.grad_arena)
+            self.optimizer.step(self.train_models, lr_dev=lr_dev)
         hist.record('loss', nn_total(terms))
         self.last_outputs = [o.detach() for o in outs]
         return hist

@@ -430,15 +430,20 @@ class Adam(object):
         ops.fill_(self._lr_dev, self._lr_t())
         return self._lr_dev
 
+    def moments(self, m):
+        """(m, v) of model m's arena, zero-initialised on first use"""
+        st = self.state.get(m.uid)
+        if st is None:
+            st = (ops.fill_(torch.empty_like(m.arena), 0.0), ops.fill_(torch.empty_like(m.arena), 0.0))
+            self.state[m.uid] = st
+        return st
+
     def step(self, models, lr_dev=None):
         if lr_dev is None:
             self.iterations += 1
         lr_t = self._lr_t() if lr_dev is None else lr_dev
         for m in models:
-            st = self.state.get(m.uid)
-            if st is None:
-                st = (ops.fill_(torch.empty_like(m.arena), 0.0), ops.fill_(torch.empty_like(m.arena), 0.0))
-                self.state[m.uid] = st
+            st = self.moments(m)
             ops.adam_step(m.arena, m.grad_arena, st[0], st[1], lr_t, self.beta_1, self.beta_2, self.epsilon, owner=m.uid)
 
 

@@ -1243,10 +1243,11 @@ def instnorm_spade(x, gamma=None, beta=None, act_alpha=-1.0):
 # ------------------------------------------------------------------------------------------------------
 # losses: value (device scalar) + gradient w.r.t. the prediction, no autograd node
 # ------------------------------------------------------------------------------------------------------
-def seg_loss(pred, target, num_masks, lambda_bce, scale, class_sum_hook=None, n_pix_global=None, want_grad=True):
+def seg_loss(pred, target, num_masks, lambda_bce, scale, class_sum_hook=None, n_pix_global=None, want_grad=True, scale_dev=None):
     """make_combined_dice_bce (lambda_bce = 0.01) or make_dice_loss_fnc (lambda_bce = 0) of costs.py.
     `class_sum_hook(t)` may all-reduce the batch-global class sums in place (data-parallel training).
-    -> (loss[1], dpred or None); dpred already multiplied by `scale` (loss weight)."""
+    -> (loss[1], dpred or None); dpred already multiplied by `scale` (loss weight) and, if given, by the device scalar `scale_dev`
+    (the dynamic loss scale, loss_scaler.py)."""
     pred, target = _c(pred), _c(target)
     B, H, W, C = pred.shape
     dev = pred.device
@@ -1264,8 +1265,12 @@ def seg_loss(pred, target, num_masks, lambda_bce, scale, class_sum_hook=None, n_
     dpred = None
     if want_grad:
         dpred = _new(pred.shape, pred)
-        N.call('mmseg_segloss_grad', pred, target, coef, dpred, B, H * W, C, num_masks, float(scale),
-               int(lambda_bce != 0.0))
+        if scale_dev is None:
+            N.call('mmseg_segloss_grad', pred, target, coef, dpred, B, H * W, C, num_masks, float(scale),
+                   int(lambda_bce != 0.0))
+        else:
+            N.call('mmseg_segloss_grad_s', pred, target, coef, dpred, B, H * W, C, num_masks, float(scale), scale_dev,
+                   int(lambda_bce != 0.0))
     return loss, dpred
 
 
@@ -1410,9 +1415,9 @@ def row_dot(w, ls):
 _DIFF_MODE = {'mae': 0, 'mse': 1, 'mean': 2}
 
 
-def diff_loss(pred, target, mode, scale, want_grad=True):
+def diff_loss(pred, target, mode, scale, want_grad=True, scale_dev=None):
     """keras 'mae' / 'mse' (target tensor or python float) or mean(pred) (costs.ypred).
-    -> (loss[1], dpred or None), dpred = scale * dloss/dpred."""
+    -> (loss[1], dpred or None), dpred = scale [* scale_dev[0]] * dloss/dpred."""
     pred = _c(pred)
     n = pred.numel()
     t, tc = (None, float(target)) if not isinstance(target, torch.Tensor) else (_c(target), 0.0)
@@ -1425,7 +1430,10 @@ def diff_loss(pred, target, mode, scale, want_grad=True):
     if want_grad:
         dpred = _new(pred.shape, pred)
         g = {0: 1.0 / n, 1: 1.0 / n, 2: 1.0 / n}[_DIFF_MODE[mode]] * scale
-        N.call('mmseg_diffloss_grad', pred, t, tc, n, _DIFF_MODE[mode], float(g), dpred)
+        if scale_dev is None:
+            N.call('mmseg_diffloss_grad', pred, t, tc, n, _DIFF_MODE[mode], float(g), dpred)
+        else:
+            N.call('mmseg_diffloss_grad_s', pred, t, tc, n, _DIFF_MODE[mode], float(g), scale_dev, dpred)
     return loss, dpred
 
 
@@ -1454,11 +1462,15 @@ def spectral_reg_multi(ws_, u0s, alpha=10.0):
     return loss, sgn
 
 
-def spectral_reg_grad_accumulate(ws_, sgn, grads, scale=1.0):
-    """grads[i] += scale * d penalty_i / d W_i  (one launch)"""
+def spectral_reg_grad_accumulate(ws_, sgn, grads, scale=1.0, scale_dev=None):
+    """grads[i] += scale [* scale_dev[0]] * d penalty_i / d W_i  (one launch)"""
     n = len(ws_)
     pad = lambda lst, fill: list(lst) + [fill] * (4 - n)
-    N.call('mmseg_spectral_grad4', *pad(ws_, ws_[0]), sgn, *pad(grads, grads[0]), n, *pad([w.numel() for w in ws_], 0), float(scale))
+    if scale_dev is None:
+        N.call('mmseg_spectral_grad4', *pad(ws_, ws_[0]), sgn, *pad(grads, grads[0]), n, *pad([w.numel() for w in ws_], 0), float(scale))
+    else:
+        N.call('mmseg_spectral_grad4_s', *pad(ws_, ws_[0]), sgn, *pad(grads, grads[0]), n, *pad([w.numel() for w in ws_], 0),
+               float(scale), scale_dev)
 
 
 def spectral_reg_grad(w, sgn, scale=1.0):
@@ -1476,6 +1488,26 @@ def adam_step(p, g, m, v, lr_t, beta_1=0.9, beta_2=0.999, eps=1e-7, owner=None):
     else:
         N.call('mmseg_adam', p, g, m, v, p.numel(), float(lr_t), float(beta_1), float(beta_2), float(eps))
     bump_weight_version(owner)
+
+
+def unscale_check(arenas, scale_dev, state):
+    """dynamic loss scale (loss_scaler.py): arenas[i] *= 1 / scale_dev[0] in place, state[0] = 1 if any element is non-finite.
+    Up to 8 flat fp32 arenas in one launch."""
+    n = len(arenas)
+    assert 1 <= n <= 8
+    pad = lambda lst, fill: list(lst) + [fill] * (8 - n)
+    N.call('mmseg_unscale_check8', *pad(arenas, arenas[0]), *pad([a.numel() for a in arenas], 0), n, scale_dev, state)
+
+
+def adam_guarded(p, g, m, v, lr_table, state, beta_1=0.9, beta_2=0.999, eps=1e-7, owner=None):
+    """adam_step skipped on the device when state[0] (found_inf) is set; lr_t from lr_table at the device iteration count state[3] + 1"""
+    assert p.numel() == g.numel() == m.numel() == v.numel()
+    N.call('mmseg_adam_guarded', p, g, m, v, p.numel(), lr_table, lr_table.numel(), state, float(beta_1), float(beta_2), float(eps))
+    bump_weight_version(owner)
+
+
+def loss_scale_update(scale_dev, state, growth_interval):
+    N.call('mmseg_loss_scale_update', scale_dev, state, int(growth_interval))
 
 
 def fill_(t, value):
