@@ -8,7 +8,11 @@ incl. the fake-pool generation, Adam updates and BatchNorm moving-average update
 
     python bench.py [--gpus N] [--steps K] [--warmup W]         # N > 1: starts its N ranks itself (child torch.distributed.run)
     python bench.py ... --dump-outputs DIR                       # + the last timed step's losses and (sampled) weights as DIR/*.npy
+    python bench.py ... --full                                   # + the measurements that take runs of their own (cpu_baseline, multi_stream)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps, writes its outputs (--dump-outputs) and prints the line; whatever needs more than
+the timed region itself waits for --full.
 
 Extra fields of the JSON line:
   roofline         -- the DOMINANT kernel instance of the step (largest GPU time), under the name rocprofv3 reports for it, e.g.
@@ -18,9 +22,9 @@ Extra fields of the JSON line:
                       (profiles/r03_conv_traffic.json, keyed by workload and kernel name; null when the workload was not profiled)
   roofline_kernels -- the same entry for every convolution kernel instance with >= 0.5 ms of GPU time per step
   roofline_family  -- the two families of round 1 (all forward + data-gradient launches / all weight-gradient launches)
-  cpu_baseline     -- the oracle (torch-CPU restatement, "port") timed on this box's host cores on a bounded sample
-  multi_stream     -- informational: the same iterations re-timed with conf.multi_stream (discriminator phases on concurrent HIP streams,
-                      bit-identical results); NOT `value` -- time-shared kernels would misstate the per-kernel roofline entries
+  cpu_baseline     -- --full: the oracle (torch-CPU restatement, "port") timed on the host's cores on a bounded sample
+  multi_stream     -- --full, informational: the same iterations re-timed with conf.multi_stream (discriminator phases on concurrent HIP
+                      streams, bit-identical results); NOT `value` -- time-shared kernels would misstate the per-kernel roofline entries
 """
 import argparse
 import json
@@ -382,8 +386,11 @@ def main():
                          "another stream's kernels no longer measures that kernel: the per-kernel roofline entries would read low)")
     ap.add_argument('--no-multi-stream', action='store_true',
                     help='the 16-bit modes (--dtype bf16 | f16) run with conf.multi_stream by default (the product default for reduced precision); this keeps them on one stream')
-    ap.add_argument('--no-multi-stream-region', action='store_true', help='skip the informational second timed region with conf.multi_stream')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the CPU baseline (the oracle in a child process) and the informational '
+                         'multi-stream region; a plain run does neither')
+    ap.add_argument('--no-multi-stream-region', action='store_true', help='with --full: skip the informational second timed region with conf.multi_stream')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-conv-timer', action='store_true')
     ap.add_argument('--conv-breakdown', action='store_true', help='per-shape convolution table on stderr')
     ap.add_argument('--conv-timer-stride', type=int, default=7, help='time every n-th convolution launch with HIP events')
@@ -550,9 +557,10 @@ def main():
     value = pairs / dt
     # informational second region (not `value`): the same iterations with conf.multi_stream -- the discriminator phases on concurrent
     # HIP streams, bit-identical results.  Kept out of the headline because per-kernel elapsed times of time-shared kernels would
-    # misstate the `roofline` entries.
+    # misstate the `roofline` entries.  --full only: it trains on for another 2 + min(steps, 10) iterations.
     multi = None
-    if args.model == 'dafnet' and not args.multi_stream and not args.graphs and not args.no_multi_stream_region and not distributed:
+    if (args.full and args.model == 'dafnet' and not args.multi_stream and not args.graphs and not args.no_multi_stream_region
+            and not distributed):
         conf['multi_stream'] = True
         for _ in range(2):
             ex.train_batch(losses)
@@ -705,7 +713,7 @@ def main():
         if committed:
             committed['note'] = 'from committed profiles of this command, not measured in this run'
             line['from_committed_profile'] = committed
-        if world == 1 and not args.no_cpu_baseline and args.model == 'dafnet':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == 'dafnet':
             _progress('cpu baseline (oracle, bounded sample)')
             line['cpu_baseline'] = cpu_baseline(H, args.decoder, args.batch)
         print(json.dumps(line))

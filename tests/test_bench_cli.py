@@ -162,3 +162,39 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
         a = np.load(str(out_dir / f))
         assert f.endswith('.npy') and a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
     assert np.load(str(out_dir / 'loss_dis_M.npy')).size == 2          # two mask-discriminator fits per DAFNet step
+
+
+def test_launcher_passes_full_to_the_ranks():
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--full', '--dry-run'],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    cmd = json.loads(out.stdout.decode().strip().splitlines()[-1])['cmd']
+    assert cmd[cmd.index(os.path.join(ROOT, 'bench.py')) + 1:] == ['--gpus', '2', '--full']
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_adds_the_rest():
+    """A plain run carries only what its own timed region measures; --full adds the CPU baseline and the informational
+    multi-stream region on top of the same headline fields"""
+    env = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
+        env.pop(k, None)
+    lines = {}
+    for extra in ([], ['--full']):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--size', '64', '--steps', '2', '--warmup', '1'] + extra
+        out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr.decode()[-3000:]
+        got = [l for l in out.stdout.decode().splitlines() if l.startswith('{')]
+        assert len(got) == 1, out.stdout.decode()[-2000:]
+        lines[bool(extra)] = json.loads(got[0])
+    plain, full = lines[False], lines[True]
+    for d in (plain, full):
+        assert d['steps'] == 2 and d['warmup'] == 1 and d['value'] > 0 and d['ms_per_step'] > 0 and d['roofline']['frac'] > 0
+        assert d['higher_is_better'] is True and d['dtype'] == 'f32' and d['unit'] == 'paired slices/s'
+    assert plain['metric'] == full['metric']
+    assert 'cpu_baseline' not in plain and 'multi_stream' not in plain
+    assert full['cpu_baseline']['value'] > 0 and full['cpu_baseline']['kind'] == 'port'
+    assert full['multi_stream']['value'] > 0 and full['multi_stream']['steps'] == 2

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EV = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'gpurun_out', 'ev5')
 P = os.path.join(ROOT, 'profiles')
 
-LINES = [('bench_f32', 'python bench.py --steps 20 --warmup 5 (headline: DAFNet-FiLM 256x256 bs8 fp32)'),
+LINES = [('bench_f32', 'python bench.py --full --steps 20 --warmup 5 (headline: DAFNet-FiLM 256x256 bs8 fp32)'),
          ('bench_f32_multistream', '--multi-stream (fp32, discriminator phases on concurrent streams)'),
          ('bench_bf16_act16', '--dtype bf16 --act16 (FiLM; multi-stream is the default of the 16-bit modes)'),
          ('bench_spade_f32', '--decoder spade (fp32)'),

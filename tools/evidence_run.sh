@@ -4,7 +4,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/ev4; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
-python3 $R/bench.py --steps 20 --warmup 3 > $O/bench_f32.json 2> $O/bench_f32.err
+python3 $R/bench.py --full --steps 20 --warmup 3 > $O/bench_f32.json 2> $O/bench_f32.err
 echo bench done
 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o b -- python3 $R/bench.py --no-cpu-baseline --steps 7 --warmup 3 > $O/trace_bench.json 2> $O/trace_bench.err
 rocprofv3 --kernel-trace --output-format csv -d $O/trace_graphs -o b -- python3 $R/bench.py --no-cpu-baseline --graphs --steps 7 --warmup 3 > $O/trace_graphs_bench.json 2> $O/trace_graphs_bench.err
