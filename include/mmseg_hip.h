@@ -377,6 +377,26 @@ int mmseg_adam_guarded(float* p, const float* g, float* m, float* v, long n, con
  * growth_interval scale *= 2 (at most 2^127), st[1] = 0.  Clears st[0]. */
 int mmseg_loss_scale_update(float* scale, int* st, int growth_interval, void* stream);
 
+/* ---- volume preprocessing (csrc/preprocess.hip): loaders/chaos.py:324-343 (resample = skimage.transform.rescale, order 1 for
+ * images / order 0 for labels, mode='constant', no anti-aliasing), 303-319 (grey label value -> one binary channel per organ),
+ * 242-246 (every slice to [-1, 1] by the min / max of the whole resampled slice), 248-264 (utils/data_utils.crop_same, mode 'equal',
+ * pad_mode 'edge').  One call handles the S raw slices [S,H,W] of one (volume, modality) and writes its channels of the NHWC
+ * containers the gather kernels read; the resampled RH x RW frame (RH = round(H * old_res / target_res), decided by the caller) is
+ * never stored.  Source coordinate of resampled pixel d: (d + 0.5) * (in / out) - 0.5 in fp64; outside [0, in-1] -> 0.
+ * Per axis the final index o reads resampled index lo + clamp(o - before, 0, kept - 1): crop (lo), the odd-surplus quirk of
+ * data_utils._crop (kept = size - 1) and edge padding (before) in one map; 0 <= lo, kept >= 1, lo + kept <= R, 0 <= before < O.
+ * The label entry point is the one place where a tensor is not fp32: lab holds the uint8 grey values as read from disk. */
+long mmseg_preprocess_workspace_floats(int S, int RH, int RW);
+/* ws[S][blocks][2] = (min, max) partials of the bilinearly resampled slices; read by mmseg_preprocess_image with the same S, RH, RW */
+int mmseg_preprocess_minmax(const float* img, float* ws, int S, int H, int W, int RH, int RW, void* stream);
+/* out [S,OH,OW,C], channel ch = 2 * (v - min) / (max - min) - 1 (a constant slice: -1) */
+int mmseg_preprocess_image(const float* img, const float* ws, float* out, int S, int H, int W, int RH, int RW, int OH, int OW, int lo_r,
+                           int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch, void* stream);
+/* out [S,OH,OW,C], channel ch0 + k = (nearest label (tap floor(c + 0.5)) == values[k]) as 0 / 1, k < K <= 16; values [K] int32 on
+ * the device */
+int mmseg_preprocess_label(const unsigned char* lab, const int* values, float* out, int S, int H, int W, int RH, int RW, int OH, int OW,
+                           int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch0, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,11 +16,11 @@ CSRC_DIR = os.path.join(_PKG_DIR, 'csrc')
 # MMSEG_HIP_LIB: another build of the same library (A/B measurements of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get('MMSEG_HIP_LIB') or os.path.join(CSRC_DIR, 'libmmseg_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'mmseg_hip.h')
-SOURCES = ('conv.hip', 'pointwise.hip', 'norm.hip', 'act16.hip', 'dense.hip', 'tps.hip', 'augment.hip', 'loss.hip', 'pairloss.hip', 'optim.hip')
+SOURCES = ('conv.hip', 'pointwise.hip', 'norm.hip', 'act16.hip', 'dense.hip', 'tps.hip', 'augment.hip', 'preprocess.hip', 'loss.hip', 'pairloss.hip', 'optim.hip')
 
 _CTYPES = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'void*': ctypes.c_void_p,
            'const float*': ctypes.c_void_p, 'float*': ctypes.c_void_p, 'const int*': ctypes.c_void_p, 'int*': ctypes.c_void_p, 'const void*': ctypes.c_void_p,
-           'const long long*': ctypes.c_void_p, 'const double*': ctypes.c_void_p}
+           'const long long*': ctypes.c_void_p, 'const double*': ctypes.c_void_p, 'const unsigned char*': ctypes.c_void_p}
 
 
 class NativeLibraryError(RuntimeError):
@@ -100,7 +100,8 @@ def _ptr(t, device, ctype='float*'):
             raise ValueError('kernel operand (%s) must be a contiguous fp32 / bf16 / fp16 tensor on %s (got %s %s)' % (ctype, device, t.dtype, t.device))
         return t.data_ptr()
     want = torch.int64 if 'long long' in ctype else (torch.int32 if 'int' in ctype else
-                                                     (torch.float64 if 'double' in ctype else torch.float32))
+                                                     (torch.float64 if 'double' in ctype else
+                                                      (torch.uint8 if 'unsigned char' in ctype else torch.float32)))
     if t.dtype != want or not t.is_contiguous() or t.device != device:
         raise ValueError('kernel operand (%s) must be a contiguous %s tensor on %s (got %s %s contiguous=%s)'
                          % (ctype, want, device, t.dtype, t.device, t.is_contiguous()))

@@ -17,9 +17,10 @@ def discriminator(name, filters, shape):
 
 
 def assemble(folder, model, executor, d_mask_filters, d_image_filters=None, **overrides):
-    loader = loader_factory.init_loader('chaos')
     p = dict(COMMON, folder=folder, model=model, executor=executor)
     p.update(overrides)
+    # a folder registered for the configured data set (loaders.data_conf) brings its own input_shape and num_masks (dataset.json)
+    loader = loader_factory.init_loader(p['dataset_name']) or loader_factory.init_loader('chaos')
     r = p['image_downsample']
     h, w, c = loader.input_shape
     shape = (int(h / r), int(w / r), c)

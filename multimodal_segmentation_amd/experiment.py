@@ -2,6 +2,10 @@
 
     python experiment.py --config <module in configuration/> --split <int> [--l_mix f] [--test b]
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
+                         [--data_folder PATH] [--test_data_folder PATH]
+
+`--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
+every configuration trains and tests on the synthetic volumes.
 
 The run folder name and the config mutations follow Experiment.get_config (experiment.py:31-72):
 `<folder>[_randomise][_automatedpairing]_l<l_mix>_<modality>_split<split>` with dots stripped, n_pairs = 3 under automated
@@ -31,6 +35,8 @@ def parse_arguments(argv=None):
     ap.add_argument('--l_mix', help='fraction of labelled volumes')
     ap.add_argument('--automatedpairing', type=bool, help='learn the pairing weights (n_pairs = 3)')
     ap.add_argument('--randomise', type=bool, help='randomise the multimodal pairs')
+    ap.add_argument('--data_folder', help='folder of exported volumes (dataset.json + .npz) to train, validate and test on')
+    ap.add_argument('--test_data_folder', help='another folder of exported volumes for the test pass')
     return ap.parse_args(argv)
 
 
@@ -69,13 +75,49 @@ def resolve(subpackage, dotted):
     return getattr(importlib.import_module('%s.%s.%s' % (_PKG, subpackage, module)), cls)
 
 
+def register_data_folders(module, args):
+    """Fill loaders.data_conf (data set name -> folder, the reference's loaders/base_loader.py:5-7) from `--data_folder` /
+    `--test_data_folder` or the configuration's `data_folder` / `test_data_folder`.  The folder is registered under the configured
+    dataset_name and test_dataset.  A separate test folder whose configured name is the training data set's is registered under
+    the `name` of its own dataset.json, which is returned as the test_dataset to use (else None)."""
+    from .loaders import data_conf
+    from .loaders.volume_folder import read_manifest
+    named = module.get()                  # without a registered folder: only the names and folders are read from it
+    folder = getattr(args, 'data_folder', None) or named.get('data_folder')
+    test_folder = getattr(args, 'test_data_folder', None) or named.get('test_data_folder')
+    train_name = named['dataset_name']
+    test_name = getattr(args, 'test_dataset', None) or named.get('test_dataset', train_name)
+    if folder:
+        data_conf[train_name] = folder
+    if not test_folder or (folder and os.path.abspath(test_folder) == os.path.abspath(folder)):
+        if folder:
+            data_conf[test_name] = folder
+        return None
+    if test_name != train_name:
+        data_conf[test_name] = test_folder
+        return None
+    own_name = read_manifest(test_folder)['name']
+    if own_name == train_name:
+        raise ValueError('the test folder %s carries the name of the training data set (%r): give its dataset.json a "name" of its '
+                         'own' % (test_folder, own_name))
+    data_conf[own_name] = test_folder
+    return own_name
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
 
     # ---- configuration --------------------------------------------------------------------------------------------
     def get_config(self, split, args):
-        conf = EasyDict(importlib.import_module('%s.configuration.%s' % (_PKG, args.config)).get())
+        module = importlib.import_module('%s.configuration.%s' % (_PKG, args.config))
+        test_dataset = register_data_folders(module, args)      # before get(): the configuration reads shapes from the loader
+        conf = EasyDict(module.get())
+        if test_dataset is not None:
+            conf.test_dataset = test_dataset
+        from .loaders import data_conf
+        if data_conf.get(conf.dataset_name):
+            conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')

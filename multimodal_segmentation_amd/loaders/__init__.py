@@ -1,0 +1,8 @@
+"""Data containers and loaders (reference loaders/).
+
+`data_conf` mirrors the dict of the same name in the reference's loaders/base_loader.py:5-7: data set name -> folder that holds
+it.  It starts empty, so every configuration trains on the synthetic volumes; `experiment.py --data_folder PATH` (or
+`conf.data_folder`) registers a folder in the format of loaders/volume_folder.py under the configured data set name, and
+`loader_factory.init_loader(name)` then returns a loader that reads it."""
+
+data_conf = {}

@@ -1,6 +1,8 @@
 """Loader registry (reference loaders/loader_factory.py).  Only the shape/label metadata of the CHAOS loader is needed
 by the hot path (configuration/*.py read input_shape and num_masks from it); reading DICOM volumes is out of scope
-(SURVEY section 2 row 26).  'synthetic' generates the seeded synthetic slices of SURVEY 8(d)."""
+(SURVEY section 2 row 26).  'synthetic' generates the seeded synthetic slices of SURVEY 8(d).  A data set name with a folder
+registered in `loaders.data_conf` gets a loaders/volume_folder.VolumeFolderLoader that reads that folder."""
+from . import data_conf
 
 
 class ChaosLoader(object):
@@ -14,6 +16,9 @@ class ChaosLoader(object):
 
 
 def init_loader(dataset):
+    if data_conf.get(dataset):
+        from .volume_folder import VolumeFolderLoader      # imported on demand: it needs the kernel bindings
+        return VolumeFolderLoader(data_conf[dataset])
     if dataset in ('chaos', 'synthetic'):
         return ChaosLoader()
     return None

@@ -1,0 +1,206 @@
+"""Loader of volumes exported to a folder, with the surface of the reference's `Loader` (loaders/base_loader.py:10-89) and the
+preprocessing of its CHAOS loader (loaders/chaos.py `_load_volume`, `resample`, `load_all_modalities_concatenated`), run on the
+device (csrc/preprocess.hip).  Reading DICOM / PNG stays out of scope: a folder holds arrays ("Volume folders").
+
+    <root>/dataset.json      settings only: name, modalities (2 or 3), label_values (one grey value per organ; everything else is
+                             background, chaos.py:303-319), target_resolution [mm, mm], input_shape, splits (a list of
+                             {training, validation, test} lists of volume ids, chaos.py:32-48) and
+                             volumes: {"<id>": {"<modality>": {"file": "<name>.npz", "slices": [[start, stop], ...]}}}
+    <root>/<name>.npz        image [S,H,W] (any integer or float dtype), label [S,H,W] uint8 grey values, resolution [2] mm per
+                             pixel along rows and columns
+
+`slices` (optional) lists [start, stop) ranges applied in order: how a user states which slices of the acquisitions show the same
+anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all modalities of a volume must hold the same number of
+slices.  S, H, W and the resolution may differ between volumes and between modalities.
+
+Per (volume, modality) the raw slices are uploaded once through pinned memory and three launches write the volume's share of the
+NHWC containers [N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map)."""
+import json
+import logging
+import os
+
+import numpy as np
+import torch
+
+from .. import nn, ops
+from .MultimodalPairedData import MultimodalPairedData
+from .data import Data
+
+log = logging.getLogger('volume_folder')
+
+SPLIT_TYPES = ('training', 'validation', 'test', 'all')
+MANIFEST = 'dataset.json'
+
+
+def resampled_size(n, old_res, new_res):
+    """np.round(n * scale), scale = old_res / new_res: skimage.transform.rescale's output extent (half to even)"""
+    return int(np.round(n * (float(old_res) / float(new_res))))
+
+
+def crop_pad_map(resampled, target):
+    """(lo, kept, before) of utils/data_utils.crop_same(mode='equal', pad_mode='edge') along one axis: final index o reads
+    resampled index lo + clamp(o - before, 0, kept - 1).  A surplus removes ceil(diff / 2) pixels from BOTH ends
+    (data_utils._crop), so an odd surplus keeps target - 1 pixels and the last one is repeated (_pad: floor(1 / 2) = 0 before)."""
+    r, n = int(resampled), int(target)
+    if r > n:
+        lo = int(np.ceil((r - n) / 2))
+        if r - 2 * lo < 1:
+            raise ValueError('cropping %d pixels to %d leaves nothing (%d are removed from both ends)' % (r, n, lo))
+        return lo, r - 2 * lo, 0
+    return 0, r, int((n - r) / 2)
+
+
+def has_data(name):
+    """True when a folder is registered for data set `name` (loaders.data_conf)"""
+    from . import data_conf
+    return bool(name) and bool(data_conf.get(name))
+
+
+def read_manifest(root):
+    path = os.path.join(root, MANIFEST)
+    if not os.path.isfile(path):
+        raise FileNotFoundError('%s: no %s (see INTEGRATION.md, "Volume folders")' % (root, MANIFEST))
+    with open(path) as f:
+        m = json.load(f)
+    for key in ('name', 'modalities', 'label_values', 'target_resolution', 'input_shape', 'splits', 'volumes'):
+        if key not in m:
+            raise ValueError('%s: missing key %r' % (path, key))
+    if len(m['modalities']) not in (2, 3) or len(set(m['modalities'])) != len(m['modalities']):
+        raise ValueError('%s: "modalities" must list 2 or 3 distinct names, got %r' % (path, m['modalities']))
+    if not m['label_values'] or len(m['label_values']) > 16 or any(not 0 <= int(v) <= 255 for v in m['label_values']):
+        raise ValueError('%s: "label_values" must hold 1..16 grey values in 0..255, got %r' % (path, m['label_values']))
+    if len(m['target_resolution']) != 2 or min(m['target_resolution']) <= 0:
+        raise ValueError('%s: "target_resolution" must be two positive numbers, got %r' % (path, m['target_resolution']))
+    if len(m['input_shape']) not in (2, 3) or min(m['input_shape'][:2]) < 1:
+        raise ValueError('%s: "input_shape" must be [H, W] or [H, W, 1], got %r' % (path, m['input_shape']))
+    if not isinstance(m['splits'], list) or not m['splits']:
+        raise ValueError('%s: "splits" must be a non-empty list' % path)
+    for i, s in enumerate(m['splits']):
+        for t in SPLIT_TYPES[:3]:
+            if t not in s:
+                raise ValueError('%s: split %d has no %r list' % (path, i, t))
+            for v in s[t]:
+                if str(v) not in m['volumes']:
+                    raise ValueError('%s: split %d (%s) names volume %r, which "volumes" does not describe' % (path, i, t, v))
+    for v, entry in m['volumes'].items():
+        for mod in m['modalities']:
+            if mod not in entry or 'file' not in entry[mod]:
+                raise ValueError('%s: volume %s has no file for modality %r' % (path, v, mod))
+    return m
+
+
+class VolumeFolderLoader(object):
+    def __init__(self, root):
+        self.data_folder = root
+        self.manifest = m = read_manifest(root)
+        self.name = m['name']
+        self.modalities = list(m['modalities'])
+        self.label_values = [int(v) for v in m['label_values']]
+        self.num_masks = len(self.label_values)
+        self.target_resolution = (float(m['target_resolution'][0]), float(m['target_resolution'][1]))
+        self.input_shape = (int(m['input_shape'][0]), int(m['input_shape'][1]), 1)
+        self.volumes = sorted(set(v for s in m['splits'] for t in SPLIT_TYPES[:3] for v in s[t]))
+        self.num_volumes = len(self.volumes)
+        self.processed_folder = None
+        self.log = log
+
+    # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
+    def splits(self):
+        return [{t: list(s[t]) for t in SPLIT_TYPES[:3]} for s in self.manifest['splits']]
+
+    def get_volumes_for_split(self, split, split_type):
+        if split_type not in SPLIT_TYPES:
+            raise ValueError('Unknown split_type: %r (expected one of %s)' % (split_type, ', '.join(SPLIT_TYPES)))
+        all_splits = self.splits()
+        if not 0 <= int(split) < len(all_splits):
+            raise ValueError('%s defines %d split(s), got split %r' % (self.data_folder, len(all_splits), split))
+        s = all_splits[int(split)]
+        if split_type == 'all':
+            return sorted(s['training'] + s['validation'] + s['test'])
+        return s[split_type]
+
+    # ---- files --------------------------------------------------------------------------------------------------------------
+    def read_volume(self, volume, modality):
+        """raw (image [S,H,W], label [S,H,W] uint8, resolution (2,)) of one volume and modality, `slices` applied"""
+        entry = self.manifest['volumes'][str(volume)][modality]
+        path = os.path.join(self.data_folder, entry['file'])
+        if not os.path.isfile(path):
+            raise FileNotFoundError('volume %s, modality %s: %s does not exist' % (volume, modality, path))
+        with np.load(path) as z:
+            for key in ('image', 'label', 'resolution'):
+                if key not in z.files:
+                    raise ValueError('%s: no array %r' % (path, key))
+            image, label, res = z['image'], z['label'], np.asarray(z['resolution'], np.float64).reshape(-1)
+        if image.ndim != 3 or label.shape != image.shape or res.shape != (2,) or label.dtype != np.uint8 or res.min() <= 0:
+            raise ValueError('%s: expected image [S,H,W], label [S,H,W] uint8 and resolution [2] > 0, got %s %s, %s %s, %s'
+                             % (path, image.shape, image.dtype, label.shape, label.dtype, res))
+        ranges = entry.get('slices')
+        if ranges is not None:
+            for a, b in ranges:
+                if not 0 <= a < b <= image.shape[0]:
+                    raise ValueError('volume %s, modality %s: slice range [%d, %d) outside the %d slices of %s'
+                                     % (volume, modality, a, b, image.shape[0], path))
+            image = np.concatenate([image[a:b] for a, b in ranges], axis=0)
+            label = np.concatenate([label[a:b] for a, b in ranges], axis=0)
+        return image, label, res
+
+    # ---- the reference's loading surface --------------------------------------------------------------------------------------
+    def load_all_modalities_concatenated(self, split, split_type, downsample=1):
+        volumes = self.get_volumes_for_split(split, split_type)
+        raw, index = [], []
+        for v in volumes:
+            per_mod = [self.read_volume(v, mod) for mod in self.modalities]
+            counts = [p[0].shape[0] for p in per_mod]
+            if len(set(counts)) != 1:
+                raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the '
+                                 'matching ranges under "slices" in %s'
+                                 % (v, ', '.join('%s: %d' % mc for mc in zip(self.modalities, counts)), MANIFEST))
+            raw.append(per_mod)
+            index.append(np.array([v] * counts[0]))
+        index = np.concatenate(index, axis=0) if index else np.zeros((0,), np.int64)
+        images, masks = self.preprocess(raw, len(index))
+        return MultimodalPairedData(images, masks, index, downsample=downsample, num_modalities=len(self.modalities))
+
+    def preprocess(self, raw, n):
+        """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks]"""
+        device = nn.default_device()
+        OH, OW = self.input_shape[:2]
+        M, K = len(self.modalities), self.num_masks
+        images = torch.zeros((n, OH, OW, M), dtype=torch.float32, device=device)
+        masks = torch.zeros((n, OH, OW, M * K), dtype=torch.float32, device=device)
+        values = nn.host_to_device(np.asarray(self.label_values), device, np.int32)
+        n0 = 0
+        for per_mod in raw:
+            S = per_mod[0][0].shape[0]
+            for mod, (image, label, res) in enumerate(per_mod):
+                H, W = image.shape[1:]
+                RH = resampled_size(H, res[0], self.target_resolution[0])
+                RW = resampled_size(W, res[1], self.target_resolution[1])
+                if RH < 1 or RW < 1:
+                    raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
+                ops.preprocess_volume(nn.host_to_device(image, device, np.float32), nn.host_to_device(label, device, np.uint8),
+                                      values, images[n0:n0 + S], masks[n0:n0 + S], (RH, RW), crop_pad_map(RH, OH),
+                                      crop_pad_map(RW, OW), mod)
+            n0 += S
+        assert n0 == n
+        return nn.to_numpy(images), nn.to_numpy(masks)
+
+    def load_labelled_data(self, split, split_type, modality, normalise=True, downsample=1, root_folder=None):
+        """one modality by name, or 'all': the modalities stacked along the slice axis (chaos.py:57-99)"""
+        data = self.load_all_modalities_concatenated(split, split_type, downsample)
+        if modality == 'all':
+            mods = range(len(self.modalities))
+        elif modality in self.modalities:
+            mods = [self.modalities.index(modality)]
+        else:
+            raise ValueError('Unknown modality: %r (%s has %s)' % (modality, self.data_folder, ', '.join(self.modalities)))
+        images = np.concatenate([data.get_images_modi(m) for m in mods], axis=0)
+        masks = np.concatenate([data.get_masks_modi(m) for m in mods], axis=0)
+        index = np.concatenate([data.index for _ in mods], axis=0)
+        return Data(images, masks, index, 1)
+
+    def load_unlabelled_data(self, split, split_type, modality, normalise=True, downsample=1):
+        return self.load_labelled_data(split, split_type, modality, normalise, downsample)
+
+    def load_all_data(self, split, split_type, modality, normalise=True, downsample=1):
+        return self.load_labelled_data(split, split_type, modality, normalise, downsample)

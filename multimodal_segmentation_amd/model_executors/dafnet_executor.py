@@ -17,7 +17,7 @@ import torch
 
 from .. import costs, nn, ops
 from ..callbacks.swa import SWA
-from ..loaders import synthetic
+from ..loaders import loader_factory, synthetic, volume_folder
 from ..model_components import anatomy_encoder, modality_encoder, anatomy_fuser, segmentor, decoder, balancer
 from ..model_tester import ModelTester
 from ..models.discriminator import Discriminator
@@ -95,9 +95,29 @@ class DAFNetExecutor(Executor):
         """All 14 synthetic training volumes (the reference reads CHAOS here: loader.load_all_modalities_concatenated,
         dafnet_executor.py:86); data seed 1234 + rank so that data-parallel ranks hold different slices."""
         from ..parallel import dp
+        if volume_folder.has_data(self.conf.dataset_name):
+            return self.load_folder_volumes('training')
         vols = synthetic.splits()['training']
         return synthetic.SyntheticPairedData(self.conf.input_shape, self.conf.num_masks, vols, slices_per_volume,
                                              data_seed + dp.rank(), num_modalities=self._num_mod())
+
+    def load_folder_volumes(self, split_type):
+        """The `split_type` volumes of split conf.split from the folder registered for conf.dataset_name (the reference's
+        loader.load_all_modalities_concatenated(conf.split, split_type, conf.image_downsample), dafnet_executor.py:86), preprocessed
+        on the device.  Every data-parallel rank loads the full set: per-rank batches already differ through the generators' seed
+        (base_executor.get_data_generator)."""
+        loader = loader_factory.init_loader(self.conf.dataset_name)
+        if len(loader.modalities) != self._num_mod():
+            raise ValueError('%s holds %d modalities (%s), the model is built for %d (%s)'
+                             % (loader.data_folder, len(loader.modalities), ', '.join(loader.modalities), self._num_mod(),
+                                ', '.join(self.model.modalities)))
+        data = loader.load_all_modalities_concatenated(self.conf.split, split_type, self.conf.get('image_downsample', 1))
+        if data.size() == 0:
+            raise ValueError('%s: split %s has no %s slices' % (loader.data_folder, self.conf.split, split_type))
+        shape = tuple(data.get_images_modi(0).shape[1:3])
+        if shape != tuple(self.conf.input_shape[:2]):
+            raise ValueError('%s yields %s slices, the model is configured for %s' % (loader.data_folder, shape, tuple(self.conf.input_shape[:2])))
+        return data
 
     def _num_mod(self):
         return len(self.model.modalities)
@@ -144,8 +164,11 @@ class DAFNetExecutor(Executor):
         everything = self.load_training_volumes(slices_per_volume, data_seed)    # 'all' data of a modality (141-143,168-171)
         self.discriminator_image = [self.get_data_generator(train_images=[everything.get_images_modi(m)])
                                     for m in range(self._num_mod())]
-        self.val_data = synthetic.SyntheticPairedData(conf.input_shape, conf.num_masks, synthetic.splits()['validation'],
-                                                      slices_per_volume, data_seed + 101, num_modalities=self._num_mod())
+        if volume_folder.has_data(conf.dataset_name):
+            self.val_data = self.load_folder_volumes('validation')
+        else:
+            self.val_data = synthetic.SyntheticPairedData(conf.input_shape, conf.num_masks, synthetic.splits()['validation'],
+                                                          slices_per_volume, data_seed + 101, num_modalities=self._num_mod())
         self.batches = int(np.ceil(self.data_len / float(conf.batch_size)))
 
     def _load_discriminator_masks(self):

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import costs
-from .loaders import synthetic
+from .loaders import loader_factory, synthetic, volume_folder
 
 log = logging.getLogger('model_tester')
 
@@ -45,6 +45,13 @@ class ModelTester(object):
         return folder
 
     def load_test_data(self):
+        if self.test_data is None and volume_folder.has_data(self.conf.test_dataset):
+            # the reference's loader.load_all_modalities_concatenated(conf.split, 'test', conf.image_downsample), model_tester.py:35-37
+            loader = loader_factory.init_loader(self.conf.test_dataset)
+            if len(loader.modalities) != len(self.model.modalities):
+                raise ValueError('%s holds %d modalities, the model is built for %d'
+                                 % (loader.data_folder, len(loader.modalities), len(self.model.modalities)))
+            self.test_data = loader.load_all_modalities_concatenated(self.conf.split, 'test', self.conf.get('image_downsample', 1))
         if self.test_data is None:
             vols = synthetic.splits()['test']
             self.test_data = synthetic.SyntheticPairedData(self.conf.input_shape, self.conf.num_masks, vols,

@@ -1550,6 +1550,27 @@ def augment_gather(data, rows, mat, shift=None, order=1, fill_mode='nearest', cv
     return out
 
 
+def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod):
+    """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
+    (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,
+    rescale every slice to [-1, 1] by the extremes of its whole resampled frame, crop / pad with the per-axis index maps
+    rows / cols = (lo, kept, before).  img [S,H,W] fp32, lab [S,H,W] uint8, values int32, all on the device of `images`.  No
+    gradient (input pipeline)."""
+    S, H, W = img.shape
+    RH, RW = int(resampled[0]), int(resampled[1])
+    K = int(values.numel())
+    OH, OW, M = images.shape[1:]
+    if (img.dtype != torch.float32 or lab.dtype != torch.uint8 or tuple(lab.shape) != (S, H, W) or images.shape[0] != S
+            or tuple(masks.shape) != (S, OH, OW, M * K) or not 0 <= mod < M or not images.is_contiguous() or not masks.is_contiguous()):
+        raise ValueError('preprocess_volume: img %s %s, lab %s %s, images %s, masks %s, K = %d, modality %d'
+                         % (tuple(img.shape), img.dtype, tuple(lab.shape), lab.dtype, tuple(images.shape), tuple(masks.shape), K, mod))
+    geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    ws = _ws('preprocess', N.call('mmseg_preprocess_workspace_floats', S, RH, RW), images.device)
+    N.call('mmseg_preprocess_minmax', _c(img), ws, S, H, W, RH, RW)
+    N.call('mmseg_preprocess_image', _c(img), ws, images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod]))
+    N.call('mmseg_preprocess_label', _c(lab), values, masks, S, H, W, RH, RW, OH, OW, *(geo + [M * K, mod * K, K]))
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

@@ -1,0 +1,379 @@
+"""Volumes read from a folder and preprocessed on the device: loaders/volume_folder.py, csrc/preprocess.hip (mmseg_preprocess_*),
+tools/make_volume_folder.py and the `--data_folder` option of experiment.py, against the fp64 restatement of the reference's CHAOS
+preprocessing in tests/volume_loader_ref.py (loaders/chaos.py:242-264, 303-343)."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from multimodal_segmentation_amd import loaders, nn
+from multimodal_segmentation_amd.loaders import loader_factory
+from multimodal_segmentation_amd.utils import data_utils
+from tests import helpers as Hh
+from tests import volume_loader_ref as R
+
+TARGET = (1.89, 1.89)
+VALUES = [63, 126, 189, 252]
+
+# Op-level scenarios: one raw geometry (H, W, resolution, image dtype) per modality, a common output size.  The extents are chosen so
+# that no source coordinate lies within 1e-6 of a nearest-neighbour tie or of the strict border (test_scenarios_are_decidable).
+SCENARIOS = {
+    # up-scaling (41 -> 54, even surplus) | down-scaling (91 -> 58)
+    'up,down': dict(out=(48, 48), mods=[(41, 41, (2.5, 2.5), np.int16), (91, 91, (1.2, 1.2), np.float32)]),
+    # anisotropic (61 x 59 -> 42 x 69, odd surplus on the columns) | non-square (51 x 37 -> 46 x 33: crop rows, pad columns by an odd
+    # amount) | identity rows with an odd surplus (45 -> 45) and padded columns (40 -> 32)
+    'aniso,nonsquare,oddcrop+pad': dict(out=(40, 40), mods=[(61, 59, (1.3, 2.2), np.float64), (51, 37, (1.7, 1.7), np.uint16),
+                                                              (45, 40, (1.89, 1.5), np.int16)]),
+    # padding on both axes (29 x 34 -> 25 x 36, odd and even) | down-scaling with an all-zero slice | the target resolution itself
+    # (50 x 44 kept: crop rows, pad columns) with a slice of constant 7 and an all-zero one.  Interpolating a constant other than 0
+    # between pixels is not exactly constant in any precision, in the yardstick's fp64 either, so the non-zero constant sits where
+    # the coordinates are integers.
+    'pad-both,constant': dict(out=(48, 48), mods=[(29, 34, (1.6, 2.0), np.float32), (79, 70, (1.4, 1.5), np.int32),
+                                                    (50, 44, (1.89, 1.89), np.uint8)], constant={1: {1: 0}, 2: {0: 7, 2: 0}}),
+}
+
+
+def _raw_volume(rng, S, H, W, dtype):
+    """smooth texture + one bright and one dark blob near the centre, so that the extremes of a slice survive the crop"""
+    yy, xx = np.mgrid[:H, :W]
+    sig = 0.05 * min(H, W)
+    image = np.zeros((S, H, W), np.float64)
+    for s in range(S):
+        f = 1000.0 * Hh.smooth_field(rng, 1, H, W, sigma=3.0)[0, ..., 0]
+        for sign, cy, cx in ((3000.0, 0.45 + 0.02 * s, 0.45), (-3000.0, 0.56, 0.55 - 0.02 * s)):
+            f = f + sign * np.exp(-((yy - cy * H) ** 2 + (xx - cx * W) ** 2) / (2 * sig * sig))
+        image[s] = f - f.min() if np.issubdtype(dtype, np.unsignedinteger) else f      # signed: 0 (outside the source) is no extreme
+    if dtype == np.uint8:
+        image = image * (255.0 / image.max())
+    image = np.round(image) if np.issubdtype(dtype, np.integer) else image
+    m = Hh.ellipse_masks(rng, S, H, W, len(VALUES))
+    label = (m * np.asarray(VALUES, np.float32)).sum(-1).astype(np.uint8)
+    return image.astype(dtype), label
+
+
+def _scenario_data(name, S=3):
+    sc = SCENARIOS[name]
+    rng = np.random.RandomState(len(name))
+    raw = []
+    for i, (H, W, res, dtype) in enumerate(sc['mods']):
+        image, label = _raw_volume(rng, S, H, W, dtype)
+        for s, value in sc.get('constant', {}).get(i, {}).items():
+            image[s] = value
+        raw.append((image, label, np.asarray(res, np.float64)))
+    return sc, raw
+
+
+@pytest.fixture
+def standin(monkeypatch):
+    """the CPU stand-in of the C ABI with the mmseg_preprocess_* stand-ins of tests/volume_loader_ref.py added to its table"""
+    from tests import cpu_backend as cb
+    for name, fn in R.STANDINS.items():
+        monkeypatch.setitem(cb._TABLE, name, fn)
+    cb.install()
+    nn.set_default_device('cpu')
+    yield cb
+    cb.uninstall()
+
+
+@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
+def device(request, monkeypatch):
+    if request.param == 'cpu':
+        from tests import cpu_backend as cb
+        for name, fn in R.STANDINS.items():
+            monkeypatch.setitem(cb._TABLE, name, fn)
+        cb.install()
+        nn.set_default_device('cpu')
+        yield 'cpu'
+        cb.uninstall()
+    else:
+        nn.set_default_device('cuda:0')
+        yield 'cuda'
+
+
+@pytest.fixture(autouse=True)
+def _clean_registry():
+    saved = dict(loaders.data_conf)
+    yield
+    loaders.data_conf.clear()
+    loaders.data_conf.update(saved)
+
+
+@pytest.fixture
+def folder(tmp_path):
+    out = str(tmp_path / 'volumes')
+    R.tool().write_folder(out, volumes=4, size=64, slices=4, seed=3)
+    return out
+
+
+# ---- the yardstick and the test inputs (no GPU) ------------------------------------------------------------------------------------
+def test_restatement_matches_skimage():
+    transform = pytest.importorskip('skimage.transform')
+    rng = np.random.RandomState(0)
+    x = rng.rand(41, 37) * 100
+    lab = (rng.rand(41, 37) * 4).astype(np.uint8) * 63
+    for res in ((2.5, 2.5), (1.3, 2.2), (1.2, 1.6)):
+        scale = (res[0] / TARGET[0], res[1] / TARGET[1])
+        got = R.resample(x, res, TARGET, 1)
+        want = transform.rescale(x, scale, order=1, anti_aliasing=False, mode='constant', preserve_range=True)
+        assert got.shape == want.shape
+        inner = (slice(1, -1), slice(1, -1))          # the outermost ring is where 'constant' rules differ between versions
+        assert np.abs(got[inner] - want[inner]).max() < 1e-9
+        got0 = R.resample(lab, res, TARGET, 0)
+        want0 = transform.rescale(lab, scale, order=0, anti_aliasing=False, mode='constant', preserve_range=True)
+        assert np.count_nonzero(got0[inner] != want0[inner]) == 0
+
+
+@pytest.mark.parametrize('name', sorted(SCENARIOS))
+def test_scenarios_are_decidable(name):
+    """no source coordinate of an op-level case lies within 1e-6 of a half-integer (nearest-neighbour tie) or of the strict border:
+    the cap on pixels excluded from the mask comparison is 0"""
+    sc, raw = _scenario_data(name)
+    for H, W, res, _ in sc['mods']:
+        for n, r, t in ((H, res[0], TARGET[0]), (W, res[1], TARGET[1])):
+            assert R.undecidable_pixels(n, R.out_extent(n, r, t)) == 0, (name, n, r)
+    for image, label, res in raw:          # and the yardstick keeps both extremes of every non-constant slice inside the crop
+        want_i, want_m = R.preprocess(image, label, res, TARGET, VALUES, sc['out'])
+        for s in range(image.shape[0]):
+            if image[s].min() != image[s].max():
+                assert want_i[s].min() == -1.0 and want_i[s].max() == 1.0, (name, s)
+            else:
+                assert np.all(want_i[s] == -1.0)
+        assert want_m.sum() > 0
+
+
+def test_crop_pad_map_is_crop_same():
+    """the (lo, kept, before) index map equals utils/data_utils.crop_same(mode='equal', pad_mode='edge') incl. the odd-surplus quirk"""
+    from multimodal_segmentation_amd.loaders.volume_folder import crop_pad_map, resampled_size
+    for n in (2, 7, 8, 40, 41):
+        for r in range(1, 2 * n + 4):
+            lo, kept, before = crop_pad_map(r, n)
+            mine = lo + np.clip(np.arange(n) - before, 0, kept - 1)
+            ramp = np.arange(r, dtype=np.float64).reshape(1, r, 1, 1)
+            [want], _ = data_utils.crop_same([ramp], [ramp.copy()], (n, 1))
+            assert want.shape[1] == n and np.array_equal(mine, want[0, :, 0, 0]), (r, n)
+            assert lo >= 0 and kept >= 1 and lo + kept <= r and 0 <= before < n
+    with pytest.raises(ValueError):
+        crop_pad_map(4, 1)              # ceil(3 / 2) pixels off both ends leave nothing, in the reference as well
+    assert crop_pad_map(45, 40) == (3, 39, 0) and crop_pad_map(32, 40) == (0, 32, 4) and crop_pad_map(25, 48) == (0, 25, 11)
+    assert resampled_size(5, 1.89 * 0.5, 1.89) == 2 and resampled_size(7, 1.89 * 0.5, 1.89) == 4      # 2.5 -> 2, 3.5 -> 4: half to even
+
+
+# ---- op level ---------------------------------------------------------------------------------------------------------------------------
+def _run_op(raw, out_hw, device):
+    from multimodal_segmentation_amd import ops
+    from multimodal_segmentation_amd.loaders.volume_folder import crop_pad_map, resampled_size
+    S, M, K = raw[0][0].shape[0], len(raw), len(VALUES)
+    images = torch.full((S, out_hw[0], out_hw[1], M), float('nan'), device=device)
+    masks = torch.full((S, out_hw[0], out_hw[1], M * K), float('nan'), device=device)
+    values = nn.host_to_device(np.asarray(VALUES), device, np.int32)
+    for mod, (image, label, res) in enumerate(raw):
+        RH, RW = resampled_size(image.shape[1], res[0], TARGET[0]), resampled_size(image.shape[2], res[1], TARGET[1])
+        ops.preprocess_volume(nn.host_to_device(image, device, np.float32), nn.host_to_device(label, device, np.uint8), values,
+                              images, masks, (RH, RW), crop_pad_map(RH, out_hw[0]), crop_pad_map(RW, out_hw[1]), mod)
+    return images, masks
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(SCENARIOS))
+def test_preprocess_op_matches_restatement(name):
+    """Per modality of every scenario: images within 2e-4 of the tensor maximum (the op-level bar), per-slice
+    extremes exactly -1 and +1 (a constant slice: -1 everywhere), masks without a single differing pixel, each modality in its own
+    channels of the shared containers, and two runs bitwise equal."""
+    sc, raw = _scenario_data(name)
+    K = len(VALUES)
+    for image, label, res in raw:                            # decidable inputs first (on the CPU), then compare
+        for n, r, t in ((image.shape[1], res[0], TARGET[0]), (image.shape[2], res[1], TARGET[1])):
+            assert R.undecidable_pixels(n, R.out_extent(n, r, t)) == 0
+    images, masks = _run_op(raw, sc['out'], 'cuda:0')
+    images2, masks2 = _run_op(raw, sc['out'], 'cuda:0')
+    assert torch.equal(images, images2) and torch.equal(masks, masks2)
+    images, masks = images.cpu().numpy(), masks.cpu().numpy()
+    assert np.isfinite(images).all() and np.isfinite(masks).all()          # every channel of the NaN-filled containers was written
+    for mod, (image, label, res) in enumerate(raw):
+        want_i, want_m = R.preprocess(image, label, res, TARGET, VALUES, sc['out'])
+        got_i, got_m = images[..., mod:mod + 1], masks[..., mod * K:(mod + 1) * K]
+        err = np.abs(got_i - want_i).max() / np.abs(want_i).max()
+        differing = int(np.count_nonzero(got_m != want_m))
+        lo, hi = got_i.min(axis=(1, 2, 3)), got_i.max(axis=(1, 2, 3))
+        print('%s modality %d: image error %.3e of the maximum, %d differing mask pixels of %d, slice minima %s maxima %s'
+              % (name, mod, err, differing, want_m.size, lo.tolist(), hi.tolist()))
+        assert err <= 2e-4
+        assert differing == 0
+        assert set(np.unique(got_m).tolist()) <= {0.0, 1.0} and want_m.sum() > 0
+        for s in range(image.shape[0]):
+            if image[s].min() == image[s].max():
+                assert np.all(got_i[s] == -1.0)
+            else:
+                assert want_i[s].min() == -1.0 and want_i[s].max() == 1.0      # the blobs keep the extremes inside the crop
+                assert lo[s] == -1.0 and hi[s] == 1.0
+
+
+def test_entry_points_declared_and_geometry_checked():
+    """the C ABI declares the four entry points, and the launchers refuse an index map that leaves the resampled frame"""
+    from multimodal_segmentation_amd import _native
+    protos = _native.parse_header()
+    for name in R.STANDINS:
+        assert name in protos, name
+    _native.build()
+    lib = _native.load()
+    assert lib.mmseg_preprocess_workspace_floats(3, 50, 50) >= 6 and lib.mmseg_preprocess_workspace_floats(0, 50, 50) == 0
+    one = 1          # stands for a non-null pointer: a refused call launches nothing and touches no memory
+    args = [one, one, one, 2, 10, 10, 12, 12, 8, 8]
+    assert lib.mmseg_preprocess_image(*(args + [2, 8, 0, 2, 8, 0, 2, 2, None])) != 0       # channel 2 of 2
+    assert lib.mmseg_preprocess_image(*(args + [6, 8, 0, 2, 8, 0, 2, 0, None])) != 0       # lo + kept > RH
+    assert lib.mmseg_preprocess_image(*(args + [2, 8, 8, 2, 8, 0, 2, 0, None])) != 0       # before >= OH
+    assert lib.mmseg_preprocess_label(*(args + [2, 8, 0, 2, 8, 0, 8, 6, 4, None])) != 0    # channels 6..9 of 8
+    assert lib.mmseg_preprocess_label(*(args + [2, 8, 0, 2, 8, 0, 40, 0, 17, None])) != 0  # more than 16 label values
+
+
+# ---- host logic (CPU, through the stand-in) -----------------------------------------------------------------------------------------
+def test_manifest_splits_and_slice_ranges(folder, standin):
+    from multimodal_segmentation_amd.loaders.volume_folder import VolumeFolderLoader
+    manifest = json.load(open(os.path.join(folder, 'dataset.json')))
+    loader = VolumeFolderLoader(folder)
+    assert loader.input_shape == (64, 64, 1) and loader.num_masks == 4 and loader.modalities == ['t1', 't2']
+    assert loader.volumes == [1, 2, 3, 4] and loader.label_values == VALUES
+    assert loader.splits() == manifest['splits'] and len(loader.splits()) == 2
+    assert loader.get_volumes_for_split(0, 'training') == [1, 2] and loader.get_volumes_for_split(0, 'validation') == [3]
+    assert loader.get_volumes_for_split(0, 'test') == [4] and loader.get_volumes_for_split(1, 'all') == [1, 2, 3, 4]
+    assert loader.get_volumes_for_split(1, 'test') == manifest['splits'][1]['test'] != [4]
+    # ranges are applied in the order listed
+    entry = manifest['volumes']['1']['t2']
+    full = np.load(os.path.join(folder, entry['file']))['image']
+    manifest['volumes']['1']['t2']['slices'] = [[3, 5], [0, 2]]
+    json.dump(manifest, open(os.path.join(folder, 'dataset.json'), 'w'))
+    image, label, res = VolumeFolderLoader(folder).read_volume(1, 't2')
+    assert np.array_equal(image, np.concatenate([full[3:5], full[0:2]])) and label.shape == image.shape and res.shape == (2,)
+
+
+def test_loader_matches_restatement_and_selects_modalities(folder, standin):
+    """load_all_modalities_concatenated = the restatement applied volume by volume; load_labelled_data by name and with 'all'"""
+    loader = loader_factory.init_loader('chaos')
+    assert type(loader).__name__ == 'ChaosLoader'
+    loaders.data_conf['chaos'] = folder
+    loader = loader_factory.init_loader('chaos')
+    assert type(loader).__name__ == 'VolumeFolderLoader'
+    data = loader.load_all_modalities_concatenated(0, 'training', 1)
+    assert data.volumes() == [1, 2] and data.size() == 8 and data.num_modalities == 2
+    assert data.get_images_modi(0).shape == (8, 64, 64, 1) and data.get_masks_modi(1).shape == (8, 64, 64, 4)
+    for v in (1, 2):
+        for m, mod in enumerate(loader.modalities):
+            image, label, res = loader.read_volume(v, mod)
+            want_i, want_m = R.preprocess(image, label, res, loader.target_resolution, loader.label_values, (64, 64))
+            assert np.abs(data.get_volume_images_modi(m, v) - want_i).max() <= 2e-4
+            assert np.array_equal(data.get_volume_masks_modi(m, v), want_m)
+    assert data.get_images_modi(0).min() >= -1 and data.get_images_modi(0).max() <= 1
+    half = loader.load_all_modalities_concatenated(0, 'training', 2)
+    assert half.get_images_modi(1).shape == (8, 32, 32, 1)
+    t2 = loader.load_labelled_data(0, 'training', 't2')
+    assert np.array_equal(t2.images, data.get_images_modi(1)) and np.array_equal(t2.masks, data.get_masks_modi(1))
+    assert np.array_equal(t2.index, data.index)
+    both = loader.load_labelled_data(0, 'validation', 'all')
+    val = loader.load_all_modalities_concatenated(0, 'validation', 1)
+    assert both.volumes() == [3] and both.size() == 2 * val.size()
+    assert np.array_equal(both.images, np.concatenate([val.get_images_modi(0), val.get_images_modi(1)]))
+    assert loader.load_unlabelled_data(0, 'test', 't1').volumes() == [4] and loader.load_all_data(0, 'all', 't1').volumes() == [1, 2, 3, 4]
+    with pytest.raises(ValueError, match='Unknown modality'):
+        loader.load_labelled_data(0, 'training', 'ct')
+
+
+def test_loader_errors_name_the_problem(folder, standin):
+    from multimodal_segmentation_amd.loaders.volume_folder import VolumeFolderLoader
+    loader = VolumeFolderLoader(folder)
+    with pytest.raises(ValueError, match='split_type'):
+        loader.load_all_modalities_concatenated(0, 'train', 1)
+    with pytest.raises(ValueError, match='split'):
+        loader.get_volumes_for_split(5, 'training')
+    path = os.path.join(folder, 'dataset.json')
+    manifest = json.load(open(path))
+    manifest['volumes']['2']['t2']['slices'] = [[0, 3]]              # 4 slices of t1 against 3 of t2
+    json.dump(manifest, open(path, 'w'))
+    with pytest.raises(ValueError, match='volume 2.*different numbers of slices'):
+        VolumeFolderLoader(folder).load_all_modalities_concatenated(0, 'training', 1)
+    os.remove(os.path.join(folder, manifest['volumes']['4']['t1']['file']))
+    with pytest.raises(FileNotFoundError, match='volume 4'):
+        VolumeFolderLoader(folder).load_all_modalities_concatenated(0, 'test', 1)
+    with pytest.raises(FileNotFoundError, match='dataset.json'):
+        VolumeFolderLoader(os.path.join(folder, 'nowhere'))
+
+
+def test_init_loader_without_a_folder_is_unchanged():
+    assert loaders.data_conf == {}
+    loader = loader_factory.init_loader('chaos')
+    assert type(loader) is loader_factory.ChaosLoader
+    assert vars(loader) == dict(input_shape=(192, 192, 1), num_masks=4, modalities=['t1', 't2'], name='chaos')
+    assert type(loader_factory.init_loader('synthetic')) is loader_factory.ChaosLoader and loader_factory.init_loader('acdc') is None
+
+
+def test_cli_registers_the_folder_before_the_configuration_is_read(folder, tmp_path, monkeypatch):
+    from multimodal_segmentation_amd.experiment import Experiment, parse_arguments
+    monkeypatch.chdir(tmp_path)
+    args = parse_arguments(['--config', 'dafnet_config_chaos', '--split', '1', '--data_folder', folder])
+    assert args.data_folder == folder and args.test_data_folder is None
+    conf = Experiment().get_config(1, args)
+    assert loaders.data_conf == {'chaos': folder} and conf.data_folder == folder and conf.test_dataset == 'chaos'
+    assert tuple(conf.input_shape) == (64, 64, 1) and conf.num_masks == 4
+    assert tuple(conf.d_mask_params.input_shape) == (64, 64, 4) and tuple(conf.anatomy_encoder.output_shape) == (64, 64, 8)
+    # another folder for the test pass is registered under the name its dataset.json carries
+    other = str(tmp_path / 'other')
+    R.tool().write_folder(other, volumes=3, size=64, slices=2, seed=5, name='site_b')
+    loaders.data_conf.clear()
+    conf = Experiment().get_config(0, parse_arguments(['--config', 'dafnet_config_chaos', '--split', '0', '--data_folder', folder,
+                                                       '--test_data_folder', other]))
+    assert loaders.data_conf == {'chaos': folder, 'site_b': other} and conf.test_dataset == 'site_b'
+    # without the option nothing is registered and the configuration is the synthetic one
+    loaders.data_conf.clear()
+    conf = Experiment().get_config(0, parse_arguments(['--config', 'dafnet_config_chaos', '--split', '0']))
+    assert loaders.data_conf == {} and tuple(conf.input_shape) == (192, 192, 1) and 'data_folder' not in conf
+
+
+# ---- end to end: experiment.py --data_folder -------------------------------------------------------------------------------------------
+def _short_run(monkeypatch):
+    """one epoch, batches of 4: everything else (shapes included) comes from the configuration and dataset.json"""
+    from multimodal_segmentation_amd.configuration import _chaos
+    real = _chaos.assemble
+
+    def short(*a, **k):
+        p = real(*a, **k)
+        p.update(epochs=1, batch_size=4)
+        return p
+    monkeypatch.setattr(_chaos, 'assemble', short)
+
+
+@pytest.mark.parametrize('config', ['dafnet_config_chaos', 'mmsdnet_config_chaos'])
+def test_experiment_trains_and_tests_from_a_folder(config, device, folder, tmp_path, monkeypatch):
+    from multimodal_segmentation_amd.experiment import Experiment
+    from multimodal_segmentation_amd.model_executors import dafnet_executor
+    monkeypatch.chdir(tmp_path)
+    _short_run(monkeypatch)
+    seen = {}
+    from multimodal_segmentation_amd.model_executors import mmsdnet_executor
+    cls = dafnet_executor.DAFNetExecutor if config.startswith('dafnet') else mmsdnet_executor.MMSDNetExecutor
+    real_init = cls.init_train_data
+    real_batch = cls.train_batch
+
+    def init_train_data(self, *a, **k):
+        real_init(self, *a, **k)
+        seen['train'], seen['val'] = self.data.volumes(), self.val_data.volumes()
+        seen['batch'] = [tuple(t.shape) for t in next(self.gen_labelled)]
+
+    def train_batch(self, epoch_loss):
+        real_batch(self, epoch_loss)
+        seen['losses'] = {k: list(v) for k, v in epoch_loss.items()}
+    monkeypatch.setattr(cls, 'init_train_data', init_train_data)
+    monkeypatch.setattr(cls, 'train_batch', train_batch)
+    Experiment().run(['--config', config, '--split', '0', '--data_folder', folder])
+    base = 'dafnet_chaos' if config.startswith('dafnet') else 'mmsdnet_chaos'
+    run = "%s_l1_['t1', 't2']_split0" % base
+    assert seen['train'] == [1, 2] and seen['val'] == [3]                       # split 0 of dataset.json
+    assert seen['batch'] == [(4, 64, 64, 1)] * 2 + [(4, 64, 64, 4)] * 2          # (x1, x2, m1, m2) at the configured shape
+    assert seen['losses'] and all(np.isfinite(v).all() for v in seen['losses'].values())
+    dumped = json.load(open(os.path.join(run, 'experiment_configuration.json')))
+    assert dumped['data_folder'] == folder and dumped['input_shape'] == [64, 64, 1]
+    for mod in ('t1', 't2'):
+        rows = open(os.path.join(run, 'test_results_chaos_%s_simple' % mod, 'results.csv')).read().strip().split('\n')
+        assert rows[0] == 'Vol, Dice, Dice0, Dice1, Dice2, Dice3'
+        assert [r.split(',')[0] for r in rows[1:]] == ['4']                          # one row per test volume, ids of dataset.json
+        assert all(np.isfinite(float(v)) for v in rows[1].split(',')[1:])

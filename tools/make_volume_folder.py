@@ -1,0 +1,109 @@
+#!/usr/bin/env python
+"""Write a folder of volumes in the format of multimodal_segmentation_amd/loaders/volume_folder.py from the synthetic generator
+(loaders/synthetic.py) -- the fixture of tests/test_volume_loader.py and a worked example of the format for users who export their
+own data ("Volume folders").
+
+Every (volume, modality) gets its own slice size, pixel spacing and slice count, like acquisitions of different scanners: the raw
+extent is drawn so that the resampled slice is sometimes larger than input_shape (cropped) and sometimes smaller (edge-padded).
+Images are int16 "scanner" intensities, labels uint8 grey values (label_values; 0 is background).  Modalities of a volume show the
+same anatomy; the later modalities carry extra leading / trailing slices, and the manifest's `slices` ranges select the matching
+ones.
+
+    python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
+                                       [--raw_size LO HI] [--name chaos]
+    python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+from multimodal_segmentation_amd.loaders import synthetic
+
+TARGET_RESOLUTION = (1.89, 1.89)          # the CHAOS loader's common pixel spacing (chaos.py:331)
+
+
+def label_values(num_masks):
+    """evenly spaced grey values as in the CHAOS ground-truth PNGs: 63, 126, 189, 252 for four organs"""
+    step = 252 // num_masks
+    return [step * (k + 1) for k in range(num_masks)]
+
+
+def make_volume(rng, anatomy_seed, mod, S, H, W, values):
+    """S slices [S,H,W]: int16 image and uint8 grey-value label; slice i of every modality draws its organs from the same seed"""
+    K = len(values)
+    image = np.zeros((S, H, W), np.int16)
+    label = np.zeros((S, H, W), np.uint8)
+    weights = np.linspace(0.4, 1.0, K)
+    sign = np.where(np.arange(K) % 2 == 0, 1.0, -1.0)
+    for i in range(S):
+        m = synthetic.ellipse_masks(np.random.RandomState(anatomy_seed + i), H, W, K)
+        organ = (m * (weights * (1.0 if mod == 0 else (-1.0 if mod == 1 else sign)))[None, None]).sum(-1)
+        img = 0.5 * synthetic.smooth_field(rng, H, W, max(H / 32.0, 1.0)) + organ
+        image[i] = np.round((img - img.min()) / (img.max() - img.min() + 1e-12) * rng.uniform(800, 1600))
+        label[i] = (m * np.asarray(values, np.float32)[None, None]).sum(-1).astype(np.uint8)
+    return image, label
+
+
+def default_splits(ids):
+    """70 / 15 / 15 like CHAOS's 14 / 3 / 3 (at least one volume each), rotated for a second split"""
+    n = len(ids)
+    n_val = n_test = max(1, int(round(0.15 * n)))
+    out = []
+    for shift in (0, n_val):
+        r = ids[shift:] + ids[:shift]
+        out.append({'training': r[:n - n_val - n_test], 'validation': r[n - n_val - n_test:n - n_test], 'test': r[n - n_test:]})
+    return out
+
+
+def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos'):
+    if volumes < 3:
+        raise ValueError('need at least 3 volumes (training, validation, test)')
+    os.makedirs(out, exist_ok=True)
+    rng = np.random.RandomState(seed)
+    values = label_values(masks)
+    ids = list(range(1, volumes + 1))
+    manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
+                    input_shape=[size, size, 1], splits=default_splits(ids), volumes={})
+    for v in ids:
+        entry = {}
+        for mod, mod_name in enumerate(modalities):
+            res = rng.uniform(1.2, 2.4, size=2)
+            if raw_size is None:      # field of view of 0.85 .. 1.2 input extents: crop on some axes, pad on others
+                H, W = [max(8, int(round(size * rng.uniform(0.85, 1.2) * TARGET_RESOLUTION[a] / res[a]))) for a in range(2)]
+            else:
+                H, W = [int(rng.randint(raw_size[0], raw_size[1] + 1)) for _ in range(2)]
+            before, after = (0, 0) if mod == 0 else (int(rng.randint(0, 3)), int(rng.randint(0, 3)))
+            image, label = make_volume(rng, 1000 * (seed + 1) * v - before, mod, before + slices + after, H, W, values)
+            fname = 'vol%02d_%s.npz' % (v, mod_name)
+            np.savez_compressed(os.path.join(out, fname), image=image, label=label, resolution=res.astype(np.float64))
+            entry[mod_name] = {'file': fname}
+            if before or after:
+                entry[mod_name]['slices'] = [[before, before + slices]]
+        manifest['volumes'][str(v)] = entry
+    with open(os.path.join(out, 'dataset.json'), 'w') as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('out')
+    ap.add_argument('--volumes', type=int, default=4)
+    ap.add_argument('--size', type=int, default=64, help='input_shape is size x size')
+    ap.add_argument('--slices', type=int, default=6, help='paired slices per volume')
+    ap.add_argument('--modalities', nargs='+', default=['t1', 't2'])
+    ap.add_argument('--masks', type=int, default=4)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--raw_size', type=int, nargs=2, metavar=('LO', 'HI'), help='draw the raw slice extents from [LO, HI]')
+    ap.add_argument('--name', default='chaos')
+    a = ap.parse_args(argv)
+    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name)
+    print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
+
+
+if __name__ == '__main__':
+    main()
