@@ -397,6 +397,21 @@ int mmseg_preprocess_image(const float* img, const float* ws, float* out, int S,
 int mmseg_preprocess_label(const unsigned char* lab, const int* values, float* out, int S, int H, int W, int RH, int RW, int OH, int OW,
                            int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch0, int K, void* stream);
 
+/* ---- predicted label volumes on a volume's own grid (csrc/postprocess.hip; build-defined, the reference writes no segmentation) ----
+ * mmseg_restore_label inverts the geometry of mmseg_preprocess_label and binarises in the same pass: prob [S,OH,OW,C] (the
+ * segmentor's output, the K <= 16 organ channels first, K <= C) -> out [S,H,W] uint8 grey values, every byte written.  Per axis the
+ * raw index d has the resampled coordinate (d + 0.5) * (R / n) - 0.5 in fp64, clamped into [0, R - 1]; outside [lo, lo + kept - 1]
+ * the pixel was cropped away on the way in and gets 0; inside, the container coordinate is coord - lo + before.  order 1 samples
+ * every organ channel bilinearly (fp32, the expression order of the image resampling), order 0 takes the tap floor(coord + 0.5)
+ * limited to the window.  The pixel gets values[k] of the lowest k whose sampled probability is > 0.5, else 0.  (lo, kept, before)
+ * and (RH, RW) are the ones given to mmseg_preprocess_*; additionally before + kept <= O, since this direction reads the window. */
+int mmseg_restore_label(const float* prob, const int* values, unsigned char* out, int S, int H, int W, int RH, int RW, int OH, int OW,
+                        int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int K, int order, void* stream);
+/* pred, truth [S,n] uint8 (n = H * W pixels per slice) -> counts [S,K,3] int32 = |pred == values[k]|, |truth == values[k]|, |both| per
+ * slice and organ.  The launcher zeroes counts on the stream; integer sums, so two runs are bitwise equal. */
+int mmseg_label_overlap(const unsigned char* pred, const unsigned char* truth, const int* values, int* counts, int S, int n, int K,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

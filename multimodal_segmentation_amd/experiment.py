@@ -3,9 +3,12 @@
     python experiment.py --config <module in configuration/> --split <int> [--l_mix f] [--test b]
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
                          [--data_folder PATH] [--test_data_folder PATH]
+                         [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
-every configuration trains and tests on the synthetic volumes.
+every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
+labelled or not, for which the checkpoint of the run folder writes label volumes on each volume's own grid (volume_predictor.py): after
+the test pass, or instead of training with `--test`.
 
 The run folder name and the config mutations follow Experiment.get_config (experiment.py:31-72):
 `<folder>[_randomise][_automatedpairing]_l<l_mix>_<modality>_split<split>` with dots stripped, n_pairs = 3 under automated
@@ -37,6 +40,10 @@ def parse_arguments(argv=None):
     ap.add_argument('--randomise', type=bool, help='randomise the multimodal pairs')
     ap.add_argument('--data_folder', help='folder of exported volumes (dataset.json + .npz) to train, validate and test on')
     ap.add_argument('--test_data_folder', help='another folder of exported volumes for the test pass')
+    ap.add_argument('--predict_folder', help='folder of exported volumes (labels optional) to write predicted label volumes for')
+    ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
+    ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
+    ap.add_argument('--predict_order', type=int, choices=[0, 1], default=1, help='resampling back to the raw grid: nearest / bilinear')
     return ap.parse_args(argv)
 
 
@@ -171,6 +178,22 @@ class Experiment(object):
             executor.test()
         dp.host_barrier()                         # not a GPU collective: the other ranks may wait longer than RCCL's watchdog allows
 
+    def run_prediction(self, conf, args):
+        """`--predict_folder`: label volumes from the CHECKPOINT of the run folder (a freshly built model loads it, as `--test` does),
+        so that a run that has just trained and a later `--test` run write the same arrays"""
+        from .loaders.volume_folder import read_manifest
+        from .volume_predictor import VolumePredictor, checkpoint_of
+        if checkpoint_of(conf.folder) is None:
+            raise FileNotFoundError('--predict_folder: the run folder %s holds no checkpoint to predict with (train first, without '
+                                    '--test)' % conf.folder)
+        if dp.is_main():
+            out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
+            model = resolve('models', conf.model)(conf)
+            model.build()
+            VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order)
+            self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
+        dp.host_barrier()
+
     def run(self, argv=None):
         args = parse_arguments(argv)
         # one process per GPU under `python -m torch.distributed.run` (RANK / LOCAL_RANK / WORLD_SIZE): join the RCCL group and
@@ -178,7 +201,14 @@ class Experiment(object):
         dp.init_from_env()
         conf = self.get_config(int(args.split), args)
         self.init_logging(conf)
+        if getattr(args, 'predict_folder', None) and args.test:
+            from .volume_predictor import checkpoint_of
+            if checkpoint_of(conf.folder) is None:          # before the test pass evaluates an untrained model
+                raise FileNotFoundError('--test --predict_folder: the run folder %s holds no checkpoint (train first, without --test)'
+                                        % conf.folder)
         self.run_experiment(conf, args.test)
+        if getattr(args, 'predict_folder', None):
+            self.run_prediction(conf, args)
 
     read_console_parameters = staticmethod(parse_arguments)
 

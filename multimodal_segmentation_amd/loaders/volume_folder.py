@@ -7,7 +7,8 @@ device (csrc/preprocess.hip).  Reading DICOM / PNG stays out of scope: a folder 
                              {training, validation, test} lists of volume ids, chaos.py:32-48) and
                              volumes: {"<id>": {"<modality>": {"file": "<name>.npz", "slices": [[start, stop], ...]}}}
     <root>/<name>.npz        image [S,H,W] (any integer or float dtype), label [S,H,W] uint8 grey values, resolution [2] mm per
-                             pixel along rows and columns
+                             pixel along rows and columns.  `label` may be missing in a folder that is only predicted on
+                             (load_volume_for_prediction, volume_predictor.py); the training surface then refuses the file.
 
 `slices` (optional) lists [start, stop) ranges applied in order: how a user states which slices of the acquisitions show the same
 anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all modalities of a volume must hold the same number of
@@ -120,29 +121,75 @@ class VolumeFolderLoader(object):
         return s[split_type]
 
     # ---- files --------------------------------------------------------------------------------------------------------------
-    def read_volume(self, volume, modality):
-        """raw (image [S,H,W], label [S,H,W] uint8, resolution (2,)) of one volume and modality, `slices` applied"""
+    def read_volume(self, volume, modality, require_label=True):
+        """raw (image [S,H,W], label [S,H,W] uint8, resolution (2,)) of one volume and modality, `slices` applied.  With
+        require_label=False a file without a `label` array yields label = None (a scan to be segmented)."""
+        image, label, res, selected = self._read_file(volume, modality, require_label)
+        if selected is not None:
+            image = image[selected]
+            label = None if label is None else label[selected]
+        return image, label, res
+
+    def _read_file(self, volume, modality, require_label):
+        """the arrays as stored (all slices of the file) and the indices that `slices` selects, in order (None: every slice)"""
         entry = self.manifest['volumes'][str(volume)][modality]
         path = os.path.join(self.data_folder, entry['file'])
         if not os.path.isfile(path):
             raise FileNotFoundError('volume %s, modality %s: %s does not exist' % (volume, modality, path))
         with np.load(path) as z:
             for key in ('image', 'label', 'resolution'):
-                if key not in z.files:
+                if key not in z.files and (require_label or key != 'label'):
                     raise ValueError('%s: no array %r' % (path, key))
-            image, label, res = z['image'], z['label'], np.asarray(z['resolution'], np.float64).reshape(-1)
-        if image.ndim != 3 or label.shape != image.shape or res.shape != (2,) or label.dtype != np.uint8 or res.min() <= 0:
+            image, res = z['image'], np.asarray(z['resolution'], np.float64).reshape(-1)
+            label = z['label'] if 'label' in z.files else None
+        if (image.ndim != 3 or res.shape != (2,) or res.min() <= 0
+                or (label is not None and (label.shape != image.shape or label.dtype != np.uint8))):
             raise ValueError('%s: expected image [S,H,W], label [S,H,W] uint8 and resolution [2] > 0, got %s %s, %s %s, %s'
-                             % (path, image.shape, image.dtype, label.shape, label.dtype, res))
+                             % (path, image.shape, image.dtype, getattr(label, 'shape', None), getattr(label, 'dtype', None), res))
         ranges = entry.get('slices')
+        selected = None
         if ranges is not None:
             for a, b in ranges:
                 if not 0 <= a < b <= image.shape[0]:
                     raise ValueError('volume %s, modality %s: slice range [%d, %d) outside the %d slices of %s'
                                      % (volume, modality, a, b, image.shape[0], path))
-            image = np.concatenate([image[a:b] for a, b in ranges], axis=0)
-            label = np.concatenate([label[a:b] for a, b in ranges], axis=0)
-        return image, label, res
+            selected = np.concatenate([np.arange(a, b) for a, b in ranges])
+        return image, label, res, selected
+
+    def geometry(self, H, W, res):
+        """(RH, RW), rows, cols: the resampled extent of an H x W slice at `res` mm and its crop / pad index maps to input_shape"""
+        RH = resampled_size(H, res[0], self.target_resolution[0])
+        RW = resampled_size(W, res[1], self.target_resolution[1])
+        if RH < 1 or RW < 1:
+            raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
+        return (RH, RW), crop_pad_map(RH, self.input_shape[0]), crop_pad_map(RW, self.input_shape[1])
+
+    def load_volume_for_prediction(self, volume):
+        """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
+        [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
+        way back needs -- file, raw_shape (S_file, H, W), slices (the selected file indices, in order), resolution, resampled (RH, RW),
+        rows / cols (lo, kept, before) and label (the selected raw slices [S,H,W] uint8, or None)."""
+        device = nn.default_device()
+        OH, OW = self.input_shape[:2]
+        images, geometry = [], []
+        for mod in self.modalities:
+            image, label, res, selected = self._read_file(volume, mod, False)
+            S_file, H, W = image.shape
+            if selected is None:
+                selected = np.arange(S_file)
+            resampled, rows, cols = self.geometry(H, W, res)
+            container = torch.zeros((len(selected), OH, OW, 1), dtype=torch.float32, device=device)
+            ops.preprocess_images(nn.host_to_device(image[selected], device, np.float32), container, resampled, rows, cols, 0)
+            images.append(container)
+            geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
+                                 slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
+                                 label=None if label is None else np.ascontiguousarray(label[selected])))
+        counts = [g.shape[0] for g in images]
+        if len(set(counts)) != 1:
+            raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the matching '
+                             'ranges under "slices" in %s' % (volume, ', '.join('%s: %d' % mc for mc in zip(self.modalities, counts)),
+                                                               MANIFEST))
+        return images, geometry
 
     # ---- the reference's loading surface --------------------------------------------------------------------------------------
     def load_all_modalities_concatenated(self, split, split_type, downsample=1):

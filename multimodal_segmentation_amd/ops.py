@@ -1571,6 +1571,54 @@ def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mo
     N.call('mmseg_preprocess_label', _c(lab), values, masks, S, H, W, RH, RW, OH, OW, *(geo + [M * K, mod * K, K]))
 
 
+def preprocess_images(img, images, resampled, rows, cols, mod):
+    """The image half of preprocess_volume, for a volume without labels: channel `mod` of images [S,OH,OW,M] is written and no label
+    kernel is launched."""
+    S, H, W = img.shape
+    RH, RW = int(resampled[0]), int(resampled[1])
+    OH, OW, M = images.shape[1:]
+    if img.dtype != torch.float32 or images.shape[0] != S or not 0 <= mod < M or not images.is_contiguous():
+        raise ValueError('preprocess_images: img %s %s, images %s, modality %d' % (tuple(img.shape), img.dtype, tuple(images.shape), mod))
+    geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    ws = _ws('preprocess', N.call('mmseg_preprocess_workspace_floats', S, RH, RW), images.device)
+    N.call('mmseg_preprocess_minmax', _c(img), ws, S, H, W, RH, RW)
+    N.call('mmseg_preprocess_image', _c(img), ws, images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod]))
+
+
+def restore_label(prob, values, raw_hw, resampled, rows, cols, order=1):
+    """prob [S,OH,OW,C] fp32 (a segmentor's output on the device, organ channels first) -> uint8 grey values [S,H,W] on the raw grid
+    raw_hw = (H, W) of the volume that preprocess_volume brought to [OH,OW] with `resampled` = (RH, RW) and the per-axis index maps
+    rows / cols = (lo, kept, before) (csrc/postprocess.hip): the crop / pad is undone, every organ channel is resampled (order 1:
+    bilinear, order 0: nearest) and the pixel gets values[k] of the organ whose probability is > 0.5, or 0; pixels that were cropped
+    away get 0.  values [K] int32 on the device, K <= C.  No gradient."""
+    H, W = int(raw_hw[0]), int(raw_hw[1])
+    RH, RW = int(resampled[0]), int(resampled[1])
+    K = int(values.numel())
+    if (prob.dim() != 4 or prob.dtype != torch.float32 or values.dtype != torch.int32 or not 1 <= K <= min(16, prob.shape[3])
+            or order not in (0, 1) or H < 1 or W < 1):
+        raise ValueError('restore_label: prob %s %s, values %s %s, raw size %s, order %r'
+                         % (tuple(prob.shape), prob.dtype, tuple(values.shape), values.dtype, (H, W), order))
+    S, OH, OW, C = prob.shape
+    geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    out = _new((S, H, W), prob, torch.uint8)
+    N.call('mmseg_restore_label', _c(prob), values, out, S, H, W, RH, RW, OH, OW, *(geo + [C, K, int(order)]))
+    return out
+
+
+def label_overlap(pred, truth, values):
+    """pred, truth [S,H,W] uint8 grey values on the device, values [K] int32 -> int32 [S,K,3]: per slice and organ the pixel counts
+    |pred == v|, |truth == v| and |both| (csrc/postprocess.hip), what a per-slice Dice on the raw grid is made of"""
+    K = int(values.numel())
+    if (pred.dim() != 3 or pred.dtype != torch.uint8 or truth.dtype != torch.uint8 or tuple(truth.shape) != tuple(pred.shape)
+            or values.dtype != torch.int32 or not 1 <= K <= 16):
+        raise ValueError('label_overlap: pred %s %s, truth %s %s, values %s %s'
+                         % (tuple(pred.shape), pred.dtype, tuple(truth.shape), truth.dtype, tuple(values.shape), values.dtype))
+    S, H, W = pred.shape
+    counts = _new((S, K, 3), pred, torch.int32)
+    N.call('mmseg_label_overlap', _c(pred), _c(truth), values, counts, S, H * W, K)
+    return counts
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

@@ -10,7 +10,7 @@ same anatomy; the later modalities carry extra leading / trailing slices, and th
 ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
-                                       [--raw_size LO HI] [--name chaos]
+                                       [--raw_size LO HI] [--name chaos] [--unlabelled]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -59,7 +59,9 @@ def default_splits(ids):
     return out
 
 
-def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos'):
+def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False):
+    """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
+    draws included, is as without it"""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
@@ -79,7 +81,9 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
             before, after = (0, 0) if mod == 0 else (int(rng.randint(0, 3)), int(rng.randint(0, 3)))
             image, label = make_volume(rng, 1000 * (seed + 1) * v - before, mod, before + slices + after, H, W, values)
             fname = 'vol%02d_%s.npz' % (v, mod_name)
-            np.savez_compressed(os.path.join(out, fname), image=image, label=label, resolution=res.astype(np.float64))
+            arrays = dict(image=image, resolution=res.astype(np.float64)) if unlabelled else dict(image=image, label=label,
+                                                                                                   resolution=res.astype(np.float64))
+            np.savez_compressed(os.path.join(out, fname), **arrays)
             entry[mod_name] = {'file': fname}
             if before or after:
                 entry[mod_name]['slices'] = [[before, before + slices]]
@@ -100,8 +104,9 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--raw_size', type=int, nargs=2, metavar=('LO', 'HI'), help='draw the raw slice extents from [LO, HI]')
     ap.add_argument('--name', default='chaos')
+    ap.add_argument('--unlabelled', action='store_true', help='write files without a label array (a folder to predict on)')
     a = ap.parse_args(argv)
-    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name)
+    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 
