@@ -412,6 +412,24 @@ int mmseg_restore_label(const float* prob, const int* values, unsigned char* out
 int mmseg_label_overlap(const unsigned char* pred, const unsigned char* truth, const int* values, int* counts, int S, int n, int K,
                         void* stream);
 
+/* ---- scores in mm on a volume's own grid (csrc/postprocess.hip; build-defined, the reference scores Dice only) ----------------------
+ * K + 1 binary problems per label volume [S,H,W]: problem k < K has foreground "== values[k]", problem K "equals any of values".
+ * S * H * W < 2^31, 1 <= K <= 16, spacings (mm between slices, rows, columns) finite and > 0; anything else is refused.  S == 0 does
+ * nothing.  A surface voxel is a foreground voxel with a face neighbour that is background or outside the volume.  Distances are
+ * exact: three per-axis passes out[i] = min over all j of in[j] + (spacing * (i - j))^2 in fp64, then one square root.
+ * surf [K+1,S,H,W] uint8 0 / 1, every byte written; counts [K+1][2] int32 = (|foreground|, |surface|), zeroed on the stream, or null */
+int mmseg_label_surface(const unsigned char* label, const int* values, unsigned char* surf, int* counts, int S, int H, int W, int K,
+                        void* stream);
+/* out [S,H,W] fp64 = mm to the nearest non-zero voxel of sites [S,H,W] (+inf when there is none); tmp: S * H * W doubles of scratch */
+int mmseg_distance_to_sites(const unsigned char* sites, double* out, double* tmp, int S, int H, int W, double dz, double dy, double dx,
+                            void* stream);
+long mmseg_surface_metrics_workspace_doubles(int S, int H, int W, int K);
+/* table [K+1,6] fp64 = nP, nT, |surface(P)|, |surface(T)|, sum and max over both surfaces of the distance to the other one (nan when
+ * either surface is empty).  The sum is reduced in a fixed order (per-block partials in ws, one final block): two runs are bitwise
+ * equal.  ws: mmseg_surface_metrics_workspace_doubles(S, H, W, K) doubles. */
+int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
+                          int H, int W, int K, double dz, double dy, double dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

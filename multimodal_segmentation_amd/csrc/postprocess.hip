@@ -21,7 +21,24 @@
 // mmseg_label_overlap: pred, truth [S,n] uint8 -> counts [S,K,3] int32 = (|pred == v|, |truth == v|, |both|) per slice and organ.
 // Per-thread counters, a wave reduction, one LDS pass across the block's waves, one integer atomicAdd per (block, counter).  Integer
 // addition is order independent: two runs are bitwise equal.  The launcher zeroes `counts` on the stream before the kernel.
+//
+// Scores in mm on a volume's own grid (build-defined; definitions in INTEGRATION.md section 5).  K + 1 binary problems per label volume:
+// problem k < K is "== values[k]", problem K "equals any of values".
+// mmseg_label_surface: label [S,H,W] -> surf [K+1,S,H,W] 0 / 1: a foreground voxel with a background (or outside) face neighbour.  One
+//   sweep: a lane reads its voxel and the six neighbours once and writes the K + 1 bytes; consecutive lanes, consecutive voxels.
+//   Optionally counts [K+1][2] int32 = (|foreground|, |surface|) with integer atomics.
+// Exact squared Euclidean distance to the nearest site, separable: three passes out[i] = min over ALL j of in[j] + (sp * (i - j))^2 in
+//   fp64 (fma(d, d, in[j]), d = sp * (i - j) with i - j exact), along W, H, S.  The minimum over a fixed set of values is the same in any
+//   order, so two runs are bitwise equal.  Pass along W (po_edt_row_kernel): a row per wave, lanes own outputs lane + 64 m, the row is
+//   staged in LDS in tiles and every lane reads the same LDS address (a broadcast).  Passes along H and S (po_edt_col_kernel): the
+//   volume is seen as [A, L, B] with B contiguous; a block owns 64 consecutive b and 64 outputs i, stages [64 j][64 b] tiles in LDS
+//   (global reads and LDS reads: consecutive lanes, consecutive doubles), a thread keeps 16 consecutive i in registers.  The last
+//   pass takes the square root.
+// mmseg_surface_metrics: per problem the two distance maps, each reduced over the other side's surface: per-thread partial sums in
+//   grid-stride order, a fixed LDS tree per block, partials [blocks][2] = (sum, max), and one block that adds the partials in a fixed
+//   tree: no floating-point atomics.  Only the [K+1,6] table is meant to leave the device.
 #include "common.hpp"
+#include <math.h>
 
 #define PO_BLOCK 256
 #define PO_MAXBLK 256
@@ -180,6 +197,226 @@ __global__ void __launch_bounds__(PO_BLOCK) po_overlap_kernel(const unsigned cha
     }
 }
 
+// ---- scores in mm: surfaces, exact distance transform, reductions ---------------------------------------------------------------------
+#define PO_SURF_MAXBLK 1024
+#define PO_RED_BLOCKS 256
+#define ED_ROW_TJ 256          // doubles of a row staged per tile and wave
+#define ED_ROW_NI 8            // outputs per lane and chunk: a chunk is 512 outputs
+#define ED_COL_T 64            // tile edge of the strided passes
+#define ED_COL_NI 16           // outputs per thread (4 thread rows x 16 = 64 outputs per block)
+
+// grid-stride over the n = S * H * W voxels.  surf [K+1][n]; counts [K+1][2] or null
+__global__ void __launch_bounds__(PO_BLOCK) po_surface_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int K,
+                                                              unsigned char* __restrict__ surf, int* __restrict__ counts, int S, int H,
+                                                              int W) {
+    __shared__ int vals[PO_MAXVALUES];
+    __shared__ unsigned member[9];          // bit g: grey value g is one of `values`
+    __shared__ int red[(PO_MAXVALUES + 1) * 2];
+    if (threadIdx.x < PO_MAXVALUES) vals[threadIdx.x] = threadIdx.x < K ? (values[threadIdx.x] & 255) : -1;      // -1 matches no byte
+    if (threadIdx.x < (PO_MAXVALUES + 1) * 2) red[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < 9; ++i) member[i] = 0u;
+        for (int k = 0; k < K; ++k) member[(values[k] & 255) >> 5] |= 1u << (values[k] & 31);
+    }
+    __syncthreads();
+    const long plane = (long)H * W, n = plane * S;
+    int cf[PO_MAXVALUES + 1], cs[PO_MAXVALUES + 1];
+#pragma unroll
+    for (int k = 0; k <= PO_MAXVALUES; ++k) cf[k] = cs[k] = 0;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int z = (int)(e / plane);
+        const int r = (int)(e - (long)z * plane);
+        const int y = r / W, x = r - y * W;
+        const int c = lab[e];
+        int nb[6];          // 256: outside the volume, which is background for every problem
+        nb[0] = x > 0 ? lab[e - 1] : 256;
+        nb[1] = x < W - 1 ? lab[e + 1] : 256;
+        nb[2] = y > 0 ? lab[e - W] : 256;
+        nb[3] = y < H - 1 ? lab[e + W] : 256;
+        nb[4] = z > 0 ? lab[e - plane] : 256;
+        nb[5] = z < S - 1 ? lab[e + plane] : 256;
+#pragma unroll
+        for (int k = 0; k < PO_MAXVALUES; ++k) {
+            const int v = vals[k];
+            const int fg = c == v;
+            const int sf = fg & ((nb[0] != v) | (nb[1] != v) | (nb[2] != v) | (nb[3] != v) | (nb[4] != v) | (nb[5] != v));
+            if (k < K) surf[(size_t)k * n + e] = (unsigned char)sf;
+            cf[k] += fg;
+            cs[k] += sf;
+        }
+        int all_in = 1;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) all_in &= nb[i] < 256 ? (int)((member[nb[i] >> 5] >> (nb[i] & 31)) & 1u) : 0;
+        const int fg = (int)((member[c >> 5] >> (c & 31)) & 1u);
+        const int sf = fg & (all_in ^ 1);
+        surf[(size_t)K * n + e] = (unsigned char)sf;
+        cf[PO_MAXVALUES] += fg;
+        cs[PO_MAXVALUES] += sf;
+    }
+    if (!counts) return;          // uniform: a kernel argument
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k <= PO_MAXVALUES; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cf[k] += __shfl_xor(cf[k], o, 64);
+            cs[k] += __shfl_xor(cs[k], o, 64);
+        }
+        if (lane == 0) {
+            atomicAdd(&red[2 * k], cf[k]);
+            atomicAdd(&red[2 * k + 1], cs[k]);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * (K + 1)) {          // problem K (the joint one) sits in slot PO_MAXVALUES of the block's counters
+        const int k = threadIdx.x >> 1, slot = k == K ? PO_MAXVALUES : k;
+        const int v = red[2 * slot + (threadIdx.x & 1)];
+        if (v) atomicAdd(counts + threadIdx.x, v);
+    }
+}
+
+__device__ __forceinline__ double ed_load(const unsigned char* p, long i) { return p[i] ? 0.0 : (double)INFINITY; }
+__device__ __forceinline__ double ed_load(const double* p, long i) { return p[i]; }
+
+// the pass along the contiguous axis: in, out [A][L].  grid ceil(A / 4), block 256: wave w of a block owns row 4 * blockIdx.x + w
+template <typename TIN, bool SQRT>
+__global__ void __launch_bounds__(PO_BLOCK) po_edt_row_kernel(const TIN* __restrict__ in, double* __restrict__ out, long A, int L,
+                                                              double sp) {
+    __shared__ double line[PO_BLOCK / 64][ED_ROW_TJ];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const long row = (long)blockIdx.x * (PO_BLOCK / 64) + wid;
+    const bool live = row < A;
+    const long base = live ? row * L : 0;
+    for (int i0 = 0; i0 < L; i0 += 64 * ED_ROW_NI) {
+        double acc[ED_ROW_NI];
+#pragma unroll
+        for (int m = 0; m < ED_ROW_NI; ++m) acc[m] = (double)INFINITY;
+        for (int j0 = 0; j0 < L; j0 += ED_ROW_TJ) {
+            __syncthreads();          // L is uniform, so every wave of the block reaches every barrier
+            for (int t = lane; t < ED_ROW_TJ; t += 64) line[wid][t] = (live && j0 + t < L) ? ed_load(in, base + j0 + t) : (double)INFINITY;
+            __syncthreads();
+            const int nj = min(ED_ROW_TJ, L - j0);
+            double dj[ED_ROW_NI];          // i - j0 per output: integers, exact in fp64
+#pragma unroll
+            for (int m = 0; m < ED_ROW_NI; ++m) dj[m] = (double)(i0 + lane + 64 * m - j0);
+            for (int t = 0; t < nj; ++t) {
+                const double v = line[wid][t], ft = (double)t;
+#pragma unroll
+                for (int m = 0; m < ED_ROW_NI; ++m)
+                    if (i0 + 64 * m < L) {          // wave-uniform
+                        const double d = sp * (dj[m] - ft);
+                        acc[m] = fmin(acc[m], fma(d, d, v));
+                    }
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < ED_ROW_NI; ++m) {
+            const int i = i0 + lane + 64 * m;
+            if (live && i < L) out[base + i] = SQRT ? sqrt(acc[m]) : acc[m];
+        }
+    }
+}
+
+// a pass along a strided axis: in, out [A][L][B], B contiguous.  grid A * nb * ni (nb = ceil(B / 64), ni = ceil(L / 64)), block 256 =
+// 64 columns b x 4 thread rows; thread row ty owns the outputs i = 64 * ic + 16 * ty + m, m < 16
+template <bool SQRT>
+__global__ void __launch_bounds__(PO_BLOCK) po_edt_col_kernel(const double* __restrict__ in, double* __restrict__ out, int L, long B, long nb,
+                                                              int ni, double sp) {
+    __shared__ double tile[ED_COL_T][ED_COL_T];          // [j][b]
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    long bid = blockIdx.x;
+    const int ic = (int)(bid % ni);
+    bid /= ni;
+    const long bb = bid % nb, a = bid / nb;
+    const long b = bb * ED_COL_T + tx;
+    const bool live = b < B;
+    const long base = a * (long)L * B + (live ? b : 0);
+    const int i_base = ic * ED_COL_T + ty * ED_COL_NI;
+    double acc[ED_COL_NI];
+#pragma unroll
+    for (int m = 0; m < ED_COL_NI; ++m) acc[m] = (double)INFINITY;
+    for (int j0 = 0; j0 < L; j0 += ED_COL_T) {
+        __syncthreads();
+        for (int r = ty; r < ED_COL_T; r += PO_BLOCK / 64) tile[r][tx] = (live && j0 + r < L) ? in[base + (long)(j0 + r) * B] : (double)INFINITY;
+        __syncthreads();
+        const int nj = min(ED_COL_T, L - j0);
+        const double d0 = (double)(i_base - j0);
+        for (int t = 0; t < nj; ++t) {
+            const double v = tile[t][tx], dj = d0 - (double)t;
+#pragma unroll
+            for (int m = 0; m < ED_COL_NI; ++m) {
+                const double d = sp * (dj + (double)m);
+                acc[m] = fmin(acc[m], fma(d, d, v));
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < ED_COL_NI; ++m) {
+        const int i = i_base + m;
+        if (live && i < L) out[base + (long)i * B] = SQRT ? sqrt(acc[m]) : acc[m];
+    }
+}
+
+// fixed-order block sum / order-free maximum over PO_BLOCK threads; results valid in thread 0
+__device__ __forceinline__ void po_block_sum_max(double& s, double& mx, double* rs, double* rm) {
+    rs[threadIdx.x] = s;
+    rm[threadIdx.x] = mx;
+    __syncthreads();
+    for (int o = PO_BLOCK / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            rs[threadIdx.x] += rs[threadIdx.x + o];
+            rm[threadIdx.x] = fmax(rm[threadIdx.x], rm[threadIdx.x + o]);
+        }
+        __syncthreads();
+    }
+    s = rs[0];
+    mx = rm[0];
+}
+
+// part [gridDim.x][2] = (sum, max) of dist over the voxels where surf != 0, this block's grid-stride share
+__global__ void __launch_bounds__(PO_BLOCK) po_surface_reduce_kernel(const unsigned char* __restrict__ surf, const double* __restrict__ dist,
+                                                                     long n, double* __restrict__ part) {
+    __shared__ double rs[PO_BLOCK], rm[PO_BLOCK];
+    double s = 0.0, mx = 0.0;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK)
+        if (surf[e]) {
+            const double d = dist[e];
+            s += d;
+            mx = fmax(mx, d);
+        }
+    po_block_sum_max(s, mx, rs, rm);
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = s;
+        part[2 * blockIdx.x + 1] = mx;
+    }
+}
+
+// one block: row [6] = nP, nT, |surface(P)|, |surface(T)|, sum, max from the counts [K+1][2] of either side and the partials
+// part [2][nblk][2] of the two directions; sum and max are nan when either surface is empty
+__global__ void __launch_bounds__(PO_BLOCK) po_surface_final_kernel(const int* __restrict__ cp, const int* __restrict__ ct,
+                                                                    const double* __restrict__ part, int nblk, int k,
+                                                                    double* __restrict__ row) {
+    __shared__ double rs[PO_BLOCK], rm[PO_BLOCK];
+    double s = 0.0, mx = 0.0;
+    if ((int)threadIdx.x < nblk) {
+        const double* a = part + 2 * threadIdx.x;
+        const double* b = part + 2 * (size_t)nblk + 2 * threadIdx.x;
+        s = a[0] + b[0];
+        mx = fmax(a[1], b[1]);
+    }
+    po_block_sum_max(s, mx, rs, rm);
+    if (threadIdx.x == 0) {
+        const int sp = cp[2 * k + 1], st = ct[2 * k + 1];
+        const bool empty = sp == 0 || st == 0;
+        row[0] = (double)cp[2 * k];
+        row[1] = (double)ct[2 * k];
+        row[2] = (double)sp;
+        row[3] = (double)st;
+        row[4] = empty ? (double)NAN : s;
+        row[5] = empty ? (double)NAN : mx;
+    }
+}
+
 static int po_blocks(long n) {
     const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
     return (int)(b < 1 ? 1 : (b < PO_MAXBLK ? b : PO_MAXBLK));
@@ -203,6 +440,40 @@ static void po_launch(dim3 grid, hipStream_t stream, const float* prob, const in
     hipLaunchKernelGGL((po_restore_kernel<VEC4, PACK>), grid, dim3(PO_BLOCK), 0, stream, prob, values, K, out, H, W, RH, RW,
                        (double)RH / (double)H, (double)RW / (double)W, OH, OW, ar, ac, C, order);
 }
+
+// [S,H,W] with 1 <= H, W and fewer than 2^31 voxels
+static bool po_volume_ok(int S, int H, int W) { return H >= 1 && W >= 1 && (long)S * H * W < 0x7fffffffL; }
+static bool po_spacing_ok(double d) { return isfinite(d) && d > 0.0; }
+
+// sites [S,H,W] -> a [S,H,W] distances in mm; b is scratch of the same size.  W pass sites -> a, H pass a -> b, S pass b -> a (sqrt)
+static int po_edt(const unsigned char* sites, double* a, double* b, int S, int H, int W, double dz, double dy, double dx, hipStream_t st) {
+    const long rows = (long)S * H;
+    hipLaunchKernelGGL((po_edt_row_kernel<unsigned char, false>), dim3((unsigned)((rows + 3) / 4)), dim3(PO_BLOCK), 0, st, sites, a, rows, W,
+                       dx);
+    long nb = ((long)W + ED_COL_T - 1) / ED_COL_T;
+    int ni = (H + ED_COL_T - 1) / ED_COL_T;
+    hipLaunchKernelGGL((po_edt_col_kernel<false>), dim3((unsigned)((long)S * nb * ni)), dim3(PO_BLOCK), 0, st, a, b, H, (long)W, nb, ni, dy);
+    const long plane = (long)H * W;
+    nb = (plane + ED_COL_T - 1) / ED_COL_T;
+    ni = (S + ED_COL_T - 1) / ED_COL_T;
+    hipLaunchKernelGGL((po_edt_col_kernel<true>), dim3((unsigned)(nb * ni)), dim3(PO_BLOCK), 0, st, b, a, S, plane, nb, ni, dz);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+static int po_surface(const unsigned char* label, const int* values, unsigned char* surf, int* counts, int S, int H, int W, int K,
+                      hipStream_t st) {
+    const long n = (long)S * H * W;
+    if (counts) {
+        const hipError_t rc = hipMemsetAsync(counts, 0, sizeof(int) * 2 * (size_t)(K + 1), st);
+        if (rc != hipSuccess) return (int)rc;
+    }
+    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
+    hipLaunchKernelGGL(po_surface_kernel, dim3((unsigned)(b < PO_SURF_MAXBLK ? b : PO_SURF_MAXBLK)), dim3(PO_BLOCK), 0, st, label, values, K,
+                       surf, counts, S, H, W);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+static long po_round8(long bytes) { return (bytes + 7) / 8; }
 
 extern "C" {
 
@@ -236,6 +507,66 @@ int mmseg_label_overlap(const unsigned char* pred, const unsigned char* truth, c
     if (rc != hipSuccess) return (int)rc;
     const dim3 grid((unsigned)po_blocks(n), S);
     hipLaunchKernelGGL(po_overlap_kernel, grid, dim3(PO_BLOCK), 0, (hipStream_t)stream, pred, truth, values, K, counts, n);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// label [S,H,W] uint8, values [K] int32 (device) -> surf [K+1,S,H,W] uint8 0 / 1, every byte written; counts [K+1][2] int32 =
+// (|foreground|, |surface|) per problem, zeroed here on the stream, or null
+int mmseg_label_surface(const unsigned char* label, const int* values, unsigned char* surf, int* counts, int S, int H, int W, int K,
+                        void* stream) {
+    if (S <= 0) return 0;
+    if (!label || !values || !surf || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES) return (int)hipErrorInvalidValue;
+    return po_surface(label, values, surf, counts, S, H, W, K, (hipStream_t)stream);
+}
+
+// sites [S,H,W] uint8 -> out [S,H,W] fp64: mm to the nearest non-zero voxel (+inf without one); tmp: S * H * W doubles of scratch
+int mmseg_distance_to_sites(const unsigned char* sites, double* out, double* tmp, int S, int H, int W, double dz, double dy, double dx,
+                            void* stream) {
+    if (S <= 0) return 0;
+    if (!sites || !out || !tmp || !po_volume_ok(S, H, W) || !po_spacing_ok(dz) || !po_spacing_ok(dy) || !po_spacing_ok(dx))
+        return (int)hipErrorInvalidValue;
+    return po_edt(sites, out, tmp, S, H, W, dz, dy, dx, (hipStream_t)stream);
+}
+
+// doubles of workspace of mmseg_surface_metrics: two distance maps, the partials, the counts and the 2 (K + 1) surface volumes
+long mmseg_surface_metrics_workspace_doubles(int S, int H, int W, int K) {
+    if (S <= 0 || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES) return 0;
+    const long n = (long)S * H * W;
+    return 2 * n + 4 * PO_RED_BLOCKS + po_round8((long)sizeof(int) * 4 * (K + 1)) + po_round8(2 * (long)(K + 1) * n);
+}
+
+// pred, truth [S,H,W] uint8 -> table [K+1,6] fp64 = nP, nT, |surface(P)|, |surface(T)|, sum and max of the surface distances in mm
+// (nan when either surface is empty).  A loop of launches over the K + 1 problems on the stream.
+int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
+                          int H, int W, int K, double dz, double dy, double dx, void* stream) {
+    if (S <= 0) return 0;
+    if (!pred || !truth || !values || !table || !ws || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES || !po_spacing_ok(dz) ||
+        !po_spacing_ok(dy) || !po_spacing_ok(dx))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)S * H * W;
+    double* da = ws;
+    double* db = da + n;
+    double* part = db + n;
+    int* cp = reinterpret_cast<int*>(part + 4 * PO_RED_BLOCKS);
+    int* ct = cp + 2 * (K + 1);
+    unsigned char* sp = reinterpret_cast<unsigned char*>(reinterpret_cast<double*>(cp) + po_round8((long)sizeof(int) * 4 * (K + 1)));
+    unsigned char* stv = sp + (size_t)(K + 1) * n;
+    int rc = po_surface(pred, values, sp, cp, S, H, W, K, st);
+    if (rc) return rc;
+    rc = po_surface(truth, values, stv, ct, S, H, W, K, st);
+    if (rc) return rc;
+    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
+    const int nblk = (int)(b < PO_RED_BLOCKS ? b : PO_RED_BLOCKS);
+    for (int k = 0; k <= K; ++k) {
+        rc = po_edt(stv + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);          // distance to surface(T), summed over surface(P)
+        if (rc) return rc;
+        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, sp + (size_t)k * n, da, n, part);
+        rc = po_edt(sp + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
+        hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 6 * k);
+    }
     return MMSEG_CHECK_LAUNCH();
 }
 

@@ -4,6 +4,7 @@
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
+                         [--predict_surface true|false]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
@@ -29,6 +30,15 @@ from .utils.config import EasyDict
 _PKG = __package__
 
 
+def true_or_false(text):
+    """`true` / `false` of --predict_surface (argparse's type=bool reads every non-empty string as True)"""
+    if text.lower() in ('true', '1', 'yes'):
+        return True
+    if text.lower() in ('false', '0', 'no'):
+        return False
+    raise argparse.ArgumentTypeError('expected true or false, got %r' % text)
+
+
 def parse_arguments(argv=None):
     ap = argparse.ArgumentParser(description='multimodal segmentation experiment')
     ap.add_argument('--config', required=True, help='module name under configuration/')
@@ -44,6 +54,8 @@ def parse_arguments(argv=None):
     ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
     ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
     ap.add_argument('--predict_order', type=int, choices=[0, 1], default=1, help='resampling back to the raw grid: nearest / bilinear')
+    ap.add_argument('--predict_surface', type=true_or_false, default=True, metavar='true|false',
+                    help='also score labelled files that carry slice_spacing in mm (RAVD, ASSD, MSSD: results_surface_<modality>.csv)')
     return ap.parse_args(argv)
 
 
@@ -190,7 +202,8 @@ class Experiment(object):
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()
-            VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order)
+            VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
+                                              surface=getattr(args, 'predict_surface', True))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 

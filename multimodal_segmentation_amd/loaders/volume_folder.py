@@ -9,6 +9,8 @@ device (csrc/preprocess.hip).  Reading DICOM / PNG stays out of scope: a folder 
     <root>/<name>.npz        image [S,H,W] (any integer or float dtype), label [S,H,W] uint8 grey values, resolution [2] mm per
                              pixel along rows and columns.  `label` may be missing in a folder that is only predicted on
                              (load_volume_for_prediction, volume_predictor.py); the training surface then refuses the file.
+                             `slice_spacing` (optional): one positive float, mm between consecutive slices of the file.  Only the
+                             scores in mm of volume_predictor.py use it; training, validation and testing ignore it.
 
 `slices` (optional) lists [start, stop) ranges applied in order: how a user states which slices of the acquisitions show the same
 anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all modalities of a volume must hold the same number of
@@ -124,14 +126,15 @@ class VolumeFolderLoader(object):
     def read_volume(self, volume, modality, require_label=True):
         """raw (image [S,H,W], label [S,H,W] uint8, resolution (2,)) of one volume and modality, `slices` applied.  With
         require_label=False a file without a `label` array yields label = None (a scan to be segmented)."""
-        image, label, res, selected = self._read_file(volume, modality, require_label)
+        image, label, res, selected, _ = self._read_file(volume, modality, require_label)
         if selected is not None:
             image = image[selected]
             label = None if label is None else label[selected]
         return image, label, res
 
     def _read_file(self, volume, modality, require_label):
-        """the arrays as stored (all slices of the file) and the indices that `slices` selects, in order (None: every slice)"""
+        """the arrays as stored (all slices of the file), the indices that `slices` selects, in order (None: every slice), and the
+        file's `slice_spacing` in mm (None when the file holds none)"""
         entry = self.manifest['volumes'][str(volume)][modality]
         path = os.path.join(self.data_folder, entry['file'])
         if not os.path.isfile(path):
@@ -142,6 +145,11 @@ class VolumeFolderLoader(object):
                     raise ValueError('%s: no array %r' % (path, key))
             image, res = z['image'], np.asarray(z['resolution'], np.float64).reshape(-1)
             label = z['label'] if 'label' in z.files else None
+            spacing = np.asarray(z['slice_spacing'], np.float64).reshape(-1) if 'slice_spacing' in z.files else None
+        if spacing is not None:
+            if spacing.shape != (1,) or not np.isfinite(spacing[0]) or spacing[0] <= 0:
+                raise ValueError('%s: slice_spacing must be one finite number > 0 (mm between consecutive slices), got %s' % (path, spacing))
+            spacing = float(spacing[0])
         if (image.ndim != 3 or res.shape != (2,) or res.min() <= 0
                 or (label is not None and (label.shape != image.shape or label.dtype != np.uint8))):
             raise ValueError('%s: expected image [S,H,W], label [S,H,W] uint8 and resolution [2] > 0, got %s %s, %s %s, %s'
@@ -154,7 +162,7 @@ class VolumeFolderLoader(object):
                     raise ValueError('volume %s, modality %s: slice range [%d, %d) outside the %d slices of %s'
                                      % (volume, modality, a, b, image.shape[0], path))
             selected = np.concatenate([np.arange(a, b) for a, b in ranges])
-        return image, label, res, selected
+        return image, label, res, selected, spacing
 
     def geometry(self, H, W, res):
         """(RH, RW), rows, cols: the resampled extent of an H x W slice at `res` mm and its crop / pad index maps to input_shape"""
@@ -168,12 +176,13 @@ class VolumeFolderLoader(object):
         """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
         [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
         way back needs -- file, raw_shape (S_file, H, W), slices (the selected file indices, in order), resolution, resampled (RH, RW),
-        rows / cols (lo, kept, before) and label (the selected raw slices [S,H,W] uint8, or None)."""
+        rows / cols (lo, kept, before), label (the selected raw slices [S,H,W] uint8, or None) and slice_spacing (mm between the file's
+        slices, or None)."""
         device = nn.default_device()
         OH, OW = self.input_shape[:2]
         images, geometry = [], []
         for mod in self.modalities:
-            image, label, res, selected = self._read_file(volume, mod, False)
+            image, label, res, selected, spacing = self._read_file(volume, mod, False)
             S_file, H, W = image.shape
             if selected is None:
                 selected = np.arange(S_file)
@@ -183,7 +192,7 @@ class VolumeFolderLoader(object):
             images.append(container)
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
-                                 label=None if label is None else np.ascontiguousarray(label[selected])))
+                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
         counts = [g.shape[0] for g in images]
         if len(set(counts)) != 1:
             raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the matching '

@@ -1619,6 +1619,77 @@ def label_overlap(pred, truth, values):
     return counts
 
 
+def _ws_f64(tag, ndoubles, device):
+    """_ws for the fp64 scratch of the scores in mm (grow-only, per tag, device and stream)"""
+    key = (tag, device, _sid(device))
+    buf = _workspaces.get(key)
+    n = max(int(ndoubles), 1)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(n, dtype=torch.float64, device=device)
+        _workspaces[key] = buf
+    return buf
+
+
+def _volume_args(op, label, values, others=()):
+    """shared checks of the scores in mm: uint8 [S,H,W] volumes of one shape on one device, values [K] int32, 1 <= K <= 16"""
+    K = int(values.numel())
+    vols = (label,) + tuple(others)
+    if (label.dim() != 3 or any(v.dtype != torch.uint8 or tuple(v.shape) != tuple(label.shape) or v.device != label.device for v in vols)
+            or values.dtype != torch.int32 or not 1 <= K <= 16 or label.numel() >= 2 ** 31 - 1):
+        raise ValueError('%s: volumes %s, values %s %s (expected uint8 [S,H,W] of one shape with fewer than 2^31 voxels and 1..16 int32 '
+                         'values)' % (op, ', '.join('%s %s' % (tuple(v.shape), v.dtype) for v in vols), tuple(values.shape), values.dtype))
+    return K
+
+
+def _spacing_args(op, spacing):
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3 or any(not (v > 0 and v < float('inf')) for v in sp):
+        raise ValueError('%s: spacing must be three finite positive numbers (mm between slices, rows, columns), got %r' % (op, spacing))
+    return sp
+
+
+def label_surface(label, values):
+    """label [S,H,W] uint8 grey values on the device, values [K] int32 -> uint8 [K+1,S,H,W], 0 or 1: the surface voxels of the K + 1
+    binary problems "== values[k]" and, last, "equals any of values" (csrc/postprocess.hip).  A surface voxel is a foreground voxel
+    with at least one of its six face neighbours in the background or outside the volume."""
+    K = _volume_args('label_surface', label, values)
+    S, H, W = label.shape
+    surf = _new((K + 1, S, H, W), label, torch.uint8)
+    N.call('mmseg_label_surface', _c(label), values, surf, None, S, H, W, K)
+    return surf
+
+
+def distance_to_sites(sites, spacing):
+    """sites [S,H,W] uint8 on the device, spacing (dz, dy, dx) in mm -> fp64 [S,H,W]: the exact Euclidean distance in mm to the
+    nearest non-zero voxel, +inf everywhere when there is none (csrc/postprocess.hip: three per-axis minimum passes over fp64
+    squared distances, one square root)"""
+    if sites.dim() != 3 or sites.dtype != torch.uint8 or sites.numel() >= 2 ** 31 - 1:
+        raise ValueError('distance_to_sites: sites %s %s (expected uint8 [S,H,W] with fewer than 2^31 voxels)'
+                         % (tuple(sites.shape), sites.dtype))
+    dz, dy, dx = _spacing_args('distance_to_sites', spacing)
+    S, H, W = sites.shape
+    out = _new((S, H, W), sites, torch.float64)
+    N.call('mmseg_distance_to_sites', _c(sites), out, _ws_f64('edt', sites.numel(), sites.device), S, H, W, dz, dy, dx)
+    return out
+
+
+def surface_metrics(pred, truth, values, spacing):
+    """pred, truth [S,H,W] uint8 grey values on the device, values [K] int32, spacing (dz, dy, dx) in mm -> fp64 [K+1,6] per binary
+    problem (the K organs, then their union): nP, nT, |surface(P)|, |surface(T)|, the sum and the maximum over both surfaces of the
+    distance in mm to the other surface; the last two are nan when either surface is empty (csrc/postprocess.hip).  RAVD, ASSD and
+    MSSD follow on the host (volume_predictor.chaos_from_table)."""
+    K = _volume_args('surface_metrics', pred, values, (truth,))
+    dz, dy, dx = _spacing_args('surface_metrics', spacing)
+    S, H, W = pred.shape
+    table = torch.zeros((K + 1, 6), dtype=torch.float64, device=pred.device)
+    if S == 0:
+        table[:, 4:] = float('nan')
+        return table
+    ws = _ws_f64('surface_metrics', N.call('mmseg_surface_metrics_workspace_doubles', S, H, W, K), pred.device)
+    N.call('mmseg_surface_metrics', _c(pred), _c(truth), values, table, ws, S, H, W, K, dz, dy, dx)
+    return table
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

@@ -12,9 +12,17 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
     <out>/predictions.json                 settings only: source folder, mode, order, model folder, per file the selected slices
     <out>/results_native_<modality>.csv    where the input files carry a `label`: Dice on the raw grid, header and row format of
                                            model_tester.write_results, one row per labelled volume
+    <out>/results_surface_<modality>.csv   where they also carry `slice_spacing`: RAVD (%), ASSD and MSSD (mm) of the union of the
+                                           organs and of every organ, one row per scored volume
 
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
-from the counts summed over the organs, then the mean over the selected slices."""
+from the counts summed over the organs, then the mean over the selected slices.
+
+The scores in mm (build-defined: the reference scores Dice only; the rules restate the metric set of the CHAOS challenge from memory,
+INTEGRATION.md section 5) are taken on the whole file grid [S_file,H,W]: the prediction is scattered to its file positions on the
+device, the truth slices that `slices` does not select are zero, and ops.surface_metrics returns one [K+1,6] table per volume, the only
+thing that leaves the device.  `score_volume` and `write_scores` are shared with tools/score_predictions.py, which scores label
+volumes written earlier (`score_folder`)."""
 import json
 import logging
 import os
@@ -48,6 +56,105 @@ def dice_from_counts(counts):
     return score(c.sum(axis=1)), [score(c[:, k]) for k in range(c.shape[1])]
 
 
+def chaos_from_table(table):
+    """table [K+1,6] = nP, nT, |surface(P)|, |surface(T)|, sum, max of ops.surface_metrics -> [K+1,3] = RAVD (%), ASSD (mm), MSSD (mm):
+    RAVD = 100 |nP - nT| / nT (nan when nT = 0), ASSD = sum / (|surface(P)| + |surface(T)|), MSSD = max; the last two are nan
+    where the table says so (an empty surface)"""
+    t = np.asarray(table, np.float64)
+    out = np.full((t.shape[0], 3), np.nan)
+    for k, (n_p, n_t, s_p, s_t, total, largest) in enumerate(t):
+        if n_t > 0:
+            out[k, 0] = 100.0 * abs(n_p - n_t) / n_t
+        if s_p > 0 and s_t > 0:
+            out[k, 1], out[k, 2] = total / (s_p + s_t), largest
+    return out
+
+
+def score_volume(pred, label, values, geometry, surface=True):
+    """pred, label: uint8 [S,H,W] on the device, the selected slices of one file in order; geometry: the record of
+    loader.load_volume_for_prediction (raw_shape, slices, resolution, slice_spacing are read) -> (joint Dice, [per organ], scores in
+    mm [K+1,3] with the union LAST, or None when they are not asked for or the file holds no slice_spacing)"""
+    joint, per_organ = dice_from_counts(nn.to_numpy(ops.label_overlap(pred, label, values)))
+    if not surface or geometry.get('slice_spacing') is None:
+        return joint, per_organ, None
+    where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=pred.device)
+    grid = tuple(int(n) for n in geometry['raw_shape'])
+    on_grid = [torch.zeros(grid, dtype=torch.uint8, device=pred.device).index_copy_(0, where, x) for x in (pred, label)]
+    spacing = (float(geometry['slice_spacing']), float(geometry['resolution'][0]), float(geometry['resolution'][1]))
+    table = ops.surface_metrics(on_grid[0], on_grid[1], values, spacing)
+    return joint, per_organ, chaos_from_table(nn.to_numpy(table))
+
+
+def write_surface_results(path, rows, num_masks):
+    """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
+    cols = ['Vol', 'RAVD', 'ASSD', 'MSSD'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('RAVD', 'ASSD', 'MSSD')]
+    with open(path, 'w') as f:
+        f.write(', '.join(cols) + '\n')
+        for vol, scores in rows:
+            ordered = np.concatenate([scores[-1:], scores[:-1]], axis=0).reshape(-1)
+            f.write(', '.join([str(vol)] + ['%.3f' % v for v in ordered]) + '\n')
+
+
+def write_scores(out_folder, modalities, rows, surface_rows, num_masks):
+    """results_native_<modality>.csv / results_surface_<modality>.csv for the modalities that have rows"""
+    for m, name in enumerate(modalities):
+        if rows[m]:
+            write_results(os.path.join(out_folder, 'results_native_%s.csv' % name), rows[m], num_masks)
+        if surface_rows[m]:
+            write_surface_results(os.path.join(out_folder, 'results_surface_%s.csv' % name), surface_rows[m], num_masks)
+
+
+def collect_scores(rows, surface_rows, m, volume, modality, scores, geometry, surface):
+    joint, per_organ, in_mm = scores
+    rows[m].append((volume, joint, per_organ))
+    log.info('volume %s, %s: Dice on the raw grid %.3f' % (volume, modality, joint))
+    if in_mm is not None:
+        surface_rows[m].append((volume, in_mm))
+        log.info('volume %s, %s: RAVD %.3f %%, ASSD %.3f mm, MSSD %.3f mm' % ((volume, modality) + tuple(in_mm[-1])))
+    elif surface:
+        log.info("volume %s, %s: %s holds no 'slice_spacing', so no scores in mm" % (volume, modality, geometry['file']))
+
+
+def score_folder(pred_folder, data_folder, out_folder=None, surface=True):
+    """Score label volumes written earlier (by VolumePredictor.run or by another program: <file name of the input>.npz with `label`
+    [S_file,H,W] uint8) against the labelled files of `data_folder`; writes the CSV files of VolumePredictor.run into out_folder
+    (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json."""
+    loader = VolumeFolderLoader(data_folder)
+    out_folder = out_folder or pred_folder
+    os.makedirs(out_folder, exist_ok=True)
+    volumes = list(loader.manifest['volumes'])
+    settings = os.path.join(pred_folder, 'predictions.json')
+    if os.path.isfile(settings):
+        with open(settings) as f:
+            listed = [str(e['volume']) for e in json.load(f)['files'].values()]
+        volumes = [v for i, v in enumerate(listed) if v not in listed[:i] and v in loader.manifest['volumes']]
+    device = nn.default_device()
+    values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
+    rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
+    for v in volumes:
+        for m, mod in enumerate(loader.modalities):
+            entry = loader.manifest['volumes'][v][mod]
+            path = os.path.join(pred_folder, entry['file'])
+            if not os.path.isfile(path):
+                continue
+            image, label, res, selected, spacing = loader._read_file(v, mod, False)
+            if label is None:
+                continue
+            with np.load(path) as z:
+                pred = z['label']
+            if pred.shape != label.shape or pred.dtype != np.uint8:
+                raise ValueError('%s: expected label %s uint8 (the grid of %s), got %s %s'
+                                 % (path, label.shape, entry['file'], pred.shape, pred.dtype))
+            selected = np.arange(label.shape[0]) if selected is None else selected
+            geo = dict(file=entry['file'], raw_shape=label.shape, slices=[int(i) for i in selected], resolution=res, slice_spacing=spacing)
+            scores = score_volume(nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8),
+                                  nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface)
+            collect_scores(rows, surface_rows, m, v, mod, scores, geo, surface)
+    write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
+    return ({name: rows[m] for m, name in enumerate(loader.modalities)},
+            {name: surface_rows[m] for m, name in enumerate(loader.modalities)})
+
+
 class VolumePredictor(object):
     def __init__(self, model, conf):
         self.model, self.conf = model, conf
@@ -60,7 +167,7 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
-    def run(self, folder, out_folder, volumes=None, mode='simple', order=1):
+    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True):
         if mode not in FUSION_MODES:
             raise ValueError('Unknown mode: %r (expected one of %s)' % (mode, ', '.join(FUSION_MODES)))
         if order not in (0, 1):
@@ -80,7 +187,7 @@ class VolumePredictor(object):
         os.makedirs(out_folder, exist_ok=True)
         device = nn.default_device()
         values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
-        rows = [[] for _ in loader.modalities]
+        rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
         files = {}
         for v in volumes:
             images, geometry = loader.load_volume_for_prediction(v)
@@ -88,17 +195,14 @@ class VolumePredictor(object):
                 prob = self.predict_volume(m, mode, images)
                 pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
                 if geo['label'] is not None:
-                    counts = ops.label_overlap(pred, nn.host_to_device(geo['label'], device, np.uint8), values)
-                    joint, per_organ = dice_from_counts(nn.to_numpy(counts))
-                    rows[m].append((v, joint, per_organ))
-                    log.info('volume %s, %s: Dice on the raw grid %.3f' % (v, loader.modalities[m], joint))
+                    scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface)
+                    collect_scores(rows, surface_rows, m, v, loader.modalities[m], scores, geo, surface)
                 label = np.zeros(geo['raw_shape'], np.uint8)
                 label[geo['slices']] = pred.cpu().numpy()
-                np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'])
-                files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'])
-        for m, name in enumerate(loader.modalities):
-            if rows[m]:
-                write_results(os.path.join(out_folder, 'results_native_%s.csv' % name), rows[m], loader.num_masks)
+                extra = {} if geo['slice_spacing'] is None else dict(slice_spacing=float(geo['slice_spacing']))
+                np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
+                files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
+        write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(dict(source_folder=folder, mode=mode, order=order, model_folder=self.conf.get('folder'),
                            label_values=loader.label_values, files=files), f, indent=1)

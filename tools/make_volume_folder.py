@@ -10,7 +10,7 @@ same anatomy; the later modalities carry extra leading / trailing slices, and th
 ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
-                                       [--raw_size LO HI] [--name chaos] [--unlabelled]
+                                       [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -59,13 +59,18 @@ def default_splits(ids):
     return out
 
 
-def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False):
+def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False,
+                 slice_spacing=None):
     """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
-    draws included, is as without it"""
+    draws included, is as without it.  slice_spacing = (LO, HI): every file also stores `slice_spacing`, mm between its slices, drawn
+    from [LO, HI] by a generator of its own, so that every other draw is as without it"""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
     rng = np.random.RandomState(seed)
+    spacing_rng = np.random.RandomState(seed + 1000003)
+    if slice_spacing is not None and not 0 < slice_spacing[0] <= slice_spacing[1]:
+        raise ValueError('slice_spacing must be 0 < LO <= HI, got %r' % (slice_spacing,))
     values = label_values(masks)
     ids = list(range(1, volumes + 1))
     manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
@@ -83,6 +88,8 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
             fname = 'vol%02d_%s.npz' % (v, mod_name)
             arrays = dict(image=image, resolution=res.astype(np.float64)) if unlabelled else dict(image=image, label=label,
                                                                                                    resolution=res.astype(np.float64))
+            if slice_spacing is not None:
+                arrays['slice_spacing'] = np.float64(spacing_rng.uniform(slice_spacing[0], slice_spacing[1]))
             np.savez_compressed(os.path.join(out, fname), **arrays)
             entry[mod_name] = {'file': fname}
             if before or after:
@@ -105,8 +112,10 @@ def main(argv=None):
     ap.add_argument('--raw_size', type=int, nargs=2, metavar=('LO', 'HI'), help='draw the raw slice extents from [LO, HI]')
     ap.add_argument('--name', default='chaos')
     ap.add_argument('--unlabelled', action='store_true', help='write files without a label array (a folder to predict on)')
+    ap.add_argument('--slice_spacing', type=float, nargs=2, metavar=('LO', 'HI'),
+                    help='store a slice spacing in mm per file, drawn from [LO, HI] (what the scores in mm need)')
     a = ap.parse_args(argv)
-    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled)
+    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 

@@ -1,0 +1,37 @@
+#!/usr/bin/env python
+"""Score label volumes that were written earlier -- by `experiment.py --predict_folder` or by another program -- against a labelled
+folder of volumes (loaders/volume_folder.py), without a model: Dice on the raw grid (results_native_<modality>.csv) and, for files
+that carry `slice_spacing`, RAVD, ASSD and MSSD in mm (results_surface_<modality>.csv), through the code path of the predictor
+(volume_predictor.score_folder, on the device).
+
+PRED_FOLDER holds one `<file name of the input>.npz` with `label` [S_file,H,W] uint8 per scored file; files that are missing there, or
+that carry no label in DATA_FOLDER, are left out.
+
+    python tools/score_predictions.py PRED_FOLDER DATA_FOLDER [--out OUT] [--surface true|false]
+"""
+import argparse
+import logging
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from multimodal_segmentation_amd.experiment import true_or_false
+from multimodal_segmentation_amd.volume_predictor import score_folder
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('pred_folder')
+    ap.add_argument('data_folder')
+    ap.add_argument('--out', help='where to write the CSV files (default: PRED_FOLDER)')
+    ap.add_argument('--surface', type=true_or_false, default=True, metavar='true|false', help='also the scores in mm')
+    a = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format='%(message)s')
+    rows, surface_rows = score_folder(a.pred_folder, a.data_folder, a.out, a.surface)
+    for name in rows:
+        print('%s: %d volumes scored, %d of them in mm' % (name, len(rows[name]), len(surface_rows[name])))
+
+
+if __name__ == '__main__':
+    main()
