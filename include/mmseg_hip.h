@@ -430,6 +430,25 @@ long mmseg_surface_metrics_workspace_doubles(int S, int H, int W, int K);
 int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
                           int H, int W, int K, double dz, double dy, double dx, void* stream);
 
+/* ---- the largest connected component of every organ (csrc/postprocess.hip; build-defined: these replace nothing in the reference,
+ * which writes no segmentation) -------------------------------------------------------------------------------------------------------
+ * Two voxels of label [S,H,W] uint8 are joined when they hold the same grey value, that value is one of values [K] (int32, device)
+ * and they are neighbours: connectivity 6 (faces) or 26 (faces, edges, corners).  S * H * W < 2^31 - 1, 1 <= H, W, 1 <= K <= 16;
+ * anything else, a null pointer or another connectivity is refused (hipErrorInvalidValue, nothing is launched).  S == 0 does nothing.
+ * comp [S,H,W] int32, every element written: 0 where the grey value is none of `values`, else 1 + the smallest linear index
+ * (s * H * W + y * W + x) in the voxel's component.  Canonical: independent of the order of blocks and atomics, so two runs are
+ * bitwise equal.  All K organs are labelled in one pass (a union-find in comp itself; parents only decrease). */
+int mmseg_label_components(const unsigned char* label, const int* values, int* comp, int S, int H, int W, int K, int connectivity,
+                           void* stream);
+/* bytes of ws for mmseg_keep_largest_components; 0 for arguments that it would refuse */
+long mmseg_keep_largest_workspace_bytes(int S, int H, int W, int K);
+/* out [S,H,W] uint8 = label, except that a voxel of values[k] outside the largest component of values[k] becomes 0 (of equally large
+ * components the one with the smallest linear index stays); other grey values are copied.  stats [K,3] int32 = (number of
+ * components, voxels of values[k] before, voxels kept), (0, 0, 0) for an organ without voxels.  Every byte of out and stats is
+ * written.  ws (8-byte aligned) is the only scratch; integer atomics only, so two runs are bitwise equal. */
+int mmseg_keep_largest_components(const unsigned char* label, const int* values, unsigned char* out, int* stats, int* ws, int S, int H,
+                                  int W, int K, int connectivity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,12 @@
 // mmseg_surface_metrics: per problem the two distance maps, each reduced over the other side's surface: per-thread partial sums in
 //   grid-stride order, a fixed LDS tree per block, partials [blocks][2] = (sum, max), and one block that adds the partials in a fixed
 //   tree: no floating-point atomics.  Only the [K+1,6] table is meant to leave the device.
+//
+// The largest connected component of every organ (build-defined; the rule is in INTEGRATION.md section 5).
+// mmseg_label_components: label [S,H,W] -> comp [S,H,W] int32 = 1 + the smallest linear index of the voxel's component, 0 for a voxel
+//   that is no organ's; all K organs in one pass (a union-find in comp itself, see the kernels).
+// mmseg_keep_largest_components: the components, their sizes (integer atomics on the root's slot), per organ one 64-bit atomicMax on
+//   (size << 32) | (0xffffffff - root), and a pass that zeroes the organ voxels outside their organ's winner.
 #include "common.hpp"
 #include <math.h>
 
@@ -475,6 +481,234 @@ static int po_surface(const unsigned char* label, const int* values, unsigned ch
 
 static long po_round8(long bytes) { return (bytes + 7) / 8; }
 
+// ---- connected components per organ, and the largest one of each --------------------------------------------------------------------
+// A union-find whose parent array is `comp` itself: comp[e] = 1 + (linear index of the parent of voxel e), 0 for a voxel that is no
+// organ's; a root points to itself.  A link always hangs the larger index below the smaller one (an integer atomic minimum), so
+// parents only decrease, every chain ends, and the root of a set is its smallest index: the labelling is canonical whatever the
+// order of blocks and atomics.  Three launches, none of which waits for another block:
+//   po_cc_local_kernel    a tile of 4 x 8 x 32 voxels per block, resolved in LDS (links along the row for free, the other backward
+//                         neighbours by unions), written out as global indices
+//   po_cc_merge_kernel    every voxel with a backward neighbour in another tile joins the two sets in global memory
+//   po_cc_flatten_kernel  comp[e] = 1 + root
+// "Backward" neighbours are those with a smaller linear index: 3 of the 6 face neighbours, 13 of the 26.
+#define CC_TX 32
+#define CC_TY 8
+#define CC_TZ 4
+#define CC_TILE (CC_TX * CC_TY * CC_TZ)
+
+// (dz, dy, dx) of the backward neighbours: the row neighbour, the other two faces, then the ten that only 26-connectivity has
+__device__ const signed char cc_off[13][3] = {{0, 0, -1}, {0, -1, 0},  {-1, 0, 0},  {0, -1, -1}, {0, -1, 1}, {-1, 0, -1}, {-1, 0, 1},
+                                              {-1, -1, 0}, {-1, 1, 0}, {-1, -1, -1}, {-1, -1, 1}, {-1, 1, -1}, {-1, 1, 1}};
+
+// p[i] = 1 + parent of i.  SCOPE: workgroup for LDS, agent for global memory (loads that other CUs' atomics are visible to)
+template <int SCOPE>
+__device__ __forceinline__ int cc_find(int* p, int i) {
+    for (;;) {
+        const int q = __hip_atomic_load(p + i, __ATOMIC_RELAXED, SCOPE) - 1;
+        if (q == i) return i;
+        i = q;          // q < i: the chain ends
+    }
+}
+
+template <int SCOPE>
+__device__ __forceinline__ void cc_union(int* p, int a, int b) {
+    for (;;) {
+        a = cc_find<SCOPE>(p, a);
+        b = cc_find<SCOPE>(p, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = __hip_atomic_fetch_min(p + a, b + 1, __ATOMIC_RELAXED, SCOPE) - 1;          // hang a below b
+        if (old == a) return;
+        a = old;          // a was no root any more and now points to min(old, b): join its former parent old < a with b as well
+    }
+}
+
+// bit g of member[]: grey value g is one of `values`
+__device__ __forceinline__ void cc_member_init(unsigned* member, const int* __restrict__ values, int K) {
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < 8; ++i) member[i] = 0u;
+        for (int k = 0; k < K; ++k) {
+            const int v = values[k];
+            if (v >= 0 && v <= 255) member[v >> 5] |= 1u << (v & 31);
+        }
+    }
+}
+
+// grid = number of tiles (x fastest), block PO_BLOCK: thread t owns the voxels (lz, t >> 5, t & 31), lz < 4
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_local_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int K,
+                                                               int* __restrict__ comp, int S, int H, int W, int ntx, int nty, int nnb) {
+    __shared__ unsigned member[8];
+    __shared__ int grey[CC_TILE];          // the grey value of an organ voxel, -1 for everything else and outside the volume
+    __shared__ int par[CC_TILE];
+    cc_member_init(member, values, K);
+    __syncthreads();
+    int tile = blockIdx.x;
+    const int x0 = (tile % ntx) * CC_TX;
+    tile /= ntx;
+    const int y0 = (tile % nty) * CC_TY, z0 = (tile / nty) * CC_TZ;
+    const int lx = threadIdx.x & (CC_TX - 1), ly = threadIdx.x >> 5;
+    const int x = x0 + lx, y = y0 + ly;
+    const long plane = (long)H * W;
+#pragma unroll
+    for (int lz = 0; lz < CC_TZ; ++lz) {
+        int v = -1;
+        if (x < W && y < H && z0 + lz < S) {
+            v = lab[(long)(z0 + lz) * plane + (long)y * W + x];
+            if (!((member[v >> 5] >> (v & 31)) & 1u)) v = -1;
+        }
+        grey[lz * PO_BLOCK + threadIdx.x] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lz = 0; lz < CC_TZ; ++lz) {          // the row neighbour is linked without an atomic
+        const int l = lz * PO_BLOCK + threadIdx.x, v = grey[l];
+        par[l] = v < 0 ? 0 : ((lx > 0 && grey[l - 1] == v) ? l : l + 1);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lz = 0; lz < CC_TZ; ++lz) {          // shorten the row chains (a racing reader sees the old or the new parent: both valid)
+        const int l = lz * PO_BLOCK + threadIdx.x;
+        if (grey[l] >= 0) par[l] = cc_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l) + 1;
+    }
+    __syncthreads();
+    for (int lz = 0; lz < CC_TZ; ++lz) {
+        const int l = lz * PO_BLOCK + threadIdx.x, v = grey[l];
+        if (v < 0) continue;
+        for (int i = 1; i < nnb; ++i) {
+            const int nz = lz + cc_off[i][0], ny = ly + cc_off[i][1], nx = lx + cc_off[i][2];
+            if (nz < 0 || ny < 0 || ny >= CC_TY || nx < 0 || nx >= CC_TX) continue;
+            const int m = (nz * CC_TY + ny) * CC_TX + nx;
+            if (grey[m] == v) cc_union<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l, m);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int lz = 0; lz < CC_TZ; ++lz) {
+        if (!(x < W && y < H && z0 + lz < S)) continue;
+        const int l = lz * PO_BLOCK + threadIdx.x;
+        int c = 0;
+        if (grey[l] >= 0) {          // local order = global order inside a tile, so the local root is the tile's smallest index too
+            const int r = cc_find<__HIP_MEMORY_SCOPE_WORKGROUP>(par, l);
+            c = 1 + (int)((long)(z0 + r / (CC_TY * CC_TX)) * plane + (long)(y0 + (r / CC_TX) % CC_TY) * W + x0 + r % CC_TX);
+        }
+        comp[(long)(z0 + lz) * plane + (long)y * W + x] = c;
+    }
+}
+
+// grid-stride over the voxels: unions across tile faces
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_merge_kernel(const unsigned char* __restrict__ lab, int* comp, int S, int H, int W, int nnb) {
+    const long plane = (long)H * W, n = plane * S;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int z = (int)(e / plane);
+        const int r = (int)(e - (long)z * plane);
+        const int y = r / W, x = r - y * W;
+        const int lx = x & (CC_TX - 1), ly = y & (CC_TY - 1);
+        if (lx != 0 && lx != CC_TX - 1 && ly != 0 && ly != CC_TY - 1 && (z & (CC_TZ - 1)) != 0) continue;          // inside its tile
+        if (comp[e] == 0) continue;          // no organ's voxel (comp[e] only changes between non-zero values)
+        const int v = lab[e];
+        for (int i = 0; i < nnb; ++i) {
+            const int nz = z + cc_off[i][0], ny = y + cc_off[i][1], nx = x + cc_off[i][2];
+            if (nz < 0 || ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
+            if (nz / CC_TZ == z / CC_TZ && ny / CC_TY == y / CC_TY && nx / CC_TX == x / CC_TX) continue;          // po_cc_local_kernel's
+            const long m = (long)nz * plane + (long)ny * W + nx;
+            if (lab[m] == v) cc_union<__HIP_MEMORY_SCOPE_AGENT>(comp, (int)e, (int)m);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_flatten_kernel(int* comp, long n) {
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK)
+        if (comp[e]) comp[e] = cc_find<__HIP_MEMORY_SCOPE_AGENT>(comp, (int)e) + 1;          // a racing reader: old or new parent, both valid
+}
+
+// size[root] += voxels of the component.  Lanes of a wave that hold the same root add once (one atomic per wave inside a large body)
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_size_kernel(const int* __restrict__ comp, int* __restrict__ size, long n) {
+    const int lane = threadIdx.x & 63;
+    for (long e0 = (long)blockIdx.x * PO_BLOCK + (threadIdx.x - lane); e0 < n; e0 += (long)gridDim.x * PO_BLOCK) {          // wave-uniform
+        const long e = e0 + lane;
+        const int c = e < n ? comp[e] : 0;
+        unsigned long long todo = __ballot(c != 0);
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const int r = __shfl(c, leader, 64);
+            const unsigned long long same = __ballot(c == r);
+            if (lane == leader) atomicAdd(size + (r - 1), __popcll(same));
+            todo &= ~same;
+        }
+    }
+}
+
+// lut[g] = the lowest k with values[k] == g, or -1
+__device__ __forceinline__ void cc_lut_init(int* lut, const int* __restrict__ values, int K) {
+    lut[threadIdx.x] = -1;          // PO_BLOCK == 256 entries
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = K - 1; k >= 0; --k) {
+            const int v = values[k];
+            if (v >= 0 && v <= 255) lut[v] = k;
+        }
+    __syncthreads();
+}
+
+// per root: stats[k] += (1, size, .), keys[k] = max over (size << 32) | (0xffffffff - root): the largest, of equals the smallest root
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_winner_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int K,
+                                                                const int* __restrict__ comp, const int* __restrict__ size,
+                                                                unsigned long long* __restrict__ keys, int* __restrict__ stats, long n) {
+    __shared__ int lut[256];
+    cc_lut_init(lut, values, K);
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        if (comp[e] != (int)e + 1) continue;
+        const int k = lut[lab[e]], sz = size[e];
+        atomicAdd(stats + 3 * k, 1);
+        atomicAdd(stats + 3 * k + 1, sz);
+        atomicMax(keys + k, ((unsigned long long)(unsigned)sz << 32) | (unsigned long long)(0xffffffffu - (unsigned)e));
+    }
+}
+
+// out = label, but 0 on organ voxels outside their organ's winner; stats[k][2] = the winner's size
+__global__ void __launch_bounds__(PO_BLOCK) po_cc_keep_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int K,
+                                                              const int* __restrict__ comp, const unsigned long long* __restrict__ keys,
+                                                              unsigned char* __restrict__ out, int* __restrict__ stats, long n) {
+    __shared__ int lut[256];
+    __shared__ int win[PO_MAXVALUES];          // comp of the winner's voxels, 0 for an organ without voxels
+    cc_lut_init(lut, values, K);
+    if (threadIdx.x < K) {
+        const unsigned long long key = keys[threadIdx.x];
+        win[threadIdx.x] = key ? (int)(0xffffffffu - (unsigned)(key & 0xffffffffull)) + 1 : 0;
+        if (blockIdx.x == 0) stats[3 * threadIdx.x + 2] = (int)(key >> 32);
+    }
+    __syncthreads();
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int c = comp[e], g = lab[e];
+        out[e] = (unsigned char)((c == 0 || c == win[lut[g]]) ? g : 0);
+    }
+}
+
+static bool po_cc_args_ok(int S, int H, int W, int K, int connectivity) {
+    return po_volume_ok(S, H, W) && K >= 1 && K <= PO_MAXVALUES && (connectivity == 6 || connectivity == 26);
+}
+
+static unsigned po_cc_blocks(long n) {
+    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
+    return (unsigned)(b < 4 * PO_SURF_MAXBLK ? b : 4 * PO_SURF_MAXBLK);
+}
+
+static int po_components(const unsigned char* label, const int* values, int* comp, int S, int H, int W, int K, int connectivity,
+                         hipStream_t st) {
+    const long n = (long)S * H * W;
+    const int ntx = (W + CC_TX - 1) / CC_TX, nty = (H + CC_TY - 1) / CC_TY, ntz = (S + CC_TZ - 1) / CC_TZ;
+    const int nnb = connectivity == 26 ? 13 : 3;
+    hipLaunchKernelGGL(po_cc_local_kernel, dim3((unsigned)((long)ntx * nty * ntz)), dim3(PO_BLOCK), 0, st, label, values, K, comp, S, H, W,
+                       ntx, nty, nnb);
+    hipLaunchKernelGGL(po_cc_merge_kernel, dim3(po_cc_blocks(n)), dim3(PO_BLOCK), 0, st, label, comp, S, H, W, nnb);
+    hipLaunchKernelGGL(po_cc_flatten_kernel, dim3(po_cc_blocks(n)), dim3(PO_BLOCK), 0, st, comp, n);
+    return MMSEG_CHECK_LAUNCH();
+}
+
 extern "C" {
 
 // prob [S,OH,OW,C] fp32, values [K] int32 (device, grey values 0..255), out [S,H,W] uint8: every byte is written
@@ -567,6 +801,46 @@ int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth,
         hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
         hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 6 * k);
     }
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// label [S,H,W] uint8, values [K] int32 (device) -> comp [S,H,W] int32, every element written: 0 where the grey value is none of
+// `values`, else 1 + the smallest linear index of the voxel's component (same grey value, joined through 6 or 26 neighbours)
+int mmseg_label_components(const unsigned char* label, const int* values, int* comp, int S, int H, int W, int K, int connectivity,
+                           void* stream) {
+    if (S <= 0) return 0;
+    if (!label || !values || !comp || !po_cc_args_ok(S, H, W, K, connectivity)) return (int)hipErrorInvalidValue;
+    return po_components(label, values, comp, S, H, W, K, connectivity, (hipStream_t)stream);
+}
+
+// bytes of workspace of mmseg_keep_largest_components: the K <= 16 winner keys, then the sizes and the components of the n voxels
+long mmseg_keep_largest_workspace_bytes(int S, int H, int W, int K) {
+    if (S <= 0 || !po_cc_args_ok(S, H, W, K, 6)) return 0;
+    return (long)sizeof(unsigned long long) * PO_MAXVALUES + 2 * (long)sizeof(int) * S * H * W;
+}
+
+// out [S,H,W] uint8 = label with every organ voxel outside its organ's largest component set to 0; stats [K,3] int32 = (components,
+// voxels before, voxels kept).  ws: mmseg_keep_largest_workspace_bytes(S, H, W, K) bytes, 8-byte aligned
+int mmseg_keep_largest_components(const unsigned char* label, const int* values, unsigned char* out, int* stats, int* ws, int S, int H,
+                                  int W, int K, int connectivity, void* stream) {
+    if (S <= 0) return 0;
+    if (!label || !values || !out || !stats || !ws || !po_cc_args_ok(S, H, W, K, connectivity))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)S * H * W;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(ws);
+    int* size = reinterpret_cast<int*>(keys + PO_MAXVALUES);
+    int* comp = size + n;
+    hipError_t rc = hipMemsetAsync(ws, 0, sizeof(unsigned long long) * PO_MAXVALUES + sizeof(int) * (size_t)n, st);          // keys and sizes
+    if (rc != hipSuccess) return (int)rc;
+    rc = hipMemsetAsync(stats, 0, sizeof(int) * 3 * (size_t)K, st);
+    if (rc != hipSuccess) return (int)rc;
+    const int err = po_components(label, values, comp, S, H, W, K, connectivity, st);
+    if (err) return err;
+    const dim3 grid(po_cc_blocks(n)), block(PO_BLOCK);
+    hipLaunchKernelGGL(po_cc_size_kernel, grid, block, 0, st, comp, size, n);
+    hipLaunchKernelGGL(po_cc_winner_kernel, grid, block, 0, st, label, values, K, comp, size, keys, stats, n);
+    hipLaunchKernelGGL(po_cc_keep_kernel, grid, block, 0, st, label, values, K, comp, keys, out, stats, n);
     return MMSEG_CHECK_LAUNCH();
 }
 

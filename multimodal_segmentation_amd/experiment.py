@@ -4,7 +4,7 @@
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
-                         [--predict_surface true|false]
+                         [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
@@ -56,6 +56,10 @@ def parse_arguments(argv=None):
     ap.add_argument('--predict_order', type=int, choices=[0, 1], default=1, help='resampling back to the raw grid: nearest / bilinear')
     ap.add_argument('--predict_surface', type=true_or_false, default=True, metavar='true|false',
                     help='also score labelled files that carry slice_spacing in mm (RAVD, ASSD, MSSD: results_surface_<modality>.csv)')
+    ap.add_argument('--predict_components', choices=['none', 'largest'], default='none',
+                    help="largest: keep each organ's largest 3-D connected component in the predicted label volumes")
+    ap.add_argument('--predict_connectivity', type=int, choices=[6, 26], default=6,
+                    help='neighbours of --predict_components: faces / faces, edges and corners')
     return ap.parse_args(argv)
 
 
@@ -203,7 +207,9 @@ class Experiment(object):
             model = resolve('models', conf.model)(conf)
             model.build()
             VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
-                                              surface=getattr(args, 'predict_surface', True))
+                                              surface=getattr(args, 'predict_surface', True),
+                                              components={'largest': 'largest'}.get(getattr(args, 'predict_components', 'none')),
+                                              connectivity=getattr(args, 'predict_connectivity', 6))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 

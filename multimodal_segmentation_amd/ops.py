@@ -1690,6 +1690,49 @@ def surface_metrics(pred, truth, values, spacing):
     return table
 
 
+def _ws_i32(tag, nbytes, device):
+    """_ws_f64 for the int32 scratch of the component filter (grow-only, per tag, device and stream)"""
+    key = (tag, device, _sid(device))
+    buf = _workspaces.get(key)
+    n = max((int(nbytes) + 3) // 4, 1)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(n, dtype=torch.int32, device=device)
+        _workspaces[key] = buf
+    return buf
+
+
+def _component_args(op, label, values, connectivity):
+    if connectivity not in (6, 26):
+        raise ValueError('%s: connectivity must be 6 (faces) or 26 (faces, edges, corners), got %r' % (op, connectivity))
+    return _volume_args(op, label, values)
+
+
+def label_components(label, values, connectivity=6):
+    """label [S,H,W] uint8 grey values on the device, values [K] int32 -> int32 [S,H,W]: 0 where the grey value is none of `values`,
+    else 1 + the smallest linear index of the voxel's connected component (csrc/postprocess.hip).  Two voxels are joined when they
+    hold the same grey value and are neighbours: connectivity 6 (faces) or 26 (faces, edges, corners)."""
+    K = _component_args('label_components', label, values, connectivity)
+    S, H, W = label.shape
+    comp = _new((S, H, W), label, torch.int32)
+    if S:
+        N.call('mmseg_label_components', _c(label), values, comp, S, H, W, K, int(connectivity))
+    return comp
+
+
+def keep_largest_components(label, values, connectivity=6):
+    """label [S,H,W] uint8 on the device, values [K] int32 -> (uint8 [S,H,W], int32 [K,3]): the volume with every organ voxel outside
+    its organ's largest connected component set to 0 (of equally large ones the component with the smallest linear index stays;
+    other grey values are copied), and per organ (number of components, voxels before, voxels kept) (csrc/postprocess.hip)"""
+    K = _component_args('keep_largest_components', label, values, connectivity)
+    S, H, W = label.shape
+    out = _new((S, H, W), label, torch.uint8)
+    stats = torch.zeros((K, 3), dtype=torch.int32, device=label.device)
+    if S:
+        ws = _ws_i32('keep_largest', N.call('mmseg_keep_largest_workspace_bytes', S, H, W, K), label.device)
+        N.call('mmseg_keep_largest_components', _c(label), values, out, stats, ws, S, H, W, K, int(connectivity))
+    return out, stats
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

@@ -14,6 +14,12 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
                                            model_tester.write_results, one row per labelled volume
     <out>/results_surface_<modality>.csv   where they also carry `slice_spacing`: RAVD (%), ASSD and MSSD (mm) of the union of the
                                            organs and of every organ, one row per scored volume
+    <out>/results_components_<modality>.csv   with components='largest': per organ the number of connected components, its voxels
+                                           before the filter and the voxels kept, one row per volume
+
+components='largest' (build-defined, off by default; the rule is in INTEGRATION.md section 5) keeps, per organ, the largest 3-D connected
+component: the prediction is scattered to the file grid [S_file,H,W] on the device and filtered there (ops.keep_largest_components),
+so that neighbours across slices are those of the file; the filtered volume is what is scored and written.
 
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
 from the counts summed over the organs, then the mean over the selected slices.
@@ -85,6 +91,36 @@ def score_volume(pred, label, values, geometry, surface=True):
     return joint, per_organ, chaos_from_table(nn.to_numpy(table))
 
 
+COMPONENTS = (None, 'largest')
+
+
+def check_components(components, connectivity):
+    if components not in COMPONENTS:
+        raise ValueError("components must be None or 'largest', got %r" % (components,))
+    if connectivity not in (6, 26):
+        raise ValueError('connectivity must be 6 (faces) or 26 (faces, edges, corners), got %r' % (connectivity,))
+
+
+def keep_largest(pred, values, geometry, connectivity=6):
+    """pred: uint8 [S,H,W] on the device, the selected slices of one file in order -> (the same slices after the filter, stats [K,3]
+    on the device).  The filter runs on the file grid [S_file,H,W] (unselected slices are zero), so that two voxels are neighbours
+    along the slice axis when they are in the file."""
+    where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=pred.device)
+    grid = tuple(int(n) for n in geometry['raw_shape'])
+    on_grid = torch.zeros(grid, dtype=torch.uint8, device=pred.device).index_copy_(0, where, pred)
+    kept, stats = ops.keep_largest_components(on_grid, values, connectivity)
+    return kept.index_select(0, where), stats
+
+
+def write_component_results(path, rows, num_masks):
+    """rows: (volume, stats [K,3]) -> Vol, N0, Before0, Kept0, N1, ..."""
+    cols = ['Vol'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('N', 'Before', 'Kept')]
+    with open(path, 'w') as f:
+        f.write(', '.join(cols) + '\n')
+        for vol, stats in rows:
+            f.write(', '.join([str(vol)] + ['%d' % v for v in np.asarray(stats).reshape(-1)]) + '\n')
+
+
 def write_surface_results(path, rows, num_masks):
     """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
     cols = ['Vol', 'RAVD', 'ASSD', 'MSSD'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('RAVD', 'ASSD', 'MSSD')]
@@ -115,10 +151,12 @@ def collect_scores(rows, surface_rows, m, volume, modality, scores, geometry, su
         log.info("volume %s, %s: %s holds no 'slice_spacing', so no scores in mm" % (volume, modality, geometry['file']))
 
 
-def score_folder(pred_folder, data_folder, out_folder=None, surface=True):
+def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6):
     """Score label volumes written earlier (by VolumePredictor.run or by another program: <file name of the input>.npz with `label`
     [S_file,H,W] uint8) against the labelled files of `data_folder`; writes the CSV files of VolumePredictor.run into out_folder
-    (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json."""
+    (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json.
+    components='largest' filters every volume first (keep_largest): the scores that post-processing would give."""
+    check_components(components, connectivity)
     loader = VolumeFolderLoader(data_folder)
     out_folder = out_folder or pred_folder
     os.makedirs(out_folder, exist_ok=True)
@@ -147,8 +185,10 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True):
                                  % (path, label.shape, entry['file'], pred.shape, pred.dtype))
             selected = np.arange(label.shape[0]) if selected is None else selected
             geo = dict(file=entry['file'], raw_shape=label.shape, slices=[int(i) for i in selected], resolution=res, slice_spacing=spacing)
-            scores = score_volume(nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8),
-                                  nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface)
+            pred = nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8)
+            if components:
+                pred, _ = keep_largest(pred, values, geo, connectivity)
+            scores = score_volume(pred, nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface)
             collect_scores(rows, surface_rows, m, v, mod, scores, geo, surface)
     write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
     return ({name: rows[m] for m, name in enumerate(loader.modalities)},
@@ -167,7 +207,8 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
-    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True):
+    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6):
+        check_components(components, connectivity)
         if mode not in FUSION_MODES:
             raise ValueError('Unknown mode: %r (expected one of %s)' % (mode, ', '.join(FUSION_MODES)))
         if order not in (0, 1):
@@ -188,12 +229,16 @@ class VolumePredictor(object):
         device = nn.default_device()
         values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
         rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
+        component_rows = [[] for _ in loader.modalities]
         files = {}
         for v in volumes:
             images, geometry = loader.load_volume_for_prediction(v)
             for m, geo in enumerate(geometry):
                 prob = self.predict_volume(m, mode, images)
                 pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
+                if components:
+                    pred, stats = keep_largest(pred, values, geo, connectivity)
+                    component_rows[m].append((v, nn.to_numpy(stats)))
                 if geo['label'] is not None:
                     scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface)
                     collect_scores(rows, surface_rows, m, v, loader.modalities[m], scores, geo, surface)
@@ -203,7 +248,13 @@ class VolumePredictor(object):
                 np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
                 files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
         write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
+        for m, name in enumerate(loader.modalities):
+            if component_rows[m]:
+                write_component_results(os.path.join(out_folder, 'results_components_%s.csv' % name), component_rows[m], loader.num_masks)
+        settings = dict(source_folder=folder, mode=mode, order=order, model_folder=self.conf.get('folder'),
+                        label_values=loader.label_values, files=files)
+        if components:
+            settings.update(components=components, connectivity=connectivity)
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
-            json.dump(dict(source_folder=folder, mode=mode, order=order, model_folder=self.conf.get('folder'),
-                           label_values=loader.label_values, files=files), f, indent=1)
+            json.dump(settings, f, indent=1)
         return {name: rows[m] for m, name in enumerate(loader.modalities)}

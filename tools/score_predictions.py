@@ -7,7 +7,11 @@ that carry `slice_spacing`, RAVD, ASSD and MSSD in mm (results_surface_<modality
 PRED_FOLDER holds one `<file name of the input>.npz` with `label` [S_file,H,W] uint8 per scored file; files that are missing there, or
 that carry no label in DATA_FOLDER, are left out.
 
-    python tools/score_predictions.py PRED_FOLDER DATA_FOLDER [--out OUT] [--surface true|false]
+`--components largest` keeps each organ's largest 3-D connected component in every volume read from PRED_FOLDER before it is scored
+(`--connectivity 6|26`): the scores that `--predict_components largest` would have given, for volumes written without it.
+
+    python tools/score_predictions.py PRED_FOLDER DATA_FOLDER [--out OUT] [--surface true|false] [--components largest]
+                                      [--connectivity 6|26]
 """
 import argparse
 import logging
@@ -26,9 +30,11 @@ def main(argv=None):
     ap.add_argument('data_folder')
     ap.add_argument('--out', help='where to write the CSV files (default: PRED_FOLDER)')
     ap.add_argument('--surface', type=true_or_false, default=True, metavar='true|false', help='also the scores in mm')
+    ap.add_argument('--components', choices=['largest'], help="filter the predicted volumes first: each organ's largest component")
+    ap.add_argument('--connectivity', type=int, choices=[6, 26], default=6, help='neighbours of --components')
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
-    rows, surface_rows = score_folder(a.pred_folder, a.data_folder, a.out, a.surface)
+    rows, surface_rows = score_folder(a.pred_folder, a.data_folder, a.out, a.surface, a.components, a.connectivity)
     for name in rows:
         print('%s: %d volumes scored, %d of them in mm' % (name, len(rows[name]), len(surface_rows[name])))
 
