@@ -581,6 +581,8 @@ def segloss_class_offset(B):
 
 
 def segloss_stats(pred, target, stats, ws, B, HW, C, nm):
+    if C > 8 or nm > C or B * 3 > 1024:          # the library's own argument check (csrc/loss.hip)
+        return 1
     p, t = pred.reshape(B, HW, C), target.reshape(B, HW, C)
     st = torch.zeros(3 * B + 16, dtype=pred.dtype)
     st[0:3 * B:3] = (t[..., :nm] * p[..., :nm]).sum((1, 2))
@@ -619,6 +621,11 @@ def segloss_grad(pred, target, coef, dpred, B, HW, C, nm, scale, use_bce):
     dpred.copy_((g * scale).reshape(dpred.shape)); return 0
 
 
+def segloss_grad_s(pred, target, coef, dpred, B, HW, C, nm, scale, scale_dev, use_bce):
+    s = float(torch.tensor(scale, dtype=torch.float32) * scale_dev[0])
+    return segloss_grad(pred, target, coef, dpred, B, HW, C, nm, s, use_bce)
+
+
 def diffloss_workspace_floats():
     return 1
 
@@ -633,6 +640,11 @@ def diffloss_grad(p, t, tconst, n, mode, scale, dp):
     d = p - (t if t is not None else tconst)
     g = torch.sign(d) if mode == 0 else (2 * d if mode == 1 else torch.ones_like(d))
     dp.copy_(g * scale); return 0
+
+
+def diffloss_grad_s(p, t, tconst, n, mode, scale, scale_dev, dp):
+    s = float(torch.tensor(scale, dtype=torch.float32) * scale_dev[0])
+    return diffloss_grad(p, t, tconst, n, mode, s, dp)
 
 
 def adam(p, g, m, v, n, lr_t, b1, b2, eps):
@@ -727,6 +739,8 @@ def _label_nll(t):
 
 
 def segpb_stats(pred, target, stats, ws, B, HW, C, nm):
+    if C > 8 or nm > C or B <= 0 or B * 11 > 1024:      # the library's own argument check (csrc/pairloss.hip)
+        return 1
     p, t = pred.reshape(B, HW, C), target.reshape(B, HW, C)
     st = torch.zeros(B, 11)
     st[:, 0] = (t[..., :nm] * p[..., :nm]).sum((1, 2))
@@ -805,7 +819,22 @@ def _call(name, *args):
     if fn is None:
         raise KeyError('cpu_backend has no stand-in for %s' % name)
     with torch.no_grad():
-        return fn(*args)
+        rc = fn(*args)
+    if rc != 0 and _takes_stream(name):          # like _native.call: a launch entry point that rejects its arguments raises
+        from multimodal_segmentation_amd import _native
+        raise _native.NativeLibraryError('%s failed with hipError_t %d' % (name, rc))
+    return rc
+
+
+_protos = {}
+
+
+def _takes_stream(name):
+    if not _protos:
+        from multimodal_segmentation_amd import _native
+        _protos.update(_native.parse_header())
+    types = _protos.get(name, (None, []))[1]
+    return bool(types) and types[-1] == 'void*'
 
 
 _saved = {}

@@ -758,3 +758,346 @@ def test_training_iterations_with_batched_weight_images_are_bitwise_the_lazy_one
     assert na > 20                                   # the images were registered (and refreshed in batches)
     assert len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
 
+
+
+# ======================================================================================================================
+# The two-stage reductions and the element-wise kernels where their loops wrap.
+#
+# Launch geometry (csrc/loss.hip, pairloss.hip, norm.hip, pointwise.hip, optim.hip): a fixed number of chunks per sample (64 for
+# InstanceNorm, 128 for the losses and FiLM), 256 threads per chunk; grid-stride loops capped at 1024 (diff_loss partials), 4096
+# (loss gradients, BatchNorm apply, Adam) blocks; a tiny final kernel over the partials.  Every case below is the smallest shape that
+# crosses one of those boundaries; the comment beside it gives the arithmetic.  Values and every gradient are compared with the fp64
+# oracle on the same seeded fp32 inputs.
+#
+# Tolerances: those of the neighbouring test of the same op (RTOL 2e-4 of the tensor's largest magnitude, 5e-4 for the norms,
+# 1e-5 / 1e-4 for loss values / loss gradients, 1e-6 for Adam).
+#   case                          | tolerance | differs from the neighbour
+#   ------------------------------+-----------+---------------------------
+#   (none)                        |           | no case needed another tolerance
+# ======================================================================================================================
+def _native_error():
+    from multimodal_segmentation_amd import _native as N
+    return N.NativeLibraryError
+
+
+# B, H, W, C, nm
+SEG_LOSS_EDGES = [
+    # HW = 36863: per = ceil(36863 / 128) = 288 > 256 -> threads 0..31 of segloss_partial_kernel make a second trip; the last chunk
+    # holds 36863 - 127 * 288 = 287 pixels; n = 6 * 36863 * 5 = 1 105 890 > 4096 * 256 = 1 048 576 -> the gradient grid wraps
+    pytest.param(6, 193, 191, 5, 4, id='HW36863-second-trip-grad-wrap'),
+    pytest.param(2, 9, 11, 5, 4, id='HW99-29-empty-chunks'),          # HW = 99 < 128: per = 1, chunks 99..127 are empty
+    pytest.param(2, 10, 13, 5, 4, id='HW130-chunks-past-end'),       # HW = 130: per = 2, chunks 65..127 start at >= 130, past the end
+    pytest.param(17, 8, 8, 5, 4, id='B17-nout67-second-round'),      # nout = 3 * 17 + 16 = 67 > 64: second round of segloss_stats_final_kernel
+    pytest.param(22, 8, 8, 5, 4, id='B22-nout82-second-round'),      # nout = 82: per-sample sums AND class sums in the second round
+    pytest.param(2, 16, 16, 8, 7, id='C8-SEG_MAXC'),                 # C = SEG_MAXC = 8
+    pytest.param(2, 16, 16, 2, 1, id='C2-smallest'),                 # the smallest C
+]
+
+
+@pytest.mark.parametrize('variant', ['bce', 'dice', 'bce-scale_dev'])
+@pytest.mark.parametrize('B,H,W,C,nm', SEG_LOSS_EDGES)
+def test_seg_loss_boundaries(B, H, W, C, nm, variant, device):
+    """ops.seg_loss (segloss_partial / stats_final / finalize / grad[_s] kernels) == costs.py's loss and its gradient in fp64"""
+    lam = 0.0 if variant == 'dice' else 0.01
+    t = _masks(B, H, W, nm, 32)
+    assert t.shape[-1] == C
+    pred = torch.softmax(rnd(B, H, W, C, seed=33), -1)
+    pr = pred.clone().double().requires_grad_(True)
+    ref = O.combined_dice_bce(t.double(), pr, nm) if lam else O.dice_loss(t.double(), pr, nm)
+    sd = 4.0 if variant == 'bce-scale_dev' else None                   # the dynamic loss scale: a power of two on the device
+    (gref,) = torch.autograd.grad(ref * 10.0 * (sd or 1.0), pr)
+    loss, dp = P.seg_loss(pred.to(device), t.to(device), nm, lam, 10.0,
+                          scale_dev=None if sd is None else torch.tensor([sd]).to(device))
+    _close(loss, ref.reshape(1), 'loss', 1e-5)
+    _close(dp, gref, 'dpred', 1e-4)
+
+
+@pytest.mark.parametrize('B,C,nm', [pytest.param(1, 9, 8, id='C9-above-SEG_MAXC'), pytest.param(342, 5, 4, id='B342-3B-above-1024')])
+def test_seg_loss_rejects_what_its_kernels_cannot_hold(B, C, nm, device):
+    """C > SEG_MAXC (register arrays of 8 channels) and 3 * B > 1024 are refused by mmseg_segloss_stats before any launch"""
+    t = _masks(B, 2, 2, C - 1, 1)
+    pred = torch.softmax(rnd(B, 2, 2, C, seed=2), -1)
+    with pytest.raises(_native_error()):
+        P.seg_loss(pred.to(device), t.to(device), nm, 0.01, 1.0)
+
+
+def _with_ties(p, t):
+    """a block of exact ties: |p - t| has gradient 0 there (keras / TF: sign(0) = 0)"""
+    p = p.clone()
+    k = max(1, p.numel() // 3)
+    p.view(-1)[:k] = t.view(-1)[:k]
+    return p
+
+
+# n = 3, 257: less than / just over one block.  66 049 = 257^2: lgrid = 259 blocks > 256, diffloss_final_kernel walks its partials twice.
+# 263 169 = 513^2 > 1024 * 256 = 262 144: the partial grid wraps.  1 050 625 = 1025^2 > 4096 * 256 = 1 048 576: the gradient grid wraps.
+DIFF_LOSS_N = [3, 257, 66049, 263169, 1050625]
+
+
+@pytest.mark.parametrize('mode', ['mae', 'mse', 'mean', 'mae-const', 'mse-const', 'mse-scale_dev'])
+@pytest.mark.parametrize('n', DIFF_LOSS_N)
+def test_diff_loss_boundaries(n, mode, device):
+    """ops.diff_loss (diffloss_partial / final / grad[_s] kernels): tensor and constant targets, exact ties in the 'mae' cases"""
+    mode, _, form = mode.partition('-')
+    p, t = rnd(n, seed=34), rnd(n, seed=35)
+    if form == 'const':
+        t = torch.full((n,), 0.25)
+        if mode == 'mae':
+            p = _with_ties(p, t)
+    elif mode == 'mae':
+        p = _with_ties(p, t)
+    pr = p.clone().double().requires_grad_(True)
+    ref = {'mae': O.mae(t.double(), pr), 'mse': O.mse(t.double(), pr), 'mean': pr.mean()}[mode]
+    sd = 8.0 if form == 'scale_dev' else None
+    (gref,) = torch.autograd.grad(ref * 0.5 * (sd or 1.0), pr)
+    loss, dp = P.diff_loss(p.to(device), 0.25 if form == 'const' else t.to(device), mode, 0.5,
+                           scale_dev=None if sd is None else torch.tensor([sd]).to(device))
+    _close(loss, ref.reshape(1), 'loss', 1e-5)
+    _close(dp, gref, 'grad', 1e-5)
+    if mode == 'mae':
+        k = max(1, n // 3)
+        assert torch.count_nonzero(dp.reshape(-1)[:k]) == 0, 'a tie has gradient 0'
+
+
+@pytest.mark.parametrize('B,H,W,C,J', [
+    # per_sample = 183 * 181 * 4 = 132 492 floats = 33 123 float4 > 128 * 256 = 32 768: pair_dice_partial_kernel and pair_dice_bwd_kernel
+    # wrap; the second `other` accumulates into dref (acc_a) on the wrapped elements too
+    pytest.param(2, 183, 181, 4, 2, id='n4-33123-wraps'),
+    pytest.param(3, 1, 1, 4, 2, id='n4-1'),                          # one float4 per sample: 127 of 128 blocks idle
+])
+def test_overlap_dice_boundaries(B, H, W, C, J, device):
+    ref = _anat(B, H, W, C, 1) * 0.9 + 0.05
+    others = [_anat(B, H, W, C, 2 + j) * 0.8 + 0.1 for j in range(J)]
+    check(lambda r, *o: P.overlap_dice(r, list(o)),
+          lambda r, *o: torch.cat([O.pair_dice(r, x) for x in o], dim=1), [ref] + others, device)
+
+
+@pytest.mark.parametrize('B,H,W,ties', [
+    pytest.param(3, 183, 181, False, id='per-sample-33123-wraps'),   # 33 123 > 128 * 256 = 32 768: both row_mae kernels wrap
+    pytest.param(2, 1, 1, False, id='one-pixel'),
+    pytest.param(3, 183, 181, True, id='exact-ties'),                # sign(0) = 0, also on the wrapped elements
+])
+def test_row_mae_boundaries(B, H, W, ties, device):
+    x, y = rnd(B, H, W, 1, seed=5), rnd(B, H, W, 1, seed=6)
+    if ties:
+        y[:, H // 2:] = x[:, H // 2:]
+    check(lambda a, b: P.row_mae(a, b), lambda a, b: O.mae_single_input(a, b).reshape(-1), [x, y], device,
+          grad_mask=[False, True])
+
+
+def _per_sample_inputs(B, H, W, C, nm):
+    t = torch.cat([_anat(B, H, W, nm, 7), torch.zeros(B, H, W, C - nm)], -1)
+    t[..., nm] = 1 - t[..., :nm].sum(-1)
+    t[0, :3] = t[0, :3] * 0.5 + 0.1                      # fractional labels (rotated masks) go through the softmax too
+    return t, torch.softmax(rnd(B, H, W, C, seed=8), -1)
+
+
+@pytest.mark.parametrize('B,H,W,C,nm', [
+    # HW = 36863: per = 288 > 256 -> second trip in segpb_partial_kernel; 36863 > 128 * 256 = 32 768 -> segpb_grad_kernel wraps
+    pytest.param(3, 193, 191, 5, 4, id='HW36863-second-trip-grad-wrap'),
+    pytest.param(2, 9, 11, 5, 4, id='HW99-29-empty-chunks'),          # HW = 99 < 128
+    pytest.param(93, 4, 4, 5, 4, id='B93-1023-threads-live'),         # 11 * 93 = 1023 of the 1024 threads of segpb_stats_final_kernel
+    pytest.param(2, 8, 8, 8, 7, id='C8-PL_MAXC'),
+])
+def test_seg_loss_per_sample_boundaries(B, H, W, C, nm, device):
+    t, p = _per_sample_inputs(B, H, W, C, nm)
+    check(lambda a, b: P.seg_loss_per_sample(a, b, nm), lambda a, b: O.combined_dice_bce_perbatch(a, b, nm), [t, p], device,
+          grad_mask=[False, True])
+
+
+def test_seg_loss_per_sample_rejects_more_samples_than_its_final_block_holds(device):
+    """11 * 94 = 1034 > 1024 threads: mmseg_segpb_stats refuses before any launch"""
+    t, p = _per_sample_inputs(94, 4, 4, 5, 4)
+    with pytest.raises(_native_error()):
+        P.seg_loss_per_sample(t.to(device), p.to(device), 4)
+
+
+@pytest.mark.parametrize('J', [1, 3])
+def test_row_dot_more_than_one_block(J, device):
+    """B = 130 > 2 * 64: three blocks of rowdot_fwd_kernel, the last with 2 live threads; B * J = 390 -> 7 blocks backward"""
+    B = 130
+    w = torch.softmax(rnd(B, J, seed=9), -1) + 0.1
+    ls = [rnd(B, 1, seed=10), rnd(B, seed=11), rnd(B, 1, seed=12)][:J]
+    check(lambda w_, *l: P.row_dot(w_, list(l)),
+          lambda w_, *l: sum(w_[:, j:j + 1] * x.reshape(-1, 1) for j, x in enumerate(l)), [w] + ls, device)
+
+
+def test_sampling_kl_more_than_one_block(device):
+    """B = 130, Z = 7: three 64-thread blocks forward, ceil(910 / 64) = 15 backward, Z not a power of two"""
+    B, Z = 130, 7
+    mu, lv, eps = rnd(B, Z, seed=26), rnd(B, Z, seed=27) * 0.3, rnd(B, Z, seed=28)
+    check(lambda m, l: P.sampling_kl(m, l, eps.to(m.device)), lambda m, l: (O.sampling(m, l, eps.double()), O.kl(m, l)),
+          [mu, lv], device)
+
+
+INSTNORM_EDGES = [
+    pytest.param(2, 36, 36, 16, id='per-sample-20736-second-trip'),  # per = 20736 / 64 = 324 > 256 in in_partial / in_bwd_partial_kernel
+    pytest.param(2, 33, 35, 16, id='per-sample-18480-not-x64'),      # 18480 = 64 * 288.75: per = 289, the last chunk holds 18480 - 63 * 289 = 273
+    pytest.param(3, 1, 1, 4, id='one-float4-per-sample'),            # per = 1: chunks 4..63 are empty
+]
+
+
+@pytest.mark.parametrize('with_mod', [True, False])
+@pytest.mark.parametrize('act_alpha', [0.2, -1.0])
+@pytest.mark.parametrize('B,H,W,C', INSTNORM_EDGES)
+def test_instnorm_spade_boundaries(B, H, W, C, act_alpha, with_mod, device):
+    x = rnd(B, H, W, C, seed=29) * 2 + 1
+    ins = [x] + ([rnd(B, H, W, C, seed=30) * 0.3, rnd(B, H, W, C, seed=31) * 0.3] if with_mod else [])
+
+    def f_ref(x, g=None, b=None):
+        v = O.instance_norm(x)
+        if g is not None:
+            v = O.spade_cond(v, g, b)
+        f_ref.pre = v if act_alpha >= 0 else None
+        return O.leaky_relu(v, act_alpha) if act_alpha >= 0 else v
+
+    check(lambda x, g=None, b=None: P.instnorm_spade(x, g, b, act_alpha), f_ref, ins, device, rtol=5e-4)
+
+
+@pytest.mark.parametrize('act_alpha', [0.2, -1.0])
+def test_instnorm_of_a_constant_sample_is_exactly_zero(act_alpha, device):
+    """a constant sample has variance exactly 0 (sums of x - x[0]): its output is exactly 0 and finite, the rest of the batch is untouched"""
+    x = rnd(3, 33, 35, 16, seed=29) * 2 + 1
+    x[1] = 3.7
+    y = P.instnorm_spade(x.to(device), None, None, act_alpha).cpu()
+    assert torch.isfinite(y).all()
+    if device == 'cuda':       # (the stand-in's plain fp32 mean of 18480 times 3.7 is not 3.7: it only checks the glue)
+        assert torch.count_nonzero(y[1]) == 0
+    v = O.instance_norm(x.double())
+    _close(y, O.leaky_relu(v, act_alpha) if act_alpha >= 0 else v, 'instnorm(const sample)', 5e-4)
+
+
+@pytest.mark.parametrize('act_alpha', [0.2, -1.0])
+@pytest.mark.parametrize('B,H,W,f', [
+    pytest.param(1, 36, 36, 64, id='n4-20736-second-trip'),          # n4 = 36 * 36 * 16 = 20736 > 64 * 256 = 16384: per = 324 > 256
+    pytest.param(2, 33, 35, 20, id='C4-5-real-division'),            # C4 = 5: pix = i / C4 is no shift
+    pytest.param(1, 59, 61, 20, id='C4-5-n4-17995-second-trip'),     # both: n4 = 59 * 61 * 5 = 17995, per = 282 > 256
+])
+def test_instnorm_spade_gb_boundaries(B, H, W, f, act_alpha, device):
+    """ops.instnorm_spade_gb on a gamma|beta tensor given directly (in_apply_gb / in_bwd_partial_gb kernels): output, dx and dgb"""
+    x = rnd(B, H, W, f, seed=2) * 1.5 + 0.3
+    gb = rnd(B, H, W, 2 * f, seed=3) * 0.3
+
+    def f_ref(x, gb):
+        u = O.instance_norm(x) * (1 + gb[..., :f]) + gb[..., f:]
+        f_ref.pre = u if act_alpha >= 0 else None
+        return O.leaky_relu(u, act_alpha) if act_alpha >= 0 else u
+
+    check(lambda x, gb: P.instnorm_spade_gb(x, gb, act_alpha), f_ref, [x, gb], device, rtol=5e-4)
+
+
+def _batchnorm_train_case(x, relu, device):
+    C = x.shape[-1]
+    gamma, beta = rnd(C, seed=6) * 0.2 + 1, rnd(C, seed=7) * 0.2
+    mm0, mv0 = rnd(C, seed=8) * 0.1, torch.rand(C, generator=torch.Generator().manual_seed(9)) + 0.5
+    mm_p, mv_p = mm0.clone().to(device), mv0.clone().to(device)
+    Pd = {}
+
+    def f_prod(x, g, b):
+        return P.batchnorm(x, g, b, mm_p, mv_p, True, relu, ggrad=g.gbuf, bgrad=b.gbuf, anchor=_anchor(x))
+
+    def f_ref(x, g, b):
+        Pd.update({'n/gamma': g, 'n/beta': b, 'n/moving_mean': mm0.double(), 'n/moving_variance': mv0.double()})
+        upd = []
+        y = O.batchnorm(x, Pd, 'n', True, upd)
+        O.apply_bn_updates(Pd, upd)
+        f_ref.pre = y
+        return torch.relu(y) if relu else y
+
+    check(f_prod, f_ref, [x, gamma, beta], device, rtol=5e-4, param_idx=(1, 2))
+    _close(mm_p, Pd['n/moving_mean'], 'moving_mean')
+    _close(mv_p, Pd['n/moving_variance'], 'moving_variance')
+
+
+BN_EDGES = [
+    # generic kernel (C % 64 != 0), never reached at op level before.  M = 3 * 19 * 23 = 1311: norm_blocks = 3 row blocks of exactly
+    # 437 rows (3 * 437 = 1311: the code leaves no short block at this M; M = 1312 below does)
+    pytest.param((3, 19, 23, 20), id='generic-C20-rl12-16-idle-threads'),       # cw = 20, rl = 256 / 20 = 12: threads 240..255 idle
+    pytest.param((3, 19, 23, 8), id='generic-C8-rl32'),
+    pytest.param((3, 19, 23, 300), id='generic-C300-two-column-passes'),        # cw = 256: second pass holds 44 columns
+    pytest.param((2, 16, 41, 20), id='generic-M1312-short-last-block'),         # rows_per_block = 438, the last block holds 436
+    # float4 kernel (C % 64 == 0)
+    pytest.param((3, 19, 23, 64), id='v4-M1311-21-blocks-of-63-last-51'),       # min(512, ceil(1311 / 64)) = 21 blocks of 63 rows, last 51
+    pytest.param((1, 3, 3, 64), id='v4-M9-fewer-rows-than-lanes'),              # 9 rows for 16 row lanes
+    pytest.param((1, 1, 1, 64), id='v4-M1-variance-0'),                         # batch variance exactly 0, dx exactly 0
+    pytest.param((2, 16, 16, 192), id='v4-C192-three-column-blocks'),
+    pytest.param((1, 130, 127, 256), id='v4-n4-1056640-apply-wraps'),           # 16510 * 64 float4 > 4096 * 256 = 1 048 576: bn_apply / bn_bwd_apply wrap
+]
+
+
+@pytest.mark.parametrize('relu', [True, False])
+@pytest.mark.parametrize('shape', BN_EDGES)
+def test_batchnorm_train_boundaries(shape, relu, device):
+    _batchnorm_train_case(rnd(*shape, seed=5) * 2 + 3.0, relu, device)
+
+
+@pytest.mark.parametrize('shape', [(3, 19, 23, 64), (3, 19, 23, 20)], ids=['v4', 'generic'])
+def test_batchnorm_train_large_mean(shape, device):
+    """mean 50, standard deviation 0.5: E[x^2] - E[x]^2 in fp32 would lose the variance; the sums shifted by x[0][c] do not"""
+    _batchnorm_train_case(rnd(*shape, seed=5) * 0.5 + 50.0, True, device)
+
+
+def test_batchnorm_infer_generic_width(device):
+    C = 20
+    x = rnd(2, 7, 9, C, seed=9)
+    g, b, mm, mv = rnd(C, seed=1) + 1, rnd(C, seed=2), rnd(C, seed=3), torch.rand(C, generator=torch.Generator().manual_seed(4)) + 0.5
+    y = P.batchnorm(x.to(device), g.to(device), b.to(device), mm.to(device), mv.to(device), False, True)
+    Pd = {'n/gamma': g, 'n/beta': b, 'n/moving_mean': mm, 'n/moving_variance': mv}
+    _close(y, torch.relu(O.batchnorm(x, Pd, 'n', False)), 'bn_infer')
+
+
+FILM_EDGES = [
+    # film_bwd_v4_kernel: 128 chunks, npl = 256 / C4 pixel lanes -> a second trip when ceil(HW / 128) > npl
+    pytest.param(3, 131, 127, 8, True, False, id='v4-C8-HW16637-second-trip'),      # C4 = 2, npl = 128: per = 130 > 128
+    pytest.param(2, 47, 45, 64, True, False, id='v4-C64-HW2115-second-trip'),       # C4 = 16, npl = 16: per = 17 > 16
+    pytest.param(2, 47, 45, 64, False, False, id='v4-res-None'),
+    # film_fwd_kernel / film_bwd_kernel (C % 4 != 0 or an operand not 16-byte aligned): npl = 256 / C
+    pytest.param(1, 183, 181, 1, True, False, id='generic-C1-HW33123-second-trip'),  # npl = 256: per = 259 > 256
+    pytest.param(2, 131, 127, 2, True, False, id='generic-C2-HW16637-second-trip'),  # npl = 128: per = 130 > 128
+    pytest.param(2, 16, 16, 2, False, False, id='generic-C2-res-None'),
+    pytest.param(2, 47, 45, 64, True, True, id='generic-x-one-float-into-a-buffer'),  # x 4 bytes past a 16-byte boundary: npl = 4, 5 trips
+]
+
+
+@pytest.mark.parametrize('B,H,W,C,with_res,unaligned', FILM_EDGES)
+def test_film_boundaries(B, H, W, C, with_res, unaligned, device):
+    ins = [rnd(B, H, W, C, seed=15), rnd(B, C, seed=16), rnd(B, C, seed=17)] + ([rnd(B, H, W, C, seed=18)] if with_res else [])
+
+    def f_prod(x, g, b, r=None):
+        if unaligned:         # a contiguous view that starts one float into a larger buffer
+            x = torch.cat([x.new_zeros(1), x.reshape(-1)])[1:].view(x.shape)
+            assert x.is_contiguous() and x.data_ptr() % 16 == 4
+        return P.film(x, g, b, r, 0.3)
+
+    def f_ref(x, g, b, r=None):
+        f_ref.pre = O.film(x, g, b)
+        v = O.leaky_relu(f_ref.pre, 0.3)
+        return v + r if r is not None else v
+
+    check(f_prod, f_ref, ins, device)
+
+
+@pytest.mark.parametrize('B,H,W,C', [pytest.param(2, 16, 16, 3, id='C3'),
+                                     pytest.param(3, 193, 191, 5, id='npix-110589-C5')])      # the seg_loss shape above; 432 blocks
+def test_softmax_round_boundaries(B, H, W, C, device):
+    x = rnd(B, H, W, C, seed=11) * 3
+    # rounding is compared exactly: the inputs hold no probability within 1e-6 of the tie at 0.5 (an fp32 softmax over <= 5 channels is
+    # off by a few ulp of 0.5, ~1.5e-7)
+    assert (torch.softmax(x.double(), -1) - 0.5).abs().min() > 1e-6
+    check(lambda x: P.softmax_round(x), lambda x: (torch.softmax(x, -1), O.round_ste(torch.softmax(x, -1))), [x], device)
+
+
+def test_adam_grid_wrap_and_tail(device):
+    """n = 4 * 1 048 576 + 4 * 300 + 3 = 4 195 507: 1 048 876 float4 > 4096 * 256 -> 300 threads make a second trip; 3-element scalar tail"""
+    import math
+    n = 4195507
+    p, g = rnd(n, seed=38), rnd(n, seed=39)
+    Pd = {'p': p.clone().double()}
+    opt = O.KerasAdam(1e-3)
+    pp, m, v = p.clone().to(device), torch.zeros(n, device=device), torch.zeros(n, device=device)
+    for t in range(1, 4):
+        gt = g * t
+        opt.step(Pd, {'p': gt.double()})
+        lr_t = 1e-3 * math.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t)
+        P.adam_step(pp, gt.to(device), m, v, lr_t)
+    _close(pp, Pd['p'], 'adam', 1e-6)
