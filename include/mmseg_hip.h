@@ -430,6 +430,27 @@ long mmseg_surface_metrics_workspace_doubles(int S, int H, int W, int K);
 int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
                           int H, int W, int K, double dz, double dy, double dx, void* stream);
 
+/* ---- order statistics of the surface distances (csrc/postprocess.hip; build-defined: HD(q) and NSD(tau) of INTEGRATION.md section 5) ----
+ * The multiset D = {a[e] : ma[e] != 0} + {b[e] : mb[e] != 0} over a, b [n] fp64 and ma, mb [n] uint8, N = |D|.  By contract every selected
+ * value is finite and >= 0 (such a value orders as its bit pattern, which is what the selection works on); unselected values may be
+ * anything.  The percentile follows numpy's linear rule: h = (N - 1) * (percentile / 100) in fp64 (numpy's order of evaluation), lo = floor(h),
+ * hi = min(lo + 1, N - 1), value = D_(lo) + (h - lo) * (D_(hi) - D_(lo)) over the sorted D.  0 <= n < 2^31, 0 <= percentile <= 100, 0 <= tolerance, both
+ * finite; anything else or a null pointer is refused (hipErrorInvalidValue, nothing is launched).  The selection is an exact radix
+ * selection on the device: no host synchronisation, allocation or copy; integer atomics only, so two runs are bitwise equal. */
+/* doubles of ws for mmseg_masked_select: 2 n for the list of selected values, and the selection's state; 0 for an n it would refuse */
+long mmseg_masked_select_workspace_doubles(long n);
+/* out [5] fp64 = N, |{x in D : x <= tolerance}|, the percentile, D_(lo), D_(hi); the last three nan when N == 0 (n == 0 included) */
+int mmseg_masked_select(const double* a, const unsigned char* ma, const double* b, const unsigned char* mb, long n, double percentile,
+                        double tolerance, double* out, double* ws, void* stream);
+/* doubles of ws for mmseg_surface_scores: mmseg_surface_metrics' 2 S H W (two distance maps) and surfaces, plus 2 S H W for the list of
+ * surface distances: about 420 MB more for a 100 x 512 x 512 CT volume.  0 for arguments that it would refuse. */
+long mmseg_surface_scores_workspace_doubles(int S, int H, int W, int K);
+/* mmseg_surface_metrics with two more columns: table [K+1,8] fp64 = nP, nT, |surface(P)|, |surface(T)|, sum, max (the same kernels, the
+ * same bits), then |{x in D : x <= tolerance}| and the percentile of D = the distances of surface(P) to surface(T) and of surface(T) to
+ * surface(P) together, tolerance in mm; columns 5 to 8 are nan when either surface is empty.  Every distance transform runs once. */
+int mmseg_surface_scores(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
+                         int H, int W, int K, double dz, double dy, double dx, double percentile, double tolerance, void* stream);
+
 /* ---- the largest connected component of every organ (csrc/postprocess.hip; build-defined: these replace nothing in the reference,
  * which writes no segmentation) -------------------------------------------------------------------------------------------------------
  * Two voxels of label [S,H,W] uint8 are joined when they hold the same grey value, that value is one of values [K] (int32, device)

@@ -38,6 +38,16 @@
 //   grid-stride order, a fixed LDS tree per block, partials [blocks][2] = (sum, max), and one block that adds the partials in a fixed
 //   tree: no floating-point atomics.  Only the [K+1,6] table is meant to leave the device.
 //
+// Order statistics of the surface distances (build-defined; HD(q) and NSD(tau) in INTEGRATION.md section 5).
+// mmseg_masked_select: the multiset {a[e] : ma[e] != 0} + {b[e] : mb[e] != 0} of finite fp64 values >= 0 -> out [5] = N, |{x <= tolerance}|,
+//   the percentile by numpy's linear rule, and the two order statistics D_(lo), D_(hi) it is interpolated from.  os_append_kernel
+//   compacts the selected values into a list (one integer atomicAdd per wave on the list's counter), then eight passes of
+//   os_hist_kernel (per-block LDS histograms of one 8-bit digit of the bit patterns, most significant first, one global integer atomic
+//   per non-empty bin) and os_pick_kernel (one block: scan, pick the digit, narrow the prefix) follow both ranks at once.  Exact and,
+//   integer counts being order independent, bitwise reproducible.  Nothing reaches the host: N and the ranks are computed on the device.
+// mmseg_surface_scores: mmseg_surface_metrics' walk with every distance map's surface values appended to the problem's list before
+//   the map is overwritten -> table [K+1,8]: the six columns of mmseg_surface_metrics (same kernels), |{x <= tolerance}|, HD(percentile).
+//
 // The largest connected component of every organ (build-defined; the rule is in INTEGRATION.md section 5).
 // mmseg_label_components: label [S,H,W] -> comp [S,H,W] int32 = 1 + the smallest linear index of the voxel's component, 0 for a voxel
 //   that is no organ's; all K organs in one pass (a union-find in comp itself, see the kernels).
@@ -481,6 +491,191 @@ static int po_surface(const unsigned char* label, const int* values, unsigned ch
 
 static long po_round8(long bytes) { return (bytes + 7) / 8; }
 
+// ---- order statistics of the surface distances -----------------------------------------------------------------------------------------
+// A non-negative finite fp64 orders as its bit pattern read as a 64-bit unsigned integer, so the k-th smallest value is found digit by
+// digit on the patterns, most significant digit first: of the elements whose higher digits equal the prefix found so far, count the
+// current digit's values, pick the digit d whose bin holds the rank (count of smaller digits <= rank < count up to d), append d to the
+// prefix and reduce the rank by the count of smaller digits.  After 64 / OS_BITS passes the prefix is the value itself: exact, no
+// comparison of rounded numbers anywhere.  The ranks lo and hi of the percentile are followed in the same passes (two prefixes, two
+// histograms).
+// The list's order differs from run to run (the waves' atomicAdds on its counter land in any order).  Nothing downstream depends on
+// it: the list is only ever counted (integer histograms, integer sums of which are order independent), never summed in floating
+// point or indexed by position, so out is bitwise equal between two runs.
+// No launch waits for another block: no spin loops, no cooperative launch; every loop is bounded by n (the grid-stride loops over the
+// inputs and over the list, whose length is at most 2 n) or by the number of digits (the launcher's pass loop, the 8-step scan).
+#define OS_BITS 8
+#define OS_BINS (1 << OS_BITS)          // == PO_BLOCK: thread t owns bin t
+#define OS_PASSES (64 / OS_BITS)
+#define OS_MAXBLK 512
+
+struct os_state {
+    unsigned count;                    // length of the list = N
+    unsigned le;                       // |{x <= tolerance}|
+    unsigned rank[2];                  // of lo, hi among the elements whose higher digits equal prefix[.]
+    unsigned long long prefix[2];      // the digits found so far, in place
+    double frac;                       // h - lo
+    double pad;                        // the histograms that follow start on a 16-byte boundary
+};
+#define OS_STATE_DOUBLES ((long)(sizeof(os_state) / 8 + OS_PASSES * 2 * OS_BINS * sizeof(unsigned) / 8))
+
+// list[count ...] <- the v[e] with m[e] != 0, in any order.  Wave-aggregated: a ballot, one returning atomicAdd per wave that selected
+// something, every selected lane stores at its rank among the wave's selected lanes.  The list has room for 2 n values and each of the
+// two calls per list appends at most n.
+__global__ void __launch_bounds__(PO_BLOCK) os_append_kernel(const double* __restrict__ v, const unsigned char* __restrict__ m, long n,
+                                                             double tol, double* __restrict__ list, os_state* __restrict__ st) {
+    const int lane = threadIdx.x & 63;
+    for (long e0 = (long)blockIdx.x * PO_BLOCK + (threadIdx.x - lane); e0 < n; e0 += (long)gridDim.x * PO_BLOCK) {          // wave-uniform
+        const long e = e0 + lane;
+        const bool sel = e < n && m[e] != 0;
+        const double x = sel ? v[e] : 0.0;
+        const unsigned long long picked = __ballot(sel);
+        if (!picked) continue;
+        const int leader = __ffsll((long long)picked) - 1;
+        int base = 0;
+        if (lane == leader) base = (int)atomicAdd(&st->count, (unsigned)__popcll(picked));
+        base = __shfl(base, leader, 64);
+        if (sel) list[(size_t)(unsigned)base + (unsigned)__popcll(picked & ((1ull << lane) - 1ull))] = x;
+        const unsigned long long within = __ballot(sel && x <= tol);
+        if (within && lane == leader) atomicAdd(&st->le, (unsigned)__popcll(within));
+    }
+}
+
+// hist [2][OS_BINS] += the digit `pass` (0 = most significant) of the list's elements whose higher digits equal prefix[r]
+__global__ void __launch_bounds__(PO_BLOCK) os_hist_kernel(const double* __restrict__ list, const os_state* __restrict__ st,
+                                                           unsigned* __restrict__ hist, int pass) {
+    __shared__ unsigned lh[2][OS_BINS];
+    const unsigned long count = st->count;
+    if ((unsigned long)blockIdx.x * PO_BLOCK >= count) return;          // block-uniform: nothing of the list is this block's
+    lh[0][threadIdx.x] = 0u;
+    lh[1][threadIdx.x] = 0u;
+    __syncthreads();
+    const int shift = 64 - OS_BITS * (pass + 1);
+    const int up = (shift + OS_BITS) & 63;          // pass 0 has no higher digits: every element matches
+    const unsigned long long p0 = pass ? st->prefix[0] >> up : 0ull, p1 = pass ? st->prefix[1] >> up : 0ull;
+    for (unsigned long e = (unsigned long)blockIdx.x * PO_BLOCK + threadIdx.x; e < count; e += (unsigned long)gridDim.x * PO_BLOCK) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(list[e]);
+        const unsigned d = (unsigned)(b >> shift) & (OS_BINS - 1);
+        const unsigned long long hb = pass ? b >> up : 0ull;
+        if (hb == p0) atomicAdd(&lh[0][d], 1u);
+        if (hb == p1) atomicAdd(&lh[1][d], 1u);
+    }
+    __syncthreads();
+    for (int r = 0; r < 2; ++r) {
+        const unsigned c = lh[r][threadIdx.x];
+        if (c) atomicAdd(hist + r * OS_BINS + threadIdx.x, c);
+    }
+}
+
+// one block.  Pass 0 first turns the list's length into the two ranks: h = (N - 1) * (percentile / 100) in fp64, lo = floor(h),
+// hi = min(lo + 1, N - 1).  Then an inclusive scan of either histogram; the one bin that holds the rank extends the prefix.  With
+// N == 0 no bin does, and the state stays zero.
+__global__ void __launch_bounds__(PO_BLOCK) os_pick_kernel(os_state* __restrict__ st, const unsigned* __restrict__ hist, int pass,
+                                                           double percentile) {
+#pragma clang fp contract(off)
+    __shared__ unsigned sc[2][OS_BINS];
+    __shared__ unsigned rk[2];
+    const int t = threadIdx.x;
+    if (t == 0) {
+        if (pass == 0) {
+            const unsigned N = st->count;
+            unsigned lo = 0u, hi = 0u;
+            double frac = 0.0;
+            if (N > 0u) {
+                const double h = (double)(N - 1u) * (percentile / 100.0);          // numpy's order: the quantile first
+                const double fl = fmin(floor(h), (double)(N - 1u));
+                lo = (unsigned)fl;
+                hi = lo + 1u < N ? lo + 1u : N - 1u;
+                frac = h - fl;
+            }
+            st->rank[0] = lo;
+            st->rank[1] = hi;
+            st->frac = frac;
+        }
+        rk[0] = st->rank[0];
+        rk[1] = st->rank[1];
+    }
+    const unsigned own[2] = {hist[t], hist[OS_BINS + t]};
+    sc[0][t] = own[0];
+    sc[1][t] = own[1];
+    __syncthreads();
+    for (int o = 1; o < OS_BINS; o <<= 1) {
+        const unsigned a0 = t >= o ? sc[0][t - o] : 0u, a1 = t >= o ? sc[1][t - o] : 0u;
+        __syncthreads();
+        sc[0][t] += a0;
+        sc[1][t] += a1;
+        __syncthreads();
+    }
+    const int shift = 64 - OS_BITS * (pass + 1);
+    for (int r = 0; r < 2; ++r) {
+        const unsigned incl = sc[r][t], excl = incl - own[r];
+        if (excl <= rk[r] && rk[r] < incl) {          // true for exactly one t when the list is not empty
+            st->prefix[r] |= (unsigned long long)t << shift;
+            st->rank[r] = rk[r] - excl;
+        }
+    }
+}
+
+// D_(lo) + (h - lo) * (D_(hi) - D_(lo)), without contraction
+__device__ __forceinline__ double os_percentile(const os_state* st, double& lo, double& hi) {
+#pragma clang fp contract(off)
+    lo = __longlong_as_double((long long)st->prefix[0]);
+    hi = __longlong_as_double((long long)st->prefix[1]);
+    const double step = hi - lo;
+    return lo + st->frac * step;
+}
+
+// out [5] = N, |{x <= tolerance}|, the percentile, D_(lo), D_(hi); the last three nan for an empty list
+__global__ void os_out_kernel(const os_state* __restrict__ st, double* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double lo, hi;
+    const double v = os_percentile(st, lo, hi);
+    const bool empty = st->count == 0u;
+    out[0] = (double)st->count;
+    out[1] = (double)st->le;
+    out[2] = empty ? (double)NAN : v;
+    out[3] = empty ? (double)NAN : lo;
+    out[4] = empty ? (double)NAN : hi;
+}
+
+// row [8] of mmseg_surface_scores: columns 7 and 8 = |{x <= tolerance}|, the percentile; nan when either surface is empty
+__global__ void os_row_kernel(const os_state* __restrict__ st, const int* __restrict__ cp, const int* __restrict__ ct, int k,
+                              double* __restrict__ row) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double lo, hi;
+    const double v = os_percentile(st, lo, hi);
+    const bool empty = cp[2 * k + 1] == 0 || ct[2 * k + 1] == 0;
+    row[6] = empty ? (double)NAN : (double)st->le;
+    row[7] = empty ? (double)NAN : v;
+}
+
+static unsigned os_blocks(long n) {
+    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
+    return (unsigned)(b < 1 ? 1 : (b < OS_MAXBLK ? b : OS_MAXBLK));
+}
+
+static bool os_args_ok(double percentile, double tolerance) {
+    return isfinite(percentile) && percentile >= 0.0 && percentile <= 100.0 && isfinite(tolerance) && tolerance >= 0.0;
+}
+
+// state: the os_state, then the OS_PASSES histograms [2][OS_BINS]; all of it is zeroed here, on the stream
+static int os_reset(double* state, hipStream_t st) {
+    return (int)hipMemsetAsync(state, 0, sizeof(double) * (size_t)OS_STATE_DOUBLES, st);
+}
+
+static void os_append(const double* v, const unsigned char* m, long n, double tol, double* list, double* state, hipStream_t st) {
+    hipLaunchKernelGGL(os_append_kernel, dim3(os_blocks(n)), dim3(PO_BLOCK), 0, st, v, m, n, tol, list, reinterpret_cast<os_state*>(state));
+}
+
+// the radix passes over a list of at most `capacity` values; the grid is sized by the capacity, the loops by the device's count
+static void os_select(const double* list, double* state, long capacity, double percentile, hipStream_t st) {
+    os_state* s = reinterpret_cast<os_state*>(state);
+    unsigned* hist = reinterpret_cast<unsigned*>(state + sizeof(os_state) / 8);
+    for (int pass = 0; pass < OS_PASSES; ++pass) {
+        hipLaunchKernelGGL(os_hist_kernel, dim3(os_blocks(capacity)), dim3(PO_BLOCK), 0, st, list, s, hist + pass * 2 * OS_BINS, pass);
+        hipLaunchKernelGGL(os_pick_kernel, dim3(1), dim3(PO_BLOCK), 0, st, s, hist + pass * 2 * OS_BINS, pass, percentile);
+    }
+}
+
 // ---- connected components per organ, and the largest one of each --------------------------------------------------------------------
 // A union-find whose parent array is `comp` itself: comp[e] = 1 + (linear index of the parent of voxel e), 0 for a voxel that is no
 // organ's; a root points to itself.  A link always hangs the larger index below the smaller one (an integer atomic minimum), so
@@ -800,6 +995,83 @@ int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth,
         if (rc) return rc;
         hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
         hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 6 * k);
+    }
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// doubles of workspace of mmseg_masked_select: the list (2 n) and the selection's state; 0 for an n that it would refuse
+long mmseg_masked_select_workspace_doubles(long n) {
+    if (n < 0 || n >= 0x80000000L) return 0;
+    return 2 * n + OS_STATE_DOUBLES;
+}
+
+// a, b [n] fp64 (finite, >= 0), ma, mb [n] uint8 -> out [5] = N, |{x <= tolerance}|, the percentile (numpy's linear rule), D_(lo), D_(hi)
+// over {a[e] : ma[e] != 0} + {b[e] : mb[e] != 0}; the last three nan when N == 0.  No host synchronisation, allocation or copy.
+int mmseg_masked_select(const double* a, const unsigned char* ma, const double* b, const unsigned char* mb, long n, double percentile,
+                        double tolerance, double* out, double* ws, void* stream) {
+    if (!a || !ma || !b || !mb || !out || !ws || n < 0 || n >= 0x80000000L || !os_args_ok(percentile, tolerance))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    double* list = ws;
+    double* state = ws + 2 * n;
+    const int rc = os_reset(state, st);
+    if (rc) return rc;
+    if (n > 0) {
+        os_append(a, ma, n, tolerance, list, state, st);
+        os_append(b, mb, n, tolerance, list, state, st);
+        os_select(list, state, 2 * n, percentile, st);
+    }
+    hipLaunchKernelGGL(os_out_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const os_state*>(state), out);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// doubles of workspace of mmseg_surface_scores: that of mmseg_surface_metrics, then the list (2 S H W) and the selection's state
+long mmseg_surface_scores_workspace_doubles(int S, int H, int W, int K) {
+    const long base = mmseg_surface_metrics_workspace_doubles(S, H, W, K);
+    if (base == 0) return 0;
+    return base + 2 * (long)S * H * W + OS_STATE_DOUBLES;
+}
+
+// pred, truth [S,H,W] uint8 -> table [K+1,8] fp64: the six columns of mmseg_surface_metrics, |{x <= tolerance}| and the percentile of the
+// surface distances of both directions together (nan when either surface is empty).  The walk of mmseg_surface_metrics; every map's
+// surface distances are appended to the problem's list before the next transform overwrites the map.
+int mmseg_surface_scores(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
+                         int H, int W, int K, double dz, double dy, double dx, double percentile, double tolerance, void* stream) {
+    if (S <= 0) return 0;
+    if (!pred || !truth || !values || !table || !ws || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES || !po_spacing_ok(dz) ||
+        !po_spacing_ok(dy) || !po_spacing_ok(dx) || !os_args_ok(percentile, tolerance))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)S * H * W;
+    double* da = ws;
+    double* db = da + n;
+    double* part = db + n;
+    int* cp = reinterpret_cast<int*>(part + 4 * PO_RED_BLOCKS);
+    int* ct = cp + 2 * (K + 1);
+    unsigned char* sp = reinterpret_cast<unsigned char*>(reinterpret_cast<double*>(cp) + po_round8((long)sizeof(int) * 4 * (K + 1)));
+    unsigned char* stv = sp + (size_t)(K + 1) * n;
+    double* list = ws + mmseg_surface_metrics_workspace_doubles(S, H, W, K);
+    double* state = list + 2 * n;
+    int rc = po_surface(pred, values, sp, cp, S, H, W, K, st);
+    if (rc) return rc;
+    rc = po_surface(truth, values, stv, ct, S, H, W, K, st);
+    if (rc) return rc;
+    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
+    const int nblk = (int)(b < PO_RED_BLOCKS ? b : PO_RED_BLOCKS);
+    for (int k = 0; k <= K; ++k) {
+        rc = os_reset(state, st);
+        if (rc) return rc;
+        rc = po_edt(stv + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);          // distance to surface(T), over surface(P)
+        if (rc) return rc;
+        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, sp + (size_t)k * n, da, n, part);
+        os_append(da, sp + (size_t)k * n, n, tolerance, list, state, st);
+        rc = po_edt(sp + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
+        os_append(da, stv + (size_t)k * n, n, tolerance, list, state, st);
+        hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 8 * k);
+        os_select(list, state, 2 * n, percentile, st);
+        hipLaunchKernelGGL(os_row_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const os_state*>(state), cp, ct, k, table + 8 * k);
     }
     return MMSEG_CHECK_LAUNCH();
 }

@@ -5,6 +5,7 @@
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
+                         [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
@@ -60,7 +61,24 @@ def parse_arguments(argv=None):
                     help="largest: keep each organ's largest 3-D connected component in the predicted label volumes")
     ap.add_argument('--predict_connectivity', type=int, choices=[6, 26], default=6,
                     help='neighbours of --predict_components: faces / faces, edges and corners')
-    return ap.parse_args(argv)
+    ap.add_argument('--predict_robust', type=true_or_false, default=False, metavar='true|false',
+                    help='also score them by HD (a percentile of the surface distances) and NSD (surface Dice at a tolerance): '
+                         'results_robust_<modality>.csv')
+    ap.add_argument('--predict_percentile', type=float, default=95.0, metavar='Q', help='percentile of --predict_robust, 0 to 100')
+    ap.add_argument('--predict_tolerance', type=float, default=1.0, metavar='MM', help='tolerance of --predict_robust in mm, 0 or more')
+    args = ap.parse_args(argv)
+    if not 0.0 <= args.predict_percentile <= 100.0:          # here, so that a bad value stops the run before the model is built
+        ap.error('--predict_percentile must lie in [0, 100], got %r' % args.predict_percentile)
+    if not 0.0 <= args.predict_tolerance < float('inf'):
+        ap.error('--predict_tolerance must be a finite number of mm >= 0, got %r' % args.predict_tolerance)
+    return args
+
+
+def robust_of(args):
+    """(percentile, tolerance in mm) of --predict_robust true, else None"""
+    if not getattr(args, 'predict_robust', False):
+        return None
+    return float(getattr(args, 'predict_percentile', 95.0)), float(getattr(args, 'predict_tolerance', 1.0))
 
 
 def _flag(config, args, name):
@@ -209,7 +227,7 @@ class Experiment(object):
             VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
                                               surface=getattr(args, 'predict_surface', True),
                                               components={'largest': 'largest'}.get(getattr(args, 'predict_components', 'none')),
-                                              connectivity=getattr(args, 'predict_connectivity', 6))
+                                              connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 

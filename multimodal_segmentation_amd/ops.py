@@ -1690,6 +1690,54 @@ def surface_metrics(pred, truth, values, spacing):
     return table
 
 
+def _robust_args(op, percentile, tolerance):
+    q, tau = float(percentile), float(tolerance)
+    if not 0.0 <= q <= 100.0:          # false for nan as well
+        raise ValueError('%s: percentile must lie in [0, 100], got %r' % (op, percentile))
+    if not 0.0 <= tau < float('inf'):
+        raise ValueError('%s: tolerance must be a finite number of mm >= 0, got %r' % (op, tolerance))
+    return q, tau
+
+
+def masked_select(a, ma, b, mb, percentile, tolerance):
+    """a, b fp64 and ma, mb uint8, all of one shape on the device -> fp64 [5] = N, |{x <= tolerance}|, the percentile, D_(lo), D_(hi) of
+    the multiset D = {a[e] : ma[e] != 0} + {b[e] : mb[e] != 0} (csrc/postprocess.hip: an exact radix selection on the bit patterns).
+    The selected values must be finite and >= 0.  numpy.percentile's linear rule: h = (N - 1) * (percentile / 100), lo = floor(h),
+    hi = min(lo + 1, N - 1), D_(lo) + (h - lo) * (D_(hi) - D_(lo)); the last three are nan when nothing is selected."""
+    q, tau = _robust_args('masked_select', percentile, tolerance)
+    if (a.dtype != torch.float64 or b.dtype != torch.float64 or ma.dtype != torch.uint8 or mb.dtype != torch.uint8
+            or any(tuple(t.shape) != tuple(a.shape) or t.device != a.device for t in (ma, b, mb)) or a.numel() >= 2 ** 31):
+        raise ValueError('masked_select: values %s %s, %s %s, masks %s %s, %s %s (expected fp64 values and uint8 masks of one shape with '
+                         'fewer than 2^31 elements)' % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype, tuple(ma.shape), ma.dtype,
+                                                        tuple(mb.shape), mb.dtype))
+    n = a.numel()
+    out = torch.zeros(5, dtype=torch.float64, device=a.device)
+    if n == 0:          # empty tensors have no storage to point at
+        out[2:] = float('nan')
+        return out
+    ws = _ws_f64('masked_select', N.call('mmseg_masked_select_workspace_doubles', n), a.device)
+    N.call('mmseg_masked_select', _c(a), _c(ma), _c(b), _c(mb), n, q, tau, out, ws)
+    return out
+
+
+def surface_scores(pred, truth, values, spacing, percentile=95.0, tolerance=1.0):
+    """surface_metrics with two more columns -> fp64 [K+1,8]: nP, nT, |surface(P)|, |surface(T)|, sum, max (bit for bit those of
+    surface_metrics), then |{x in D : x <= tolerance}| and numpy.percentile(D, percentile), where D holds the distances in mm of
+    surface(P) to surface(T) and of surface(T) to surface(P) together; columns 5 to 8 are nan when either surface is empty.  Every
+    distance transform runs once.  HD(q) and NSD(tau) follow on the host (volume_predictor.robust_from_table)."""
+    K = _volume_args('surface_scores', pred, values, (truth,))
+    dz, dy, dx = _spacing_args('surface_scores', spacing)
+    q, tau = _robust_args('surface_scores', percentile, tolerance)
+    S, H, W = pred.shape
+    table = torch.zeros((K + 1, 8), dtype=torch.float64, device=pred.device)
+    if S == 0:
+        table[:, 4:] = float('nan')
+        return table
+    ws = _ws_f64('surface_metrics', N.call('mmseg_surface_scores_workspace_doubles', S, H, W, K), pred.device)
+    N.call('mmseg_surface_scores', _c(pred), _c(truth), values, table, ws, S, H, W, K, dz, dy, dx, q, tau)
+    return table
+
+
 def _ws_i32(tag, nbytes, device):
     """_ws_f64 for the int32 scratch of the component filter (grow-only, per tag, device and stream)"""
     key = (tag, device, _sid(device))

@@ -14,6 +14,9 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
                                            model_tester.write_results, one row per labelled volume
     <out>/results_surface_<modality>.csv   where they also carry `slice_spacing`: RAVD (%), ASSD and MSSD (mm) of the union of the
                                            organs and of every organ, one row per scored volume
+    <out>/results_robust_<modality>.csv    with robust=(percentile, tolerance in mm), for the files the surface file scores: HD (the
+                                           percentile of the surface distances, mm) and NSD (the share of them within the tolerance)
+                                           of the union of the organs and of every organ, one row per scored volume
     <out>/results_components_<modality>.csv   with components='largest': per organ the number of connected components, its voxels
                                            before the filter and the voxels kept, one row per volume
 
@@ -27,7 +30,9 @@ from the counts summed over the organs, then the mean over the selected slices.
 The scores in mm (build-defined: the reference scores Dice only; the rules restate the metric set of the CHAOS challenge from memory,
 INTEGRATION.md section 5) are taken on the whole file grid [S_file,H,W]: the prediction is scattered to its file positions on the
 device, the truth slices that `slices` does not select are zero, and ops.surface_metrics returns one [K+1,6] table per volume, the only
-thing that leaves the device.  `score_volume` and `write_scores` are shared with tools/score_predictions.py, which scores label
+thing that leaves the device.  With robust=(percentile, tolerance) (build-defined, off by default; HD(q) and NSD(tau) of INTEGRATION.md
+section 5) ops.surface_scores takes its place: the same table with two more columns, from the same distance transforms, so that one
+call serves both CSV files.  `score_volume` and `write_scores` are shared with tools/score_predictions.py, which scores label
 volumes written earlier (`score_folder`)."""
 import json
 import logging
@@ -76,19 +81,51 @@ def chaos_from_table(table):
     return out
 
 
-def score_volume(pred, label, values, geometry, surface=True):
+def check_robust(robust):
+    """robust: None or (percentile in [0, 100], tolerance in mm >= 0) -> None or the pair as floats"""
+    if robust is None:
+        return None
+    try:
+        q, tau = (float(v) for v in robust)
+    except (TypeError, ValueError):
+        raise ValueError('robust must be None or (percentile, tolerance in mm), got %r' % (robust,))
+    if not 0.0 <= q <= 100.0:
+        raise ValueError('robust: the percentile must lie in [0, 100], got %r' % (robust[0],))
+    if not 0.0 <= tau < float('inf'):
+        raise ValueError('robust: the tolerance must be a finite number of mm >= 0, got %r' % (robust[1],))
+    return q, tau
+
+
+def robust_from_table(table):
+    """table [K+1,8] of ops.surface_scores -> [K+1,2] = HD (mm: column 8, the percentile of the surface distances of both directions
+    together), NSD = column 7 / (|surface(P)| + |surface(T)|); both nan where the table says so (an empty surface)"""
+    t = np.asarray(table, np.float64)
+    out = np.full((t.shape[0], 2), np.nan)
+    for k, row in enumerate(t):
+        if row[2] > 0 and row[3] > 0:
+            out[k] = row[7], row[6] / (row[2] + row[3])
+    return out
+
+
+def score_volume(pred, label, values, geometry, surface=True, robust=None):
     """pred, label: uint8 [S,H,W] on the device, the selected slices of one file in order; geometry: the record of
     loader.load_volume_for_prediction (raw_shape, slices, resolution, slice_spacing are read) -> (joint Dice, [per organ], scores in
-    mm [K+1,3] with the union LAST, or None when they are not asked for or the file holds no slice_spacing)"""
+    mm [K+1,3] with the union LAST, or None when they are not asked for or the file holds no slice_spacing).  With robust =
+    (percentile, tolerance in mm) a fourth item follows: [K+1,2] = HD, NSD with the union last, or None for a file without
+    slice_spacing; both tables then come from one ops.surface_scores call."""
+    robust = check_robust(robust)
     joint, per_organ = dice_from_counts(nn.to_numpy(ops.label_overlap(pred, label, values)))
-    if not surface or geometry.get('slice_spacing') is None:
-        return joint, per_organ, None
+    if (not surface and robust is None) or geometry.get('slice_spacing') is None:
+        return (joint, per_organ, None) if robust is None else (joint, per_organ, None, None)
     where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=pred.device)
     grid = tuple(int(n) for n in geometry['raw_shape'])
     on_grid = [torch.zeros(grid, dtype=torch.uint8, device=pred.device).index_copy_(0, where, x) for x in (pred, label)]
     spacing = (float(geometry['slice_spacing']), float(geometry['resolution'][0]), float(geometry['resolution'][1]))
-    table = ops.surface_metrics(on_grid[0], on_grid[1], values, spacing)
-    return joint, per_organ, chaos_from_table(nn.to_numpy(table))
+    if robust is None:
+        table = ops.surface_metrics(on_grid[0], on_grid[1], values, spacing)
+        return joint, per_organ, chaos_from_table(nn.to_numpy(table))
+    table = nn.to_numpy(ops.surface_scores(on_grid[0], on_grid[1], values, spacing, robust[0], robust[1]))
+    return joint, per_organ, (chaos_from_table(table[:, :6]) if surface else None), robust_from_table(table)
 
 
 COMPONENTS = (None, 'largest')
@@ -131,32 +168,50 @@ def write_surface_results(path, rows, num_masks):
             f.write(', '.join([str(vol)] + ['%.3f' % v for v in ordered]) + '\n')
 
 
-def write_scores(out_folder, modalities, rows, surface_rows, num_masks):
-    """results_native_<modality>.csv / results_surface_<modality>.csv for the modalities that have rows"""
+def write_robust_results(path, rows, num_masks):
+    """rows: (volume, [K+1,2] with the union last) -> Vol, HD, NSD, HD0, NSD0, ...: the union first"""
+    cols = ['Vol', 'HD', 'NSD'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('HD', 'NSD')]
+    with open(path, 'w') as f:
+        f.write(', '.join(cols) + '\n')
+        for vol, scores in rows:
+            ordered = np.concatenate([scores[-1:], scores[:-1]], axis=0).reshape(-1)
+            f.write(', '.join([str(vol)] + ['%.3f' % v for v in ordered]) + '\n')
+
+
+def write_scores(out_folder, modalities, rows, surface_rows, num_masks, robust_rows=None):
+    """results_native_<modality>.csv / results_surface_<modality>.csv / results_robust_<modality>.csv for the modalities that have rows"""
     for m, name in enumerate(modalities):
         if rows[m]:
             write_results(os.path.join(out_folder, 'results_native_%s.csv' % name), rows[m], num_masks)
         if surface_rows[m]:
             write_surface_results(os.path.join(out_folder, 'results_surface_%s.csv' % name), surface_rows[m], num_masks)
+        if robust_rows and robust_rows[m]:
+            write_robust_results(os.path.join(out_folder, 'results_robust_%s.csv' % name), robust_rows[m], num_masks)
 
 
-def collect_scores(rows, surface_rows, m, volume, modality, scores, geometry, surface):
-    joint, per_organ, in_mm = scores
+def collect_scores(rows, surface_rows, m, volume, modality, scores, geometry, surface, robust_rows=None):
+    joint, per_organ, in_mm = scores[:3]
+    robust = scores[3] if robust_rows is not None else None
     rows[m].append((volume, joint, per_organ))
     log.info('volume %s, %s: Dice on the raw grid %.3f' % (volume, modality, joint))
     if in_mm is not None:
         surface_rows[m].append((volume, in_mm))
         log.info('volume %s, %s: RAVD %.3f %%, ASSD %.3f mm, MSSD %.3f mm' % ((volume, modality) + tuple(in_mm[-1])))
-    elif surface:
+    if robust is not None:
+        robust_rows[m].append((volume, robust))
+        log.info('volume %s, %s: HD %.3f mm, NSD %.3f' % ((volume, modality) + tuple(robust[-1])))
+    if geometry.get('slice_spacing') is None and (surface or robust_rows is not None):
         log.info("volume %s, %s: %s holds no 'slice_spacing', so no scores in mm" % (volume, modality, geometry['file']))
 
 
-def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6):
+def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6, robust=None):
     """Score label volumes written earlier (by VolumePredictor.run or by another program: <file name of the input>.npz with `label`
     [S_file,H,W] uint8) against the labelled files of `data_folder`; writes the CSV files of VolumePredictor.run into out_folder
     (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json.
-    components='largest' filters every volume first (keep_largest): the scores that post-processing would give."""
+    components='largest' filters every volume first (keep_largest): the scores that post-processing would give.
+    robust=(percentile, tolerance in mm) also writes results_robust_<modality>.csv, and a third dictionary with its rows is returned."""
     check_components(components, connectivity)
+    robust = check_robust(robust)
     loader = VolumeFolderLoader(data_folder)
     out_folder = out_folder or pred_folder
     os.makedirs(out_folder, exist_ok=True)
@@ -169,6 +224,7 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
     device = nn.default_device()
     values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
     rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
+    robust_rows = None if robust is None else [[] for _ in loader.modalities]
     for v in volumes:
         for m, mod in enumerate(loader.modalities):
             entry = loader.manifest['volumes'][v][mod]
@@ -188,11 +244,14 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
             pred = nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8)
             if components:
                 pred, _ = keep_largest(pred, values, geo, connectivity)
-            scores = score_volume(pred, nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface)
-            collect_scores(rows, surface_rows, m, v, mod, scores, geo, surface)
-    write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
-    return ({name: rows[m] for m, name in enumerate(loader.modalities)},
-            {name: surface_rows[m] for m, name in enumerate(loader.modalities)})
+            scores = score_volume(pred, nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface,
+                                  robust)
+            collect_scores(rows, surface_rows, m, v, mod, scores, geo, surface, robust_rows)
+    write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks, robust_rows)
+    by_name = [{name: table[m] for m, name in enumerate(loader.modalities)} for table in (rows, surface_rows)]
+    if robust is None:
+        return by_name[0], by_name[1]
+    return by_name[0], by_name[1], {name: robust_rows[m] for m, name in enumerate(loader.modalities)}
 
 
 class VolumePredictor(object):
@@ -207,8 +266,9 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
-    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6):
+    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None):
         check_components(components, connectivity)
+        robust = check_robust(robust)
         if mode not in FUSION_MODES:
             raise ValueError('Unknown mode: %r (expected one of %s)' % (mode, ', '.join(FUSION_MODES)))
         if order not in (0, 1):
@@ -230,6 +290,7 @@ class VolumePredictor(object):
         values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
         rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
         component_rows = [[] for _ in loader.modalities]
+        robust_rows = None if robust is None else [[] for _ in loader.modalities]
         files = {}
         for v in volumes:
             images, geometry = loader.load_volume_for_prediction(v)
@@ -240,14 +301,14 @@ class VolumePredictor(object):
                     pred, stats = keep_largest(pred, values, geo, connectivity)
                     component_rows[m].append((v, nn.to_numpy(stats)))
                 if geo['label'] is not None:
-                    scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface)
-                    collect_scores(rows, surface_rows, m, v, loader.modalities[m], scores, geo, surface)
+                    scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface, robust)
+                    collect_scores(rows, surface_rows, m, v, loader.modalities[m], scores, geo, surface, robust_rows)
                 label = np.zeros(geo['raw_shape'], np.uint8)
                 label[geo['slices']] = pred.cpu().numpy()
                 extra = {} if geo['slice_spacing'] is None else dict(slice_spacing=float(geo['slice_spacing']))
                 np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
                 files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
-        write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks)
+        write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks, robust_rows)
         for m, name in enumerate(loader.modalities):
             if component_rows[m]:
                 write_component_results(os.path.join(out_folder, 'results_components_%s.csv' % name), component_rows[m], loader.num_masks)
@@ -255,6 +316,8 @@ class VolumePredictor(object):
                         label_values=loader.label_values, files=files)
         if components:
             settings.update(components=components, connectivity=connectivity)
+        if robust is not None:
+            settings.update(percentile=robust[0], tolerance_mm=robust[1])
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
         return {name: rows[m] for m, name in enumerate(loader.modalities)}

@@ -7,11 +7,15 @@ that carry `slice_spacing`, RAVD, ASSD and MSSD in mm (results_surface_<modality
 PRED_FOLDER holds one `<file name of the input>.npz` with `label` [S_file,H,W] uint8 per scored file; files that are missing there, or
 that carry no label in DATA_FOLDER, are left out.
 
+`--predict_robust true` also writes HD (the `--predict_percentile` of the surface distances, default 95) and NSD (the share of them
+within `--predict_tolerance` mm, default 1.0) into results_robust_<modality>.csv, for the files the surface file scores.
+
 `--components largest` keeps each organ's largest 3-D connected component in every volume read from PRED_FOLDER before it is scored
 (`--connectivity 6|26`): the scores that `--predict_components largest` would have given, for volumes written without it.
 
     python tools/score_predictions.py PRED_FOLDER DATA_FOLDER [--out OUT] [--surface true|false] [--components largest]
-                                      [--connectivity 6|26]
+                                      [--connectivity 6|26] [--predict_robust true|false] [--predict_percentile Q]
+                                      [--predict_tolerance MM]
 """
 import argparse
 import logging
@@ -32,11 +36,22 @@ def main(argv=None):
     ap.add_argument('--surface', type=true_or_false, default=True, metavar='true|false', help='also the scores in mm')
     ap.add_argument('--components', choices=['largest'], help="filter the predicted volumes first: each organ's largest component")
     ap.add_argument('--connectivity', type=int, choices=[6, 26], default=6, help='neighbours of --components')
+    ap.add_argument('--predict_robust', type=true_or_false, default=False, metavar='true|false', help='also HD and NSD')
+    ap.add_argument('--predict_percentile', type=float, default=95.0, metavar='Q', help='percentile of --predict_robust, 0 to 100')
+    ap.add_argument('--predict_tolerance', type=float, default=1.0, metavar='MM', help='tolerance of --predict_robust in mm, 0 or more')
     a = ap.parse_args(argv)
+    if not 0.0 <= a.predict_percentile <= 100.0:
+        ap.error('--predict_percentile must lie in [0, 100], got %r' % a.predict_percentile)
+    if not 0.0 <= a.predict_tolerance < float('inf'):
+        ap.error('--predict_tolerance must be a finite number of mm >= 0, got %r' % a.predict_tolerance)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
-    rows, surface_rows = score_folder(a.pred_folder, a.data_folder, a.out, a.surface, a.components, a.connectivity)
+    robust = (a.predict_percentile, a.predict_tolerance) if a.predict_robust else None
+    tables = score_folder(a.pred_folder, a.data_folder, a.out, a.surface, a.components, a.connectivity, robust)
+    rows, surface_rows = tables[:2]
     for name in rows:
         print('%s: %d volumes scored, %d of them in mm' % (name, len(rows[name]), len(surface_rows[name])))
+        if robust is not None:
+            print('%s: %d volumes scored by HD(%g) and NSD(%g mm)' % ((name, len(tables[2][name])) + robust))
 
 
 if __name__ == '__main__':
