@@ -243,10 +243,14 @@ def colsum(x, out, ws, M, C, scale, accumulate):
 
 
 def maxpool2_fwd(x, y, B, H, W, C):
+    if (C & 3) or (H & 1) or (W & 1):            # the library's own argument check (csrc/pointwise.hip)
+        return 1
     y.copy_(O.maxpool2(x.reshape(B, H, W, C))); return 0
 
 
 def maxpool2_bwd(x, y, dy, dx, B, H, W, C):
+    if (C & 3) or (H & 1) or (W & 1):
+        return 1
     with torch.enable_grad():
         xr = x.reshape(B, H, W, C).detach().clone().requires_grad_(True)
         out = O.maxpool2(xr)
@@ -255,7 +259,9 @@ def maxpool2_bwd(x, y, dy, dx, B, H, W, C):
 
 
 def maxpool2_bwd_add_t(x, y, dy, add, dx, B, H, W, C, h):
-    maxpool2_bwd(x, y, dy, dx, B, H, W, C)
+    rc = maxpool2_bwd(x, y, dy, dx, B, H, W, C)
+    if rc:
+        return rc
     if add is not None:
         dx.add_(add.reshape(dx.shape))
     return 0
@@ -291,19 +297,27 @@ def add_residual(msk, out, M, C):
 
 
 def upsample2_bwd(dy, dx, B, H, W, C):
+    if C & 3:                                    # the library's own argument check (csrc/pointwise.hip)
+        return 1
     d = dy.reshape(B, H, 2, W, 2, C).sum((2, 4))
     dx.copy_(d); return 0
 
 
 def upsample2_fwd(x, y, B, H, W, C):
+    if C & 3:
+        return 1
     y.copy_(O.upsample2(x.reshape(B, H, W, C))); return 0
 
 
 def subsample_fwd(x, y, B, Ho, Wo, C, f):
+    if f < 1:                                    # the library's own argument check (csrc/pointwise.hip)
+        return 1
     y.copy_(x.reshape(B, Ho * f, Wo * f, C)[:, ::f, ::f]); return 0
 
 
 def subsample_bwd(dy, dx, B, Ho, Wo, C, f):
+    if f < 1:
+        return 1
     d = torch.zeros(B, Ho * f, Wo * f, C, dtype=dy.dtype)
     d[:, ::f, ::f] = dy.reshape(B, Ho, Wo, C)
     dx.copy_(d); return 0
@@ -356,10 +370,14 @@ def maximum_bwd(a, b, dy, da, db, n):
 
 
 def slice_fwd(x, y, M, C, c0, Cs):
+    if c0 < 0 or c0 + Cs > C:                    # the library's own argument check (csrc/pointwise.hip)
+        return 1
     y.copy_(x.reshape(M, C)[:, c0:c0 + Cs].reshape(y.shape)); return 0
 
 
 def slice_bwd(dy, dx, M, C, c0, Cs):
+    if c0 < 0 or c0 + Cs > C:
+        return 1
     d = torch.zeros(M, C, dtype=dy.dtype)
     d[:, c0:c0 + Cs] = dy.reshape(M, Cs)
     dx.copy_(d.reshape(dx.shape)); return 0
@@ -510,6 +528,8 @@ def dense_workspace_floats(R, K, N):
 
 
 def dense_fwd(x, w, bias, y, ws, R, K, N, act, alpha):
+    if R < 1 or R > 32:                          # the library's own argument check (csrc/dense.hip): <= 32 rows in registers
+        return 1
     v = x.reshape(R, K) @ w.reshape(K, N)
     if bias is not None:
         v = v + bias
@@ -517,10 +537,14 @@ def dense_fwd(x, w, bias, y, ws, R, K, N, act, alpha):
 
 
 def dense_dgrad(dy, w, dx, R, K, N):
+    if R < 1 or R > 32:
+        return 1
     dx.copy_(dy.reshape(R, N) @ w.reshape(K, N).t()); return 0
 
 
 def dense_wgrad(x, dy, dw, R, K, N, accumulate):
+    if R < 1 or R > 32:
+        return 1
     v = (x.reshape(R, K).t() @ dy.reshape(R, N)).reshape(dw.shape)
     if accumulate:
         dw.add_(v)
@@ -672,12 +696,16 @@ def spectral_fwd(w, u0, loss, sgn, ws, K, N, alpha):
 
 
 def spectral_fwd4(w0, w1, w2, w3, u0, u1, u2, u3, loss, sgn, ws, n, K0, N0, K1, N1, K2, N2, K3, N3, alpha):
+    if n < 1 or n > 4:                           # the library's own argument check (csrc/optim.hip)
+        return 1
     for i, (w, u, K, N_) in enumerate(((w0, u0, K0, N0), (w1, u1, K1, N1), (w2, u2, K2, N2), (w3, u3, K3, N3))[:n]):
         spectral_fwd(w, u, loss[i:i + 1], sgn[i:i + 1], None, K, N_, alpha)
     return 0
 
 
 def spectral_grad4(w0, w1, w2, w3, sgn, d0, d1, d2, d3, n, n0, n1, n2, n3, scale):
+    if n < 1 or n > 4:
+        return 1
     for i, (w, d) in enumerate(((w0, d0), (w1, d1), (w2, d2), (w3, d3))[:n]):
         d.add_(torch.sign(w) * sgn[i] * scale)
     return 0

@@ -28,16 +28,27 @@ def _close(a, b, name, rtol=RTOL):
     assert err <= rtol * scale + 1e-7, '%s: max err %.3e (scale %.3e)' % (name, err, scale)
 
 
-def check(f_prod, f_ref, inputs, device, grad_mask=None, rtol=RTOL, param_idx=()):
+def gbuf_pattern(t):
+    """a non-zero content for a gradient buffer: 0.125, 0.25, 0.375, 0.5 repeating (dyadic, so that adding a gradient of magnitude
+    ~1 and subtracting the pattern again costs one fp32 rounding, ~6e-8 of the sum)"""
+    return ((torch.arange(t.numel(), dtype=torch.float32) % 4 + 1) * 0.125).reshape(t.shape)
+
+
+def check(f_prod, f_ref, inputs, device, grad_mask=None, rtol=RTOL, param_idx=(), gbuf_fill=None):
     """inputs: list of CPU fp32 tensors.  Runs both functions, a random cotangent, and compares outputs and the
     gradients of every input with grad_mask[i] true.  Inputs listed in `param_idx` are weights: the product gets
-    them as plain tensors plus a zeroed gradient buffer `t.gbuf` it accumulates into (no autograd leaf)."""
+    them as plain tensors plus a zeroed gradient buffer `t.gbuf` it accumulates into (no autograd leaf).  With
+    `gbuf_fill` (a function of the weight, e.g. gbuf_pattern) the buffers start from its value instead of zero and
+    `gbuf - fill` is what is compared: the product must ADD its gradient to what the buffer holds."""
     grad_mask = grad_mask or [True] * len(inputs)
-    xs_p = []
+    xs_p, fills = [], {}
     for i, (t, m) in enumerate(zip(inputs, grad_mask)):
         tp = t.clone().to(device)
         if i in param_idx:
             tp.gbuf = torch.zeros_like(tp)
+            if gbuf_fill is not None:
+                fills[i] = gbuf_fill(t)
+                tp.gbuf.copy_(fills[i])
         else:
             tp.requires_grad_(m)
         xs_p.append(tp)
@@ -59,6 +70,8 @@ def check(f_prod, f_ref, inputs, device, grad_mask=None, rtol=RTOL, param_idx=()
         if m:
             gp = xs_p[i].gbuf if i in param_idx else xs_p[i].grad
             assert gp is not None, 'no grad for input %d' % i
+            if i in fills:
+                gp = gp.detach().cpu().double() - fills[i].double()
             _close(gp, xs_r[i].grad, 'grad%d' % i, rtol)
 
 
