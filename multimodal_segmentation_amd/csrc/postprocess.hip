@@ -34,9 +34,9 @@
 //   volume is seen as [A, L, B] with B contiguous; a block owns 64 consecutive b and 64 outputs i, stages [64 j][64 b] tiles in LDS
 //   (global reads and LDS reads: consecutive lanes, consecutive doubles), a thread keeps 16 consecutive i in registers.  The last
 //   pass takes the square root.
-// mmseg_surface_metrics: per problem the two distance maps, each reduced over the other side's surface: per-thread partial sums in
-//   grid-stride order, a fixed LDS tree per block, partials [blocks][2] = (sum, max), and one block that adds the partials in a fixed
-//   tree: no floating-point atomics.  Only the [K+1,6] table is meant to leave the device.
+// po_surface_walk (behind mmseg_surface_metrics and mmseg_surface_scores): per problem the two distance maps, each reduced over the
+//   other side's surface: per-thread partial sums in grid-stride order, a fixed LDS tree per block, partials [blocks][2] = (sum, max),
+//   and one block that adds the partials in a fixed tree: no floating-point atomics.  Only the [K+1,6] table is meant to leave the device.
 //
 // Order statistics of the surface distances (build-defined; HD(q) and NSD(tau) in INTEGRATION.md section 5).
 // mmseg_masked_select: the multiset {a[e] : ma[e] != 0} + {b[e] : mb[e] != 0} of finite fp64 values >= 0 -> out [5] = N, |{x <= tolerance}|,
@@ -45,8 +45,8 @@
 //   os_hist_kernel (per-block LDS histograms of one 8-bit digit of the bit patterns, most significant first, one global integer atomic
 //   per non-empty bin) and os_pick_kernel (one block: scan, pick the digit, narrow the prefix) follow both ranks at once.  Exact and,
 //   integer counts being order independent, bitwise reproducible.  Nothing reaches the host: N and the ranks are computed on the device.
-// mmseg_surface_scores: mmseg_surface_metrics' walk with every distance map's surface values appended to the problem's list before
-//   the map is overwritten -> table [K+1,8]: the six columns of mmseg_surface_metrics (same kernels), |{x <= tolerance}|, HD(percentile).
+// mmseg_surface_scores: the same walk, told to append every distance map's surface values to the problem's list before the map is
+//   overwritten -> table [K+1,8]: the six columns of mmseg_surface_metrics (same launches), |{x <= tolerance}|, HD(percentile).
 //
 // The largest connected component of every organ (build-defined; the rule is in INTEGRATION.md section 5).
 // mmseg_label_components: label [S,H,W] -> comp [S,H,W] int32 = 1 + the smallest linear index of the voxel's component, 0 for a voxel
@@ -433,9 +433,11 @@ __global__ void __launch_bounds__(PO_BLOCK) po_surface_final_kernel(const int* _
     }
 }
 
-static int po_blocks(long n) {
+// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep, PO_RED_BLOCKS
+// the reductions (po_surface_final_kernel adds that many partials with one block), OS_MAXBLK the order statistics, CC_MAXBLK the components
+static unsigned po_grid(long n, long cap) {
     const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    return (int)(b < 1 ? 1 : (b < PO_MAXBLK ? b : PO_MAXBLK));
+    return (unsigned)(b < cap ? b : cap);
 }
 
 // as pp_axis_ok (0 <= lo, 1 <= kept, lo + kept <= R, 0 <= before < O), and the kept window must lie inside the container, which is
@@ -460,6 +462,8 @@ static void po_launch(dim3 grid, hipStream_t stream, const float* prob, const in
 // [S,H,W] with 1 <= H, W and fewer than 2^31 voxels
 static bool po_volume_ok(int S, int H, int W) { return H >= 1 && W >= 1 && (long)S * H * W < 0x7fffffffL; }
 static bool po_spacing_ok(double d) { return isfinite(d) && d > 0.0; }
+static bool po_spacings_ok(double dz, double dy, double dx) { return po_spacing_ok(dz) && po_spacing_ok(dy) && po_spacing_ok(dx); }
+static bool po_problem_ok(int S, int H, int W, int K) { return po_volume_ok(S, H, W) && K >= 1 && K <= PO_MAXVALUES; }
 
 // sites [S,H,W] -> a [S,H,W] distances in mm; b is scratch of the same size.  W pass sites -> a, H pass a -> b, S pass b -> a (sqrt)
 static int po_edt(const unsigned char* sites, double* a, double* b, int S, int H, int W, double dz, double dy, double dx, hipStream_t st) {
@@ -483,9 +487,7 @@ static int po_surface(const unsigned char* label, const int* values, unsigned ch
         const hipError_t rc = hipMemsetAsync(counts, 0, sizeof(int) * 2 * (size_t)(K + 1), st);
         if (rc != hipSuccess) return (int)rc;
     }
-    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    hipLaunchKernelGGL(po_surface_kernel, dim3((unsigned)(b < PO_SURF_MAXBLK ? b : PO_SURF_MAXBLK)), dim3(PO_BLOCK), 0, st, label, values, K,
-                       surf, counts, S, H, W);
+    hipLaunchKernelGGL(po_surface_kernel, dim3(po_grid(n, PO_SURF_MAXBLK)), dim3(PO_BLOCK), 0, st, label, values, K, surf, counts, S, H, W);
     return MMSEG_CHECK_LAUNCH();
 }
 
@@ -648,10 +650,9 @@ __global__ void os_row_kernel(const os_state* __restrict__ st, const int* __rest
     row[7] = empty ? (double)NAN : v;
 }
 
-static unsigned os_blocks(long n) {
-    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    return (unsigned)(b < 1 ? 1 : (b < OS_MAXBLK ? b : OS_MAXBLK));
-}
+struct os_args {
+    double percentile, tolerance;
+};
 
 static bool os_args_ok(double percentile, double tolerance) {
     return isfinite(percentile) && percentile >= 0.0 && percentile <= 100.0 && isfinite(tolerance) && tolerance >= 0.0;
@@ -663,7 +664,8 @@ static int os_reset(double* state, hipStream_t st) {
 }
 
 static void os_append(const double* v, const unsigned char* m, long n, double tol, double* list, double* state, hipStream_t st) {
-    hipLaunchKernelGGL(os_append_kernel, dim3(os_blocks(n)), dim3(PO_BLOCK), 0, st, v, m, n, tol, list, reinterpret_cast<os_state*>(state));
+    hipLaunchKernelGGL(os_append_kernel, dim3(po_grid(n, OS_MAXBLK)), dim3(PO_BLOCK), 0, st, v, m, n, tol, list,
+                       reinterpret_cast<os_state*>(state));
 }
 
 // the radix passes over a list of at most `capacity` values; the grid is sized by the capacity, the loops by the device's count
@@ -671,7 +673,7 @@ static void os_select(const double* list, double* state, long capacity, double p
     os_state* s = reinterpret_cast<os_state*>(state);
     unsigned* hist = reinterpret_cast<unsigned*>(state + sizeof(os_state) / 8);
     for (int pass = 0; pass < OS_PASSES; ++pass) {
-        hipLaunchKernelGGL(os_hist_kernel, dim3(os_blocks(capacity)), dim3(PO_BLOCK), 0, st, list, s, hist + pass * 2 * OS_BINS, pass);
+        hipLaunchKernelGGL(os_hist_kernel, dim3(po_grid(capacity, OS_MAXBLK)), dim3(PO_BLOCK), 0, st, list, s, hist + pass * 2 * OS_BINS, pass);
         hipLaunchKernelGGL(os_pick_kernel, dim3(1), dim3(PO_BLOCK), 0, st, s, hist + pass * 2 * OS_BINS, pass, percentile);
     }
 }
@@ -690,6 +692,7 @@ static void os_select(const double* list, double* state, long capacity, double p
 #define CC_TY 8
 #define CC_TZ 4
 #define CC_TILE (CC_TX * CC_TY * CC_TZ)
+#define CC_MAXBLK 4096          // of the grid-stride kernels
 
 // (dz, dy, dx) of the backward neighbours: the row neighbour, the other two faces, then the ten that only 26-connectivity has
 __device__ const signed char cc_off[13][3] = {{0, 0, -1}, {0, -1, 0},  {-1, 0, 0},  {0, -1, -1}, {0, -1, 1}, {-1, 0, -1}, {-1, 0, 1},
@@ -884,12 +887,7 @@ __global__ void __launch_bounds__(PO_BLOCK) po_cc_keep_kernel(const unsigned cha
 }
 
 static bool po_cc_args_ok(int S, int H, int W, int K, int connectivity) {
-    return po_volume_ok(S, H, W) && K >= 1 && K <= PO_MAXVALUES && (connectivity == 6 || connectivity == 26);
-}
-
-static unsigned po_cc_blocks(long n) {
-    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    return (unsigned)(b < 4 * PO_SURF_MAXBLK ? b : 4 * PO_SURF_MAXBLK);
+    return po_problem_ok(S, H, W, K) && (connectivity == 6 || connectivity == 26);
 }
 
 static int po_components(const unsigned char* label, const int* values, int* comp, int S, int H, int W, int K, int connectivity,
@@ -899,8 +897,67 @@ static int po_components(const unsigned char* label, const int* values, int* com
     const int nnb = connectivity == 26 ? 13 : 3;
     hipLaunchKernelGGL(po_cc_local_kernel, dim3((unsigned)((long)ntx * nty * ntz)), dim3(PO_BLOCK), 0, st, label, values, K, comp, S, H, W,
                        ntx, nty, nnb);
-    hipLaunchKernelGGL(po_cc_merge_kernel, dim3(po_cc_blocks(n)), dim3(PO_BLOCK), 0, st, label, comp, S, H, W, nnb);
-    hipLaunchKernelGGL(po_cc_flatten_kernel, dim3(po_cc_blocks(n)), dim3(PO_BLOCK), 0, st, comp, n);
+    hipLaunchKernelGGL(po_cc_merge_kernel, dim3(po_grid(n, CC_MAXBLK)), dim3(PO_BLOCK), 0, st, label, comp, S, H, W, nnb);
+    hipLaunchKernelGGL(po_cc_flatten_kernel, dim3(po_grid(n, CC_MAXBLK)), dim3(PO_BLOCK), 0, st, comp, n);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// the workspace of po_surface_walk, in this order; n = S * H * W
+struct po_walk_ws {
+    double *da, *db;               // two distance maps [n]
+    double* part;                  // the partials [2][PO_RED_BLOCKS][2] of the two directions
+    int *cp, *ct;                  // counts [K+1][2] of pred and of truth
+    unsigned char *sp, *st;        // surfaces [K+1][n] of pred and of truth
+    double *list, *state;          // with the order statistics only: the list [2 n] and the selection's state
+};
+
+// the one place that knows the layout: fills w from ws, or only sizes it when ws is null; returns the doubles needed
+static long po_walk_carve(double* ws, long n, int K, bool robust, po_walk_ws* w) {
+    const long counts = po_round8((long)sizeof(int) * 4 * (K + 1));
+    const long plain = 2 * n + 4 * PO_RED_BLOCKS + counts + po_round8(2 * (long)(K + 1) * n);
+    if (ws) {
+        w->da = ws;
+        w->db = w->da + n;
+        w->part = w->db + n;
+        w->cp = reinterpret_cast<int*>(w->part + 4 * PO_RED_BLOCKS);
+        w->ct = w->cp + 2 * (K + 1);
+        w->sp = reinterpret_cast<unsigned char*>(w->part + 4 * PO_RED_BLOCKS + counts);
+        w->st = w->sp + (size_t)(K + 1) * n;
+        w->list = ws + plain;
+        w->state = w->list + 2 * n;
+    }
+    return robust ? plain + 2 * n + OS_STATE_DOUBLES : plain;
+}
+
+// A loop of launches over the K + 1 problems on the stream: row k of `table` (rows `stride` doubles apart) gets its six columns and, with
+// `robust`, two more: every map's surface distances are then appended to the problem's list before the next transform overwrites the map
+static int po_surface_walk(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
+                           int H, int W, int K, double dz, double dy, double dx, int stride, const os_args* robust /* null: six columns */,
+                           hipStream_t st) {
+    const long n = (long)S * H * W;
+    po_walk_ws w;
+    po_walk_carve(ws, n, K, robust != nullptr, &w);
+    int rc = po_surface(pred, values, w.sp, w.cp, S, H, W, K, st);
+    if (rc) return rc;
+    rc = po_surface(truth, values, w.st, w.ct, S, H, W, K, st);
+    if (rc) return rc;
+    const int nblk = (int)po_grid(n, PO_RED_BLOCKS);
+    for (int k = 0; k <= K; ++k) {
+        const unsigned char* side[2] = {w.sp + (size_t)k * n, w.st + (size_t)k * n};
+        double* row = table + (size_t)stride * k;
+        if (robust && (rc = os_reset(w.state, st))) return rc;
+        for (int d = 0; d < 2; ++d) {          // the distance to surface(T) over surface(P), then the other way round
+            rc = po_edt(side[1 - d], w.da, w.db, S, H, W, dz, dy, dx, st);
+            if (rc) return rc;
+            hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, side[d], w.da, n, w.part + d * 2 * nblk);
+            if (robust) os_append(w.da, side[d], n, robust->tolerance, w.list, w.state, st);
+        }
+        hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, w.cp, w.ct, w.part, nblk, k, row);
+        if (robust) {
+            os_select(w.list, w.state, 2 * n, robust->percentile, st);
+            hipLaunchKernelGGL(os_row_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const os_state*>(w.state), w.cp, w.ct, k, row);
+        }
+    }
     return MMSEG_CHECK_LAUNCH();
 }
 
@@ -915,7 +972,7 @@ int mmseg_restore_label(const float* prob, const int* values, unsigned char* out
         return (int)hipErrorInvalidValue;
     const bool pack = (W & 3) == 0 && ((uintptr_t)out & 3) == 0;
     const bool vec4 = K == 4 && (C & 3) == 0 && ((uintptr_t)prob & 15) == 0;
-    const dim3 grid((unsigned)po_blocks(pack ? (long)H * (W >> 2) : (long)H * W), S);
+    const dim3 grid(po_grid(pack ? (long)H * (W >> 2) : (long)H * W, PO_MAXBLK), S);
     const po_axis ar = {lo_r, kept_r, before_r}, ac = {lo_c, kept_c, before_c};
     const hipStream_t st = (hipStream_t)stream;
     if (vec4 && pack) po_launch<true, true>(grid, st, prob, values, K, out, H, W, RH, RW, OH, OW, ar, ac, C, order);
@@ -934,7 +991,7 @@ int mmseg_label_overlap(const unsigned char* pred, const unsigned char* truth, c
         return (int)hipErrorInvalidValue;
     const hipError_t rc = hipMemsetAsync(counts, 0, sizeof(int) * 3 * (size_t)K * S, (hipStream_t)stream);
     if (rc != hipSuccess) return (int)rc;
-    const dim3 grid((unsigned)po_blocks(n), S);
+    const dim3 grid(po_grid(n, PO_MAXBLK), S);
     hipLaunchKernelGGL(po_overlap_kernel, grid, dim3(PO_BLOCK), 0, (hipStream_t)stream, pred, truth, values, K, counts, n);
     return MMSEG_CHECK_LAUNCH();
 }
@@ -944,7 +1001,7 @@ int mmseg_label_overlap(const unsigned char* pred, const unsigned char* truth, c
 int mmseg_label_surface(const unsigned char* label, const int* values, unsigned char* surf, int* counts, int S, int H, int W, int K,
                         void* stream) {
     if (S <= 0) return 0;
-    if (!label || !values || !surf || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES) return (int)hipErrorInvalidValue;
+    if (!label || !values || !surf || !po_problem_ok(S, H, W, K)) return (int)hipErrorInvalidValue;
     return po_surface(label, values, surf, counts, S, H, W, K, (hipStream_t)stream);
 }
 
@@ -952,51 +1009,24 @@ int mmseg_label_surface(const unsigned char* label, const int* values, unsigned 
 int mmseg_distance_to_sites(const unsigned char* sites, double* out, double* tmp, int S, int H, int W, double dz, double dy, double dx,
                             void* stream) {
     if (S <= 0) return 0;
-    if (!sites || !out || !tmp || !po_volume_ok(S, H, W) || !po_spacing_ok(dz) || !po_spacing_ok(dy) || !po_spacing_ok(dx))
-        return (int)hipErrorInvalidValue;
+    if (!sites || !out || !tmp || !po_volume_ok(S, H, W) || !po_spacings_ok(dz, dy, dx)) return (int)hipErrorInvalidValue;
     return po_edt(sites, out, tmp, S, H, W, dz, dy, dx, (hipStream_t)stream);
 }
 
 // doubles of workspace of mmseg_surface_metrics: two distance maps, the partials, the counts and the 2 (K + 1) surface volumes
 long mmseg_surface_metrics_workspace_doubles(int S, int H, int W, int K) {
-    if (S <= 0 || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES) return 0;
-    const long n = (long)S * H * W;
-    return 2 * n + 4 * PO_RED_BLOCKS + po_round8((long)sizeof(int) * 4 * (K + 1)) + po_round8(2 * (long)(K + 1) * n);
+    if (S <= 0 || !po_problem_ok(S, H, W, K)) return 0;
+    return po_walk_carve(nullptr, (long)S * H * W, K, false, nullptr);
 }
 
 // pred, truth [S,H,W] uint8 -> table [K+1,6] fp64 = nP, nT, |surface(P)|, |surface(T)|, sum and max of the surface distances in mm
-// (nan when either surface is empty).  A loop of launches over the K + 1 problems on the stream.
+// (nan when either surface is empty)
 int mmseg_surface_metrics(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
                           int H, int W, int K, double dz, double dy, double dx, void* stream) {
     if (S <= 0) return 0;
-    if (!pred || !truth || !values || !table || !ws || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES || !po_spacing_ok(dz) ||
-        !po_spacing_ok(dy) || !po_spacing_ok(dx))
+    if (!pred || !truth || !values || !table || !ws || !po_problem_ok(S, H, W, K) || !po_spacings_ok(dz, dy, dx))
         return (int)hipErrorInvalidValue;
-    const hipStream_t st = (hipStream_t)stream;
-    const long n = (long)S * H * W;
-    double* da = ws;
-    double* db = da + n;
-    double* part = db + n;
-    int* cp = reinterpret_cast<int*>(part + 4 * PO_RED_BLOCKS);
-    int* ct = cp + 2 * (K + 1);
-    unsigned char* sp = reinterpret_cast<unsigned char*>(reinterpret_cast<double*>(cp) + po_round8((long)sizeof(int) * 4 * (K + 1)));
-    unsigned char* stv = sp + (size_t)(K + 1) * n;
-    int rc = po_surface(pred, values, sp, cp, S, H, W, K, st);
-    if (rc) return rc;
-    rc = po_surface(truth, values, stv, ct, S, H, W, K, st);
-    if (rc) return rc;
-    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    const int nblk = (int)(b < PO_RED_BLOCKS ? b : PO_RED_BLOCKS);
-    for (int k = 0; k <= K; ++k) {
-        rc = po_edt(stv + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);          // distance to surface(T), summed over surface(P)
-        if (rc) return rc;
-        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, sp + (size_t)k * n, da, n, part);
-        rc = po_edt(sp + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
-        hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 6 * k);
-    }
-    return MMSEG_CHECK_LAUNCH();
+    return po_surface_walk(pred, truth, values, table, ws, S, H, W, K, dz, dy, dx, 6, nullptr, (hipStream_t)stream);
 }
 
 // doubles of workspace of mmseg_masked_select: the list (2 n) and the selection's state; 0 for an n that it would refuse
@@ -1027,53 +1057,20 @@ int mmseg_masked_select(const double* a, const unsigned char* ma, const double* 
 
 // doubles of workspace of mmseg_surface_scores: that of mmseg_surface_metrics, then the list (2 S H W) and the selection's state
 long mmseg_surface_scores_workspace_doubles(int S, int H, int W, int K) {
-    const long base = mmseg_surface_metrics_workspace_doubles(S, H, W, K);
-    if (base == 0) return 0;
-    return base + 2 * (long)S * H * W + OS_STATE_DOUBLES;
+    if (S <= 0 || !po_problem_ok(S, H, W, K)) return 0;
+    return po_walk_carve(nullptr, (long)S * H * W, K, true, nullptr);
 }
 
 // pred, truth [S,H,W] uint8 -> table [K+1,8] fp64: the six columns of mmseg_surface_metrics, |{x <= tolerance}| and the percentile of the
-// surface distances of both directions together (nan when either surface is empty).  The walk of mmseg_surface_metrics; every map's
-// surface distances are appended to the problem's list before the next transform overwrites the map.
+// surface distances of both directions together (nan when either surface is empty)
 int mmseg_surface_scores(const unsigned char* pred, const unsigned char* truth, const int* values, double* table, double* ws, int S,
                          int H, int W, int K, double dz, double dy, double dx, double percentile, double tolerance, void* stream) {
     if (S <= 0) return 0;
-    if (!pred || !truth || !values || !table || !ws || !po_volume_ok(S, H, W) || K < 1 || K > PO_MAXVALUES || !po_spacing_ok(dz) ||
-        !po_spacing_ok(dy) || !po_spacing_ok(dx) || !os_args_ok(percentile, tolerance))
+    if (!pred || !truth || !values || !table || !ws || !po_problem_ok(S, H, W, K) || !po_spacings_ok(dz, dy, dx) ||
+        !os_args_ok(percentile, tolerance))
         return (int)hipErrorInvalidValue;
-    const hipStream_t st = (hipStream_t)stream;
-    const long n = (long)S * H * W;
-    double* da = ws;
-    double* db = da + n;
-    double* part = db + n;
-    int* cp = reinterpret_cast<int*>(part + 4 * PO_RED_BLOCKS);
-    int* ct = cp + 2 * (K + 1);
-    unsigned char* sp = reinterpret_cast<unsigned char*>(reinterpret_cast<double*>(cp) + po_round8((long)sizeof(int) * 4 * (K + 1)));
-    unsigned char* stv = sp + (size_t)(K + 1) * n;
-    double* list = ws + mmseg_surface_metrics_workspace_doubles(S, H, W, K);
-    double* state = list + 2 * n;
-    int rc = po_surface(pred, values, sp, cp, S, H, W, K, st);
-    if (rc) return rc;
-    rc = po_surface(truth, values, stv, ct, S, H, W, K, st);
-    if (rc) return rc;
-    const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
-    const int nblk = (int)(b < PO_RED_BLOCKS ? b : PO_RED_BLOCKS);
-    for (int k = 0; k <= K; ++k) {
-        rc = os_reset(state, st);
-        if (rc) return rc;
-        rc = po_edt(stv + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);          // distance to surface(T), over surface(P)
-        if (rc) return rc;
-        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, sp + (size_t)k * n, da, n, part);
-        os_append(da, sp + (size_t)k * n, n, tolerance, list, state, st);
-        rc = po_edt(sp + (size_t)k * n, da, db, S, H, W, dz, dy, dx, st);
-        if (rc) return rc;
-        hipLaunchKernelGGL(po_surface_reduce_kernel, dim3(nblk), dim3(PO_BLOCK), 0, st, stv + (size_t)k * n, da, n, part + 2 * nblk);
-        os_append(da, stv + (size_t)k * n, n, tolerance, list, state, st);
-        hipLaunchKernelGGL(po_surface_final_kernel, dim3(1), dim3(PO_BLOCK), 0, st, cp, ct, part, nblk, k, table + 8 * k);
-        os_select(list, state, 2 * n, percentile, st);
-        hipLaunchKernelGGL(os_row_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const os_state*>(state), cp, ct, k, table + 8 * k);
-    }
-    return MMSEG_CHECK_LAUNCH();
+    const os_args robust = {percentile, tolerance};
+    return po_surface_walk(pred, truth, values, table, ws, S, H, W, K, dz, dy, dx, 8, &robust, (hipStream_t)stream);
 }
 
 // label [S,H,W] uint8, values [K] int32 (device) -> comp [S,H,W] int32, every element written: 0 where the grey value is none of
@@ -1109,7 +1106,7 @@ int mmseg_keep_largest_components(const unsigned char* label, const int* values,
     if (rc != hipSuccess) return (int)rc;
     const int err = po_components(label, values, comp, S, H, W, K, connectivity, st);
     if (err) return err;
-    const dim3 grid(po_cc_blocks(n)), block(PO_BLOCK);
+    const dim3 grid(po_grid(n, CC_MAXBLK)), block(PO_BLOCK);
     hipLaunchKernelGGL(po_cc_size_kernel, grid, block, 0, st, comp, size, n);
     hipLaunchKernelGGL(po_cc_winner_kernel, grid, block, 0, st, label, values, K, comp, size, keys, stats, n);
     hipLaunchKernelGGL(po_cc_keep_kernel, grid, block, 0, st, label, values, K, comp, keys, out, stats, n);

@@ -31,14 +31,14 @@ def _sid(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-def _ws(tag, nfloats, device):
-    """Grow-only scratch buffer per (tag, device, stream).  The kernels of one stream run in order, so a buffer can be handed to the
-    next kernel as soon as the previous launch has been queued."""
+def _ws(tag, n, device, dtype=torch.float32):
+    """Grow-only scratch buffer of at least n elements per (tag, device, stream); a tag keeps to one dtype.  The kernels of one stream
+    run in order, so a buffer can be handed to the next kernel as soon as the previous launch has been queued."""
     key = (tag, device, _sid(device))
     buf = _workspaces.get(key)
-    n = max(int(nfloats), 1)
+    n = max(int(n), 1)
     if buf is None or buf.numel() < n:
-        buf = torch.empty(max(n, 1024), dtype=torch.float32, device=device)
+        buf = torch.empty(max(n, 1024), dtype=dtype, device=device)
         _workspaces[key] = buf
     return buf
 
@@ -1619,17 +1619,6 @@ def label_overlap(pred, truth, values):
     return counts
 
 
-def _ws_f64(tag, ndoubles, device):
-    """_ws for the fp64 scratch of the scores in mm (grow-only, per tag, device and stream)"""
-    key = (tag, device, _sid(device))
-    buf = _workspaces.get(key)
-    n = max(int(ndoubles), 1)
-    if buf is None or buf.numel() < n:
-        buf = torch.empty(n, dtype=torch.float64, device=device)
-        _workspaces[key] = buf
-    return buf
-
-
 def _volume_args(op, label, values, others=()):
     """shared checks of the scores in mm: uint8 [S,H,W] volumes of one shape on one device, values [K] int32, 1 <= K <= 16"""
     K = int(values.numel())
@@ -1669,7 +1658,7 @@ def distance_to_sites(sites, spacing):
     dz, dy, dx = _spacing_args('distance_to_sites', spacing)
     S, H, W = sites.shape
     out = _new((S, H, W), sites, torch.float64)
-    N.call('mmseg_distance_to_sites', _c(sites), out, _ws_f64('edt', sites.numel(), sites.device), S, H, W, dz, dy, dx)
+    N.call('mmseg_distance_to_sites', _c(sites), out, _ws('edt', sites.numel(), sites.device, torch.float64), S, H, W, dz, dy, dx)
     return out
 
 
@@ -1678,16 +1667,7 @@ def surface_metrics(pred, truth, values, spacing):
     problem (the K organs, then their union): nP, nT, |surface(P)|, |surface(T)|, the sum and the maximum over both surfaces of the
     distance in mm to the other surface; the last two are nan when either surface is empty (csrc/postprocess.hip).  RAVD, ASSD and
     MSSD follow on the host (volume_predictor.chaos_from_table)."""
-    K = _volume_args('surface_metrics', pred, values, (truth,))
-    dz, dy, dx = _spacing_args('surface_metrics', spacing)
-    S, H, W = pred.shape
-    table = torch.zeros((K + 1, 6), dtype=torch.float64, device=pred.device)
-    if S == 0:
-        table[:, 4:] = float('nan')
-        return table
-    ws = _ws_f64('surface_metrics', N.call('mmseg_surface_metrics_workspace_doubles', S, H, W, K), pred.device)
-    N.call('mmseg_surface_metrics', _c(pred), _c(truth), values, table, ws, S, H, W, K, dz, dy, dx)
-    return table
+    return _surface_table('surface_metrics', pred, truth, values, spacing)
 
 
 def _robust_args(op, percentile, tolerance):
@@ -1697,6 +1677,22 @@ def _robust_args(op, percentile, tolerance):
     if not 0.0 <= tau < float('inf'):
         raise ValueError('%s: tolerance must be a finite number of mm >= 0, got %r' % (op, tolerance))
     return q, tau
+
+
+def _surface_table(op, pred, truth, values, spacing, robust=None):
+    """the body of surface_metrics (robust None -> [K+1,6]) and of surface_scores (robust = (percentile, tolerance) -> [K+1,8]); `op`
+    names the C entry point mmseg_<op>, its workspace query and the errors.  Both share one scratch buffer, which the larger sizes."""
+    K = _volume_args(op, pred, values, (truth,))
+    dz, dy, dx = _spacing_args(op, spacing)
+    extra = () if robust is None else _robust_args(op, *robust)
+    S, H, W = pred.shape
+    table = torch.zeros((K + 1, 6 + len(extra)), dtype=torch.float64, device=pred.device)
+    if S == 0:
+        table[:, 4:] = float('nan')
+        return table
+    ws = _ws('surface_metrics', N.call('mmseg_%s_workspace_doubles' % op, S, H, W, K), pred.device, torch.float64)
+    N.call('mmseg_' + op, _c(pred), _c(truth), values, table, ws, S, H, W, K, dz, dy, dx, *extra)
+    return table
 
 
 def masked_select(a, ma, b, mb, percentile, tolerance):
@@ -1715,7 +1711,7 @@ def masked_select(a, ma, b, mb, percentile, tolerance):
     if n == 0:          # empty tensors have no storage to point at
         out[2:] = float('nan')
         return out
-    ws = _ws_f64('masked_select', N.call('mmseg_masked_select_workspace_doubles', n), a.device)
+    ws = _ws('masked_select', N.call('mmseg_masked_select_workspace_doubles', n), a.device, torch.float64)
     N.call('mmseg_masked_select', _c(a), _c(ma), _c(b), _c(mb), n, q, tau, out, ws)
     return out
 
@@ -1725,28 +1721,7 @@ def surface_scores(pred, truth, values, spacing, percentile=95.0, tolerance=1.0)
     surface_metrics), then |{x in D : x <= tolerance}| and numpy.percentile(D, percentile), where D holds the distances in mm of
     surface(P) to surface(T) and of surface(T) to surface(P) together; columns 5 to 8 are nan when either surface is empty.  Every
     distance transform runs once.  HD(q) and NSD(tau) follow on the host (volume_predictor.robust_from_table)."""
-    K = _volume_args('surface_scores', pred, values, (truth,))
-    dz, dy, dx = _spacing_args('surface_scores', spacing)
-    q, tau = _robust_args('surface_scores', percentile, tolerance)
-    S, H, W = pred.shape
-    table = torch.zeros((K + 1, 8), dtype=torch.float64, device=pred.device)
-    if S == 0:
-        table[:, 4:] = float('nan')
-        return table
-    ws = _ws_f64('surface_metrics', N.call('mmseg_surface_scores_workspace_doubles', S, H, W, K), pred.device)
-    N.call('mmseg_surface_scores', _c(pred), _c(truth), values, table, ws, S, H, W, K, dz, dy, dx, q, tau)
-    return table
-
-
-def _ws_i32(tag, nbytes, device):
-    """_ws_f64 for the int32 scratch of the component filter (grow-only, per tag, device and stream)"""
-    key = (tag, device, _sid(device))
-    buf = _workspaces.get(key)
-    n = max((int(nbytes) + 3) // 4, 1)
-    if buf is None or buf.numel() < n:
-        buf = torch.empty(n, dtype=torch.int32, device=device)
-        _workspaces[key] = buf
-    return buf
+    return _surface_table('surface_scores', pred, truth, values, spacing, (percentile, tolerance))
 
 
 def _component_args(op, label, values, connectivity):
@@ -1776,7 +1751,7 @@ def keep_largest_components(label, values, connectivity=6):
     out = _new((S, H, W), label, torch.uint8)
     stats = torch.zeros((K, 3), dtype=torch.int32, device=label.device)
     if S:
-        ws = _ws_i32('keep_largest', N.call('mmseg_keep_largest_workspace_bytes', S, H, W, K), label.device)
+        ws = _ws('keep_largest', (N.call('mmseg_keep_largest_workspace_bytes', S, H, W, K) + 3) // 4, label.device, torch.int32)
         N.call('mmseg_keep_largest_components', _c(label), values, out, stats, ws, S, H, W, K, int(connectivity))
     return out, stats
 

@@ -32,7 +32,7 @@ INTEGRATION.md section 5) are taken on the whole file grid [S_file,H,W]: the pre
 device, the truth slices that `slices` does not select are zero, and ops.surface_metrics returns one [K+1,6] table per volume, the only
 thing that leaves the device.  With robust=(percentile, tolerance) (build-defined, off by default; HD(q) and NSD(tau) of INTEGRATION.md
 section 5) ops.surface_scores takes its place: the same table with two more columns, from the same distance transforms, so that one
-call serves both CSV files.  `score_volume` and `write_scores` are shared with tools/score_predictions.py, which scores label
+call serves both CSV files.  `score_volume` and `ScoreSheet` are shared with tools/score_predictions.py, which scores label
 volumes written earlier (`score_folder`)."""
 import json
 import logging
@@ -82,18 +82,14 @@ def chaos_from_table(table):
 
 
 def check_robust(robust):
-    """robust: None or (percentile in [0, 100], tolerance in mm >= 0) -> None or the pair as floats"""
+    """robust: None or (percentile in [0, 100], tolerance in mm >= 0) -> None or the pair as floats (the ranges are those of the op)"""
     if robust is None:
         return None
     try:
         q, tau = (float(v) for v in robust)
     except (TypeError, ValueError):
         raise ValueError('robust must be None or (percentile, tolerance in mm), got %r' % (robust,))
-    if not 0.0 <= q <= 100.0:
-        raise ValueError('robust: the percentile must lie in [0, 100], got %r' % (robust[0],))
-    if not 0.0 <= tau < float('inf'):
-        raise ValueError('robust: the tolerance must be a finite number of mm >= 0, got %r' % (robust[1],))
-    return q, tau
+    return ops._robust_args('robust', q, tau)
 
 
 def robust_from_table(table):
@@ -107,23 +103,27 @@ def robust_from_table(table):
     return out
 
 
+def _on_file_grid(x, geometry):
+    """x: uint8 [S,H,W] on the device, the selected slices of one file in order -> (x on the zero file grid [S_file,H,W], its positions)"""
+    where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=x.device)
+    grid = tuple(int(n) for n in geometry['raw_shape'])
+    return torch.zeros(grid, dtype=torch.uint8, device=x.device).index_copy_(0, where, x), where
+
+
 def score_volume(pred, label, values, geometry, surface=True, robust=None):
     """pred, label: uint8 [S,H,W] on the device, the selected slices of one file in order; geometry: the record of
     loader.load_volume_for_prediction (raw_shape, slices, resolution, slice_spacing are read) -> (joint Dice, [per organ], scores in
-    mm [K+1,3] with the union LAST, or None when they are not asked for or the file holds no slice_spacing).  With robust =
-    (percentile, tolerance in mm) a fourth item follows: [K+1,2] = HD, NSD with the union last, or None for a file without
-    slice_spacing; both tables then come from one ops.surface_scores call."""
+    mm [K+1,3], HD and NSD [K+1,2]), the tables with the union LAST.  The third is None when surface is off, the fourth without robust =
+    (percentile, tolerance in mm), both for a file without slice_spacing; otherwise both come from one ops.surface_scores call."""
     robust = check_robust(robust)
     joint, per_organ = dice_from_counts(nn.to_numpy(ops.label_overlap(pred, label, values)))
     if (not surface and robust is None) or geometry.get('slice_spacing') is None:
-        return (joint, per_organ, None) if robust is None else (joint, per_organ, None, None)
-    where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=pred.device)
-    grid = tuple(int(n) for n in geometry['raw_shape'])
-    on_grid = [torch.zeros(grid, dtype=torch.uint8, device=pred.device).index_copy_(0, where, x) for x in (pred, label)]
+        return joint, per_organ, None, None
+    on_grid = [_on_file_grid(x, geometry)[0] for x in (pred, label)]
     spacing = (float(geometry['slice_spacing']), float(geometry['resolution'][0]), float(geometry['resolution'][1]))
     if robust is None:
         table = ops.surface_metrics(on_grid[0], on_grid[1], values, spacing)
-        return joint, per_organ, chaos_from_table(nn.to_numpy(table))
+        return joint, per_organ, chaos_from_table(nn.to_numpy(table)), None
     table = nn.to_numpy(ops.surface_scores(on_grid[0], on_grid[1], values, spacing, robust[0], robust[1]))
     return joint, per_organ, (chaos_from_table(table[:, :6]) if surface else None), robust_from_table(table)
 
@@ -142,66 +142,72 @@ def keep_largest(pred, values, geometry, connectivity=6):
     """pred: uint8 [S,H,W] on the device, the selected slices of one file in order -> (the same slices after the filter, stats [K,3]
     on the device).  The filter runs on the file grid [S_file,H,W] (unselected slices are zero), so that two voxels are neighbours
     along the slice axis when they are in the file."""
-    where = torch.as_tensor(np.asarray(geometry['slices'], np.int64), device=pred.device)
-    grid = tuple(int(n) for n in geometry['raw_shape'])
-    on_grid = torch.zeros(grid, dtype=torch.uint8, device=pred.device).index_copy_(0, where, pred)
+    on_grid, where = _on_file_grid(pred, geometry)
     kept, stats = ops.keep_largest_components(on_grid, values, connectivity)
     return kept.index_select(0, where), stats
 
 
-def write_component_results(path, rows, num_masks):
-    """rows: (volume, stats [K,3]) -> Vol, N0, Before0, Kept0, N1, ..."""
-    cols = ['Vol'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('N', 'Before', 'Kept')]
+def _write_table(path, rows, names, num_masks, fmt, union_first):
+    """rows: (volume, one row of len(names) values per organ, then with union_first the union's) -> Vol, [names,] names of organ 0, ..."""
+    cols = ['Vol'] + list(names if union_first else ()) + ['%s%d' % (name, k) for k in range(num_masks) for name in names]
     with open(path, 'w') as f:
         f.write(', '.join(cols) + '\n')
-        for vol, stats in rows:
-            f.write(', '.join([str(vol)] + ['%d' % v for v in np.asarray(stats).reshape(-1)]) + '\n')
+        for vol, table in rows:
+            table = np.asarray(table)
+            if union_first:
+                table = np.concatenate([table[-1:], table[:-1]], axis=0)
+            f.write(', '.join([str(vol)] + [fmt % v for v in table.reshape(-1)]) + '\n')
+
+
+def write_component_results(path, rows, num_masks):
+    """rows: (volume, stats [K,3]) -> Vol, N0, Before0, Kept0, N1, ..."""
+    _write_table(path, rows, ('N', 'Before', 'Kept'), num_masks, '%d', False)
 
 
 def write_surface_results(path, rows, num_masks):
     """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
-    cols = ['Vol', 'RAVD', 'ASSD', 'MSSD'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('RAVD', 'ASSD', 'MSSD')]
-    with open(path, 'w') as f:
-        f.write(', '.join(cols) + '\n')
-        for vol, scores in rows:
-            ordered = np.concatenate([scores[-1:], scores[:-1]], axis=0).reshape(-1)
-            f.write(', '.join([str(vol)] + ['%.3f' % v for v in ordered]) + '\n')
+    _write_table(path, rows, ('RAVD', 'ASSD', 'MSSD'), num_masks, '%.3f', True)
 
 
 def write_robust_results(path, rows, num_masks):
     """rows: (volume, [K+1,2] with the union last) -> Vol, HD, NSD, HD0, NSD0, ...: the union first"""
-    cols = ['Vol', 'HD', 'NSD'] + ['%s%d' % (name, k) for k in range(num_masks) for name in ('HD', 'NSD')]
-    with open(path, 'w') as f:
-        f.write(', '.join(cols) + '\n')
-        for vol, scores in rows:
-            ordered = np.concatenate([scores[-1:], scores[:-1]], axis=0).reshape(-1)
-            f.write(', '.join([str(vol)] + ['%.3f' % v for v in ordered]) + '\n')
+    _write_table(path, rows, ('HD', 'NSD'), num_masks, '%.3f', True)
 
 
-def write_scores(out_folder, modalities, rows, surface_rows, num_masks, robust_rows=None):
-    """results_native_<modality>.csv / results_surface_<modality>.csv / results_robust_<modality>.csv for the modalities that have rows"""
-    for m, name in enumerate(modalities):
-        if rows[m]:
-            write_results(os.path.join(out_folder, 'results_native_%s.csv' % name), rows[m], num_masks)
-        if surface_rows[m]:
-            write_surface_results(os.path.join(out_folder, 'results_surface_%s.csv' % name), surface_rows[m], num_masks)
-        if robust_rows and robust_rows[m]:
-            write_robust_results(os.path.join(out_folder, 'results_robust_%s.csv' % name), robust_rows[m], num_masks)
+class ScoreSheet(object):
+    """the rows of one run's results_<kind>_<modality>.csv files: rows[kind][m] holds those of modality m; `scores` is score_volume's"""
+    WRITERS = (('native', write_results), ('surface', write_surface_results), ('robust', write_robust_results),
+               ('components', write_component_results))
 
+    def __init__(self, modalities, num_masks, in_mm):
+        self.modalities, self.num_masks, self.in_mm = list(modalities), num_masks, in_mm
+        self.rows = {kind: [[] for _ in self.modalities] for kind, _ in self.WRITERS}
 
-def collect_scores(rows, surface_rows, m, volume, modality, scores, geometry, surface, robust_rows=None):
-    joint, per_organ, in_mm = scores[:3]
-    robust = scores[3] if robust_rows is not None else None
-    rows[m].append((volume, joint, per_organ))
-    log.info('volume %s, %s: Dice on the raw grid %.3f' % (volume, modality, joint))
-    if in_mm is not None:
-        surface_rows[m].append((volume, in_mm))
-        log.info('volume %s, %s: RAVD %.3f %%, ASSD %.3f mm, MSSD %.3f mm' % ((volume, modality) + tuple(in_mm[-1])))
-    if robust is not None:
-        robust_rows[m].append((volume, robust))
-        log.info('volume %s, %s: HD %.3f mm, NSD %.3f' % ((volume, modality) + tuple(robust[-1])))
-    if geometry.get('slice_spacing') is None and (surface or robust_rows is not None):
-        log.info("volume %s, %s: %s holds no 'slice_spacing', so no scores in mm" % (volume, modality, geometry['file']))
+    def add(self, m, volume, scores, geometry):
+        modality, (joint, per_organ, in_mm, robust) = self.modalities[m], scores
+        self.rows['native'][m].append((volume, joint, per_organ))
+        log.info('volume %s, %s: Dice on the raw grid %.3f' % (volume, modality, joint))
+        if in_mm is not None:
+            self.rows['surface'][m].append((volume, in_mm))
+            log.info('volume %s, %s: RAVD %.3f %%, ASSD %.3f mm, MSSD %.3f mm' % ((volume, modality) + tuple(in_mm[-1])))
+        if robust is not None:
+            self.rows['robust'][m].append((volume, robust))
+            log.info('volume %s, %s: HD %.3f mm, NSD %.3f' % ((volume, modality) + tuple(robust[-1])))
+        if geometry.get('slice_spacing') is None and self.in_mm:          # scores in mm were asked for
+            log.info("volume %s, %s: %s holds no 'slice_spacing', so no scores in mm" % (volume, modality, geometry['file']))
+
+    def add_components(self, m, volume, stats):
+        self.rows['components'][m].append((volume, nn.to_numpy(stats)))
+
+    def write(self, out_folder):
+        """one file per kind and modality that has rows"""
+        for kind, writer in self.WRITERS:
+            for m, name in enumerate(self.modalities):
+                if self.rows[kind][m]:
+                    writer(os.path.join(out_folder, 'results_%s_%s.csv' % (kind, name)), self.rows[kind][m], self.num_masks)
+
+    def by_name(self, kind):
+        return {name: self.rows[kind][m] for m, name in enumerate(self.modalities)}
 
 
 def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6, robust=None):
@@ -223,8 +229,7 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
         volumes = [v for i, v in enumerate(listed) if v not in listed[:i] and v in loader.manifest['volumes']]
     device = nn.default_device()
     values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
-    rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
-    robust_rows = None if robust is None else [[] for _ in loader.modalities]
+    sheet = ScoreSheet(loader.modalities, loader.num_masks, surface or robust is not None)
     for v in volumes:
         for m, mod in enumerate(loader.modalities):
             entry = loader.manifest['volumes'][v][mod]
@@ -246,12 +251,9 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
                 pred, _ = keep_largest(pred, values, geo, connectivity)
             scores = score_volume(pred, nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface,
                                   robust)
-            collect_scores(rows, surface_rows, m, v, mod, scores, geo, surface, robust_rows)
-    write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks, robust_rows)
-    by_name = [{name: table[m] for m, name in enumerate(loader.modalities)} for table in (rows, surface_rows)]
-    if robust is None:
-        return by_name[0], by_name[1]
-    return by_name[0], by_name[1], {name: robust_rows[m] for m, name in enumerate(loader.modalities)}
+            sheet.add(m, v, scores, geo)
+    sheet.write(out_folder)
+    return tuple(sheet.by_name(kind) for kind in (('native', 'surface') if robust is None else ('native', 'surface', 'robust')))
 
 
 class VolumePredictor(object):
@@ -288,9 +290,7 @@ class VolumePredictor(object):
         os.makedirs(out_folder, exist_ok=True)
         device = nn.default_device()
         values = nn.host_to_device(np.asarray(loader.label_values), device, np.int32)
-        rows, surface_rows = [[] for _ in loader.modalities], [[] for _ in loader.modalities]
-        component_rows = [[] for _ in loader.modalities]
-        robust_rows = None if robust is None else [[] for _ in loader.modalities]
+        sheet = ScoreSheet(loader.modalities, loader.num_masks, surface or robust is not None)
         files = {}
         for v in volumes:
             images, geometry = loader.load_volume_for_prediction(v)
@@ -299,19 +299,16 @@ class VolumePredictor(object):
                 pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
                 if components:
                     pred, stats = keep_largest(pred, values, geo, connectivity)
-                    component_rows[m].append((v, nn.to_numpy(stats)))
+                    sheet.add_components(m, v, stats)
                 if geo['label'] is not None:
                     scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface, robust)
-                    collect_scores(rows, surface_rows, m, v, loader.modalities[m], scores, geo, surface, robust_rows)
+                    sheet.add(m, v, scores, geo)
                 label = np.zeros(geo['raw_shape'], np.uint8)
                 label[geo['slices']] = pred.cpu().numpy()
                 extra = {} if geo['slice_spacing'] is None else dict(slice_spacing=float(geo['slice_spacing']))
                 np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
                 files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
-        write_scores(out_folder, loader.modalities, rows, surface_rows, loader.num_masks, robust_rows)
-        for m, name in enumerate(loader.modalities):
-            if component_rows[m]:
-                write_component_results(os.path.join(out_folder, 'results_components_%s.csv' % name), component_rows[m], loader.num_masks)
+        sheet.write(out_folder)
         settings = dict(source_folder=folder, mode=mode, order=order, model_folder=self.conf.get('folder'),
                         label_values=loader.label_values, files=files)
         if components:
@@ -320,4 +317,4 @@ class VolumePredictor(object):
             settings.update(percentile=robust[0], tolerance_mm=robust[1])
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
-        return {name: rows[m] for m, name in enumerate(loader.modalities)}
+        return sheet.by_name('native')

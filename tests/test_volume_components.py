@@ -14,13 +14,12 @@ import numpy as np
 import pytest
 import torch
 
-from multimodal_segmentation_amd import loaders, nn
 from tests import volume_components_ref as C
 from tests import volume_loader_ref as R
 from tests import volume_metrics_ref as M
-from tests import volume_predict_ref as P
 from tests.test_volume_loader import VALUES
 from tests.test_volume_metrics import CASES, OTHER_GREY, _case_data
+from tests.volume_fixtures import _clean_registry, _csv_rows, _dev, _score_tool, _up, device  # noqa: F401
 
 CONNECTIVITIES = (6, 26)
 KNOWN_SHAPES = ((12, 53, 47), (3, 37, 41))          # no tile size divides them
@@ -43,38 +42,6 @@ def _reference(name, connectivity):
     for a in (comp, out, stats):
         a.setflags(write=False)
     return comp, out, stats
-
-
-@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
-def device(request, monkeypatch):
-    if request.param == 'cpu':
-        from tests import cpu_backend as cb
-        for table in (R.STANDINS, P.STANDINS, M.STANDINS, C.STANDINS):
-            for name, fn in table.items():
-                monkeypatch.setitem(cb._TABLE, name, fn)
-        cb.install()
-        nn.set_default_device('cpu')
-        yield 'cpu'
-        cb.uninstall()
-    else:
-        nn.set_default_device('cuda:0')
-        yield 'cuda'
-
-
-@pytest.fixture(autouse=True)
-def _clean_registry():
-    saved = dict(loaders.data_conf)
-    yield
-    loaders.data_conf.clear()
-    loaders.data_conf.update(saved)
-
-
-def _dev(device):
-    return 'cuda:0' if device == 'cuda' else 'cpu'
-
-
-def _up(a, dev, dtype=np.uint8):
-    return nn.host_to_device(np.array(a), dev, dtype)
 
 
 def _run(volume, values, connectivity, dev):
@@ -301,19 +268,6 @@ def folder(tmp_path):
             arrays['label'] = C.keep_largest(arrays['label'], VALUES, 6)[0]
             np.savez_compressed(os.path.join(out, e['file']), **arrays)
     return out
-
-
-def _score_tool():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location('score_predictions', os.path.join(R.ROOT, 'tools', 'score_predictions.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _csv_rows(path):
-    lines = open(path).read().strip().split('\n')
-    return lines[0], {l.split(', ')[0]: l.split(', ')[1:] for l in lines[1:]}
 
 
 def _file_contents(path):

@@ -13,6 +13,7 @@ from multimodal_segmentation_amd.loaders import loader_factory
 from multimodal_segmentation_amd.utils import data_utils
 from tests import helpers as Hh
 from tests import volume_loader_ref as R
+from tests.volume_fixtures import _clean_registry, device  # noqa: F401
 
 TARGET = (1.89, 1.89)
 VALUES = [63, 126, 189, 252]
@@ -75,29 +76,6 @@ def standin(monkeypatch):
     nn.set_default_device('cpu')
     yield cb
     cb.uninstall()
-
-
-@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
-def device(request, monkeypatch):
-    if request.param == 'cpu':
-        from tests import cpu_backend as cb
-        for name, fn in R.STANDINS.items():
-            monkeypatch.setitem(cb._TABLE, name, fn)
-        cb.install()
-        nn.set_default_device('cpu')
-        yield 'cpu'
-        cb.uninstall()
-    else:
-        nn.set_default_device('cuda:0')
-        yield 'cuda'
-
-
-@pytest.fixture(autouse=True)
-def _clean_registry():
-    saved = dict(loaders.data_conf)
-    yield
-    loaders.data_conf.clear()
-    loaders.data_conf.update(saved)
 
 
 @pytest.fixture

@@ -7,7 +7,6 @@ Comparison rules (set by the feature's issue).  Surfaces and counts are integers
 sides take the square root of a sum of three fp64 squares of the same index differences, a few ulp apart, so 1e-12 relative per voxel and
 exactly 0 at the sites; the same bar for the maximum.  The sum: at most about 1e6 fp64 terms in another order give at most n * 2^-53,
 about 1e-10; the bar sits ten times above that, 1e-9 relative.  Two runs are bitwise equal."""
-import importlib.util
 import json
 import os
 
@@ -15,12 +14,11 @@ import numpy as np
 import pytest
 import torch
 
-from multimodal_segmentation_amd import loaders, nn
 from tests import helpers as Hh
 from tests import volume_loader_ref as R
 from tests import volume_metrics_ref as M
-from tests import volume_predict_ref as P
 from tests.test_volume_loader import VALUES
+from tests.volume_fixtures import _clean_registry, _csv_rows, _dev, _score_tool, _up, device  # noqa: F401
 
 REL_DISTANCE = 1e-12
 REL_SUM = 1e-9
@@ -50,38 +48,6 @@ def _case_data(name):
     values = VALUES[:K]
     grey = np.asarray([0] + values + [OTHER_GREY] * (classes - K - 1), np.uint8)
     return grey[np.argmax(f + 0.35 * g, axis=-1)], grey[np.argmax(f, axis=-1)], values, spacing
-
-
-@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
-def device(request, monkeypatch):
-    if request.param == 'cpu':
-        from tests import cpu_backend as cb
-        for table in (R.STANDINS, P.STANDINS, M.STANDINS):
-            for name, fn in table.items():
-                monkeypatch.setitem(cb._TABLE, name, fn)
-        cb.install()
-        nn.set_default_device('cpu')
-        yield 'cpu'
-        cb.uninstall()
-    else:
-        nn.set_default_device('cuda:0')
-        yield 'cuda'
-
-
-@pytest.fixture(autouse=True)
-def _clean_registry():
-    saved = dict(loaders.data_conf)
-    yield
-    loaders.data_conf.clear()
-    loaders.data_conf.update(saved)
-
-
-def _dev(device):
-    return 'cuda:0' if device == 'cuda' else 'cpu'
-
-
-def _up(a, dev, dtype=np.uint8):
-    return nn.host_to_device(np.ascontiguousarray(a), dev, dtype)
 
 
 def _rel(got, want):
@@ -334,18 +300,6 @@ def test_loader_reads_slice_spacing(folder, plain_folder, device):
 
 
 # ---- 9: end to end -------------------------------------------------------------------------------------------------------------------------
-def _score_tool():
-    spec = importlib.util.spec_from_file_location('score_predictions', os.path.join(R.ROOT, 'tools', 'score_predictions.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _surface_rows(path):
-    lines = open(path).read().strip().split('\n')
-    return lines[0], {l.split(', ')[0]: l.split(', ')[1:] for l in lines[1:]}
-
-
 def test_predictor_scores_in_mm(folder, plain_folder, tmp_path, device):
     from multimodal_segmentation_amd.loaders.volume_folder import VolumeFolderLoader
     from multimodal_segmentation_amd.volume_predictor import VolumePredictor
@@ -368,8 +322,8 @@ def test_predictor_scores_in_mm(folder, plain_folder, tmp_path, device):
     written = json.load(open(os.path.join(out, 'predictions.json')))
     header = 'Vol, RAVD, ASSD, MSSD, ' + ', '.join('%s%d' % (n, k) for k in range(K) for n in ('RAVD', 'ASSD', 'MSSD'))
     for mod in ('t1', 't2'):
-        head, rows = _surface_rows(os.path.join(out, 'results_surface_%s.csv' % mod))
-        _, rolled = _surface_rows(os.path.join(out_rolled, 'results_surface_%s.csv' % mod))
+        head, rows = _csv_rows(os.path.join(out, 'results_surface_%s.csv' % mod))
+        _, rolled = _csv_rows(os.path.join(out_rolled, 'results_surface_%s.csv' % mod))
         assert head == header and len(head.split(', ')) == 3 * (K + 1) + 1
         assert list(rows) == ['1', '2', '3', '4'] and all(len(r) == 3 * (K + 1) for r in rows.values())
         for v in ('1', '2', '3', '4'):

@@ -13,11 +13,12 @@ import pytest
 import torch
 from scipy import ndimage as ndi
 
-from multimodal_segmentation_amd import loaders, nn
+from multimodal_segmentation_amd import nn
 from tests import helpers as Hh
 from tests import volume_loader_ref as R
 from tests import volume_predict_ref as P
 from tests.test_volume_loader import SCENARIOS, TARGET, VALUES
+from tests.volume_fixtures import device, _clean_registry  # noqa: F401
 
 S = 3
 
@@ -52,30 +53,6 @@ def _case_data(name):
     e = np.exp(f - f.max(-1, keepdims=True))
     prob = (e / e.sum(-1, keepdims=True)).astype(np.float32)
     return prob, VALUES[:K], (H, W), _geometry(H, W, res, out_hw)
-
-
-@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
-def device(request, monkeypatch):
-    if request.param == 'cpu':
-        from tests import cpu_backend as cb
-        for table in (R.STANDINS, P.STANDINS):
-            for name, fn in table.items():
-                monkeypatch.setitem(cb._TABLE, name, fn)
-        cb.install()
-        nn.set_default_device('cpu')
-        yield 'cpu'
-        cb.uninstall()
-    else:
-        nn.set_default_device('cuda:0')
-        yield 'cuda'
-
-
-@pytest.fixture(autouse=True)
-def _clean_registry():
-    saved = dict(loaders.data_conf)
-    yield
-    loaders.data_conf.clear()
-    loaders.data_conf.update(saved)
 
 
 # ---- the test inputs (no GPU) ----------------------------------------------------------------------------------------------------------

@@ -21,14 +21,12 @@ import numpy as np
 import pytest
 import torch
 
-from multimodal_segmentation_amd import loaders, nn
-from tests import volume_components_ref as C
 from tests import volume_loader_ref as R
 from tests import volume_metrics_ref as M
-from tests import volume_predict_ref as P
 from tests import volume_robust_ref as B
 from tests.test_volume_loader import VALUES
 from tests.test_volume_metrics import CASES, REL_DISTANCE, _case_data
+from tests.volume_fixtures import _clean_registry, _csv_rows, _dev, _score_tool, _up, device  # noqa: F401
 
 Q, TAU = 95.0, 2.0
 COMBINED = ('7x40x36', 'one-slice', 'odd-45x38', 'k2', 'other-grey', '24x160x144')
@@ -36,38 +34,6 @@ LENGTHS = (1, 2, 63, 64, 65, 257, 200003)
 WRAP = 512 * 256          # elements one sweep of the grid covers
 PERCENTILES = (0.0, 50.0, 95.0, 99.9, 100.0)
 CONTENTS = ('uniform', 'equal', 'lowest-bit', 'exponent', 'zeros', 'only-a', 'only-b', 'none', 'one-each')
-
-
-@pytest.fixture(params=[pytest.param('cpu', id='cpu-standin'), pytest.param('cuda', marks=pytest.mark.gpu, id='mi355x')])
-def device(request, monkeypatch):
-    if request.param == 'cpu':
-        from tests import cpu_backend as cb
-        for table in (R.STANDINS, P.STANDINS, M.STANDINS, C.STANDINS, B.STANDINS):
-            for name, fn in table.items():
-                monkeypatch.setitem(cb._TABLE, name, fn)
-        cb.install()
-        nn.set_default_device('cpu')
-        yield 'cpu'
-        cb.uninstall()
-    else:
-        nn.set_default_device('cuda:0')
-        yield 'cuda'
-
-
-@pytest.fixture(autouse=True)
-def _clean_registry():
-    saved = dict(loaders.data_conf)
-    yield
-    loaders.data_conf.clear()
-    loaders.data_conf.update(saved)
-
-
-def _dev(device):
-    return 'cuda:0' if device == 'cuda' else 'cpu'
-
-
-def _up(a, dev, dtype=np.uint8):
-    return nn.host_to_device(np.ascontiguousarray(a), dev, dtype)
 
 
 def _bits(x):
@@ -350,18 +316,6 @@ def folder(tmp_path):
     out = str(tmp_path / 'volumes')
     R.tool().write_folder(out, volumes=4, size=64, slices=4, seed=3, slice_spacing=(4.0, 9.0))
     return out
-
-
-def _score_tool():
-    spec = importlib.util.spec_from_file_location('score_predictions', os.path.join(R.ROOT, 'tools', 'score_predictions.py'))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _csv_rows(path):
-    lines = open(path).read().strip().split('\n')
-    return lines[0], {l.split(', ')[0]: l.split(', ')[1:] for l in lines[1:]}
 
 
 def _model(loader, dev, islands=False):
