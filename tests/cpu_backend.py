@@ -268,7 +268,11 @@ def maxpool2_bwd_add_t(x, y, dy, add, dx, B, H, W, C, h):
 
 
 def sum_n_t(p0, p1, p2, p3, p4, p5, p6, p7, n, out, numel, h):
+    if n < 1 or n > 8 or numel < 0 or h not in (0, 1, 2):      # the library's own argument checks (csrc/act16.hip)
+        return 1
     ps = [p0, p1, p2, p3, p4, p5, p6, p7][:n]
+    if any(q is None for q in ps):
+        return 1
     acc = ps[0].reshape(-1).float().clone()
     for q in ps[1:]:
         acc += q.reshape(-1).float()
@@ -276,6 +280,8 @@ def sum_n_t(p0, p1, p2, p3, p4, p5, p6, p7, n, out, numel, h):
 
 
 def cat_words(p0, p1, p2, p3, p4, p5, p6, p7, n, out, words):
+    if n < 1 or n > 8 or words < 0:
+        return 1
     ps = [p0, p1, p2, p3, p4, p5, p6, p7][:n]
     B = out.shape[0] // n
     for k, q in enumerate(ps):
@@ -287,10 +293,16 @@ def cat_words(p0, p1, p2, p3, p4, p5, p6, p7, n, out, words):
 
 
 def gather_rows(src, idx, out, rows, words, src_rows):
+    if rows < 0 or words < 0:
+        return 1
+    if rows == 0 or words == 0:
+        return 0
     out.copy_(src.index_select(0, idx.long()).reshape(out.shape)); return 0
 
 
 def add_residual(msk, out, M, C):
+    if C < 1:
+        return 1
     m = msk.reshape(M, C)
     res = 1.0 - (m == 1).any(-1, keepdim=True).to(m.dtype)
     out.copy_(torch.cat([m, res], -1).reshape(out.shape)); return 0

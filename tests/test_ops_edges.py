@@ -13,9 +13,17 @@ inputs, and the id or the comment of a case gives the arithmetic it exercises, r
                       act_bwd / axpby: float4 body + a scalar tail of n % 4 run by one thread.
   csrc/optim.hip      spectral penalty: 32 K slices of kper = ceil(K / 32), column blocks of 256, one block of 1024 threads
                       normalises, gradient on min(4096, ceil(n / 256)) blocks (2048 in the batched launch).
+  csrc/act16.hip      batch plumbing (last section): grid16(n) = min(4096, ceil(n / 256)) blocks of 256, so a grid-stride loop wraps
+                      above 1 048 576 work items.  sum_n_kernel: grid16(numel / 4 + 1), groups of four elements + a scalar tail of
+                      numel % 4 run by one thread, at most 8 operands per launch (ops._sum_n chains launches).  cat_words_kernel:
+                      grid16(words / 4 + 1); per part 16-byte copies + a scalar tail of words % 4 when source AND destination are
+                      16-byte aligned, else one 4-byte word per thread; at most 8 parts per launch.  gather_rows_kernel: grid
+                      (min(1024, ceil(words / 4 / 256)), min(4096, rows)), 16-byte copies when words % 4 == 0.  add_residual_kernel:
+                      grid16(M), one row per thread.
 
 Tolerances: those of the neighbouring tests (RTOL = 2e-4 of the tensor's largest magnitude for values and gradients, 1e-4 / 1e-5
-for the spectral loss / gradient), exact equality where an op only moves or selects data.
+for the spectral loss / gradient), exact equality where an op only moves or selects data (and for the fp32 sums of sum_n_kernel, which
+are left-to-right additions that plain torch repeats bit for bit).
   case                          | tolerance | differs from the neighbour
   ------------------------------+-----------+---------------------------
   (none)                        |           | no case needed another tolerance
@@ -357,3 +365,240 @@ def test_spectral_reg_multi_boundaries(members, device):
         _close(g - 0.5, c[3], 'grad', 1e-5)
         assert torch.equal(g.cpu()[c[0] == 0], torch.full((int((c[0] == 0).sum()),), 0.5)), 'a weight that is 0 adds exactly 0'
         assert torch.count_nonzero((g.cpu() - 0.5)[c[0] != 0]) == (c[0] != 0).sum()
+
+
+# ======================================================================================================================
+# batch plumbing of csrc/act16.hip: sums of fan-out gradients, batch concatenation, row gather, background channel
+# ======================================================================================================================
+# Where the code differs from the plan these cases were drawn up from: ops._cat_words hands the second launch of more than 8 parts the
+# destination out[8 * B:], 8 * words * 4 = 32 * words bytes behind the first: a multiple of 16 for ANY words, so a second launch never
+# starts unaligned through cat_batch / split_batch (words = 7, n = 15: byte 224).  Inside each launch parts 1, 2, 3, 5, 6, 7 of 7 words
+# are unaligned; a destination that itself starts unaligned is covered by the direct calls below (`off` = 1 word).
+NAN = float('nan')
+SENTINEL = -77.0
+
+
+def _N():
+    from multimodal_segmentation_amd import _native as N
+    return N
+
+
+def _left_to_right(ts):
+    acc = ts[0].clone()
+    for t in ts[1:]:
+        acc = acc + t
+    return acc
+
+
+# n operands, numel.  n4 = numel // 4 groups of four + numel % 4 tail elements; n = 9: two launches (8 operands, then the sum + the 9th)
+SUM_N_CASES = [pytest.param(n, numel, id='n%d-numel%d-%s' % (n, numel, 'tail-only' if numel < 4 else 'one-quad-tail-%d' % (numel % 4)))
+               for numel in (3, 5, 6, 7) for n in (1, 2, 8, 9)] + [
+    # grid16(n4 + 1) = 4096 blocks x 256 threads = 1 048 576: one quad makes a second trip, and three tail elements follow
+    pytest.param(2, 4194311, id='n2-numel4194311-1048577-quads-wrap-tail-3')]
+
+
+@pytest.mark.parametrize('n,numel', SUM_N_CASES)
+def test_sum_n_tail_and_wrap(n, numel, device):
+    """mmseg_sum_n_t with element code 0 (sum_n_kernel<0>) through ops._sum_n, ops.share and by direct call into a NaN buffer: the fp64
+    sum at RTOL, and bit for bit the left-to-right fp32 sum of plain torch"""
+    ts = [rnd(numel, seed=80 + k) for k in range(n)]
+    want, exact = sum(t.double() for t in ts), _left_to_right(ts)
+    ds = [t.to(device) for t in ts]
+    got = P._sum_n(ds, ds[0])
+    _close(got, want, 'sum of %d' % n)
+    assert torch.equal(got.cpu(), exact)
+    if n <= 8:
+        out = torch.full((numel,), NAN).to(device)
+        _N().call('mmseg_sum_n_t', *(ds + [None] * (8 - n)), n, out, numel, 0)
+        _close(out, want, 'direct sum of %d' % n)
+        assert torch.equal(out.cpu(), exact)
+    if n > 1 and numel < 100:
+        x = rnd(numel, seed=79).to(device).requires_grad_(True)
+        torch.autograd.backward(P.share(x, n), ds)
+        _close(x.grad, want, 'shared grad')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('dtype,h', [(torch.bfloat16, 1), (torch.float16, 2)], ids=['bf16', 'fp16'])
+@pytest.mark.parametrize('n,numel', SUM_N_CASES)
+def test_sum_n_16bit_codes(n, numel, dtype, h):
+    """sum_n_kernel<1> / <2> on the device: bit for bit the rounding of the fp32 left-to-right sum of the widened operands (n = 9: the
+    first launch's sum is rounded to 16 bits before the ninth operand is added)"""
+    ts = [rnd(numel, seed=80 + k).to(dtype) for k in range(n)]
+    ds = [t.to('cuda') for t in ts]
+    if n <= 8:
+        out = torch.full((numel,), NAN, dtype=dtype, device='cuda')
+        _N().call('mmseg_sum_n_t', *(ds + [None] * (8 - n)), n, out, numel, h)
+        assert torch.equal(out.cpu(), _left_to_right([t.float() for t in ts]).to(dtype))
+        want = out.cpu()
+    else:
+        first = _left_to_right([t.float() for t in ts[:8]]).to(dtype)
+        want = _left_to_right([first.float()] + [t.float() for t in ts[8:]]).to(dtype)
+    got = P._sum_n(ds, ds[0])
+    assert got.dtype == dtype and torch.equal(got.cpu(), want)
+
+
+def test_sum_n_rejects_operand_counts_and_null_operands(device):
+    a = rnd(8, seed=1).to(device)
+    out = torch.zeros(8).to(device)
+    N = _N()
+    N.call('mmseg_sum_n_t', a, a, a, None, None, None, None, None, 3, out, 8, 0)                # (accepted)
+    with pytest.raises(_native_error()):
+        N.call('mmseg_sum_n_t', a, None, None, None, None, None, None, None, 0, out, 8, 0)      # n = 0
+    with pytest.raises(_native_error()):
+        N.call('mmseg_sum_n_t', a, a, a, a, a, a, a, a, 9, out, 8, 0)                           # n = 9
+    with pytest.raises(_native_error()):
+        N.call('mmseg_sum_n_t', a, None, a, None, None, None, None, None, 3, out, 8, 0)         # a NULL operand below n
+
+
+# n parts, shape of a part, dtype
+CAT_CASES = [
+    # 24 bytes per part: part 0 takes the 16-byte branch with a 2-word tail, part 1 starts at byte 24 (one word per thread), part 2 at
+    # byte 48 is aligned again
+    pytest.param(3, (1, 6), torch.float32, id='words6-n3-vector-tail-2-scalar-vector'),
+    pytest.param(8, (1, 1), torch.float32, id='words1-n8-w4-0-parts-0-and-4-tail-only'),
+    pytest.param(15, (1, 7), torch.float32, id='words7-n15-two-launches-8+7'),
+    pytest.param(2, (1, 4194308), torch.float32, id='words4194308-n2-1048577-quads-wrap'),      # grid16(w4 + 1) = 4096 blocks: one quad wraps
+    pytest.param(4, (3, 10), torch.bfloat16, id='bf16-30-elements-15-words-n4'),                # part k starts at byte 60 * k
+    pytest.param(3, (2, 4), torch.float16, id='fp16-8-elements-4-words-n3'),
+]
+
+
+@pytest.mark.parametrize('n,shape,dtype', CAT_CASES)
+def test_cat_and_split_batch_boundaries(n, shape, dtype, device):
+    """ops.cat_batch and the gradient of ops.split_batch (mmseg_cat_words) move bytes: bit for bit; an unused split (a NULL part, written
+    as zeros) in the first, a middle and the last position"""
+    B = shape[0]
+    parts = [rnd(*shape, seed=20 + i).to(dtype) for i in range(n)]
+    y = P.cat_batch([t.to(device) for t in parts])
+    assert y.dtype == dtype and torch.equal(y.cpu(), torch.cat(parts, 0))
+    for unused in sorted({0, n // 2, n - 1}):
+        big = rnd(n * B, *shape[1:], seed=6).to(dtype).to(device).requires_grad_(True)
+        sp = P.split_batch(big, n)
+        use = [i for i in range(n) if i != unused]
+        torch.autograd.backward([sp[i] for i in use], [parts[i].to(device) for i in use])
+        want = torch.cat([torch.zeros(shape, dtype=dtype) if i == unused else parts[i] for i in range(n)], 0)
+        assert torch.equal(big.grad.cpu(), want), 'unused split %d' % unused
+
+
+def test_cat_batch_of_views_that_start_4_bytes_into_a_buffer(device):
+    """ops._c keeps a contiguous view, so the kernel gets sources that are NOT 16-byte aligned for aligned destinations (parts of 24
+    words): one word per thread"""
+    shape = (2, 3, 4)
+    bufs = [rnd(28, seed=30 + i).to(device) for i in range(3)]
+    xs = [b[1:25].view(shape) for b in bufs]
+    if device == 'cuda':
+        assert all(x.data_ptr() % 16 == 4 for x in xs)
+    y = P.cat_batch(xs)
+    assert torch.equal(y.cpu(), torch.cat([b.cpu()[1:25].view(shape) for b in bufs], 0))
+
+
+@pytest.mark.parametrize('n,words,off,nulls', [
+    pytest.param(3, 6, 0, (), id='words6-n3'),
+    pytest.param(3, 6, 0, (0,), id='words6-n3-null-first'),
+    pytest.param(3, 6, 0, (1,), id='words6-n3-null-middle-unaligned-part'),
+    pytest.param(3, 6, 0, (2,), id='words6-n3-null-last'),
+    pytest.param(8, 1, 0, (), id='words1-n8'),
+    pytest.param(7, 7, 0, (3,), id='words7-n7-null-middle'),
+    pytest.param(4, 8, 1, (), id='words8-n4-destination-starts-at-byte-4-all-scalar'),
+    pytest.param(2, 9, 3, (1,), id='words9-n2-destination-starts-at-byte-12-part-1-aligned-null'),   # 12 + 36 = 48
+    pytest.param(2, 4194308, 0, (), id='words4194308-n2-wraps'),
+])
+def test_cat_words_writes_its_range_and_nothing_else(n, words, off, nulls, device):
+    """mmseg_cat_words by direct call into a buffer full of a sentinel: the n * words words are written, the words in front (`off`) and
+    the row behind keep the sentinel"""
+    buf = torch.full((off + (n + 1) * words,), SENTINEL).to(device)
+    out = buf[off:off + n * words].view(n, words)
+    parts = [None if k in nulls else rnd(1, words, seed=30 + k) for k in range(n)]
+    _N().call('mmseg_cat_words', *([None if t is None else t.to(device) for t in parts] + [None] * (8 - n)), n, out, words)
+    want = torch.cat([torch.zeros(1, words) if t is None else t for t in parts], 0)
+    got = buf.cpu()
+    assert torch.equal(got[off:off + n * words].view(n, words), want)
+    assert bool((got[:off] == SENTINEL).all()) and bool((got[off + n * words:] == SENTINEL).all()), 'written outside the range'
+
+
+def test_cat_words_rejects_part_counts(device):
+    a = rnd(1, 4, seed=1).to(device)
+    N = _N()
+    with pytest.raises(_native_error()):
+        N.call('mmseg_cat_words', a, None, None, None, None, None, None, None, 0, torch.zeros(1, 4).to(device), 4)
+    with pytest.raises(_native_error()):
+        N.call('mmseg_cat_words', a, a, a, a, a, a, a, a, 9, torch.zeros(9, 4).to(device), 4)
+
+
+def _idx(rows, src_rows, seed):
+    return torch.randint(0, src_rows, (rows,), generator=torch.Generator().manual_seed(seed), dtype=torch.int64)
+
+
+GATHER_CASES = [
+    # gridDim.y = min(4096, rows): row 4096 is taken by the block of row 0 on its second trip
+    pytest.param((50, 4), _idx(4097, 50, 1), id='rows4097-of-4-words-gridy-4096-row-4096-second-trip'),
+    pytest.param((10, 6), torch.tensor([9, 8, 7, 7, 6, 5, 4, 3, 3, 2, 1, 0, 0]), id='6-words-scalar-branch-descending-repeated'),
+    pytest.param((5, 1028), torch.tensor([4, 4, 0, 2]), id='1028-words-257-quads-two-x-blocks-second-holds-1'),
+    # words / 4 = 1 048 578 quads for min(1024, 4097) = 1024 x blocks of 256: every thread makes 4 trips, two make a fifth
+    pytest.param((2, 4194312), torch.tensor([1, 0]), id='2-rows-of-4194312-words-bx-capped-at-1024-wraps'),
+    pytest.param((5, 8), torch.zeros(0, dtype=torch.int64), id='rows0-no-launch'),
+    pytest.param((5, 0), torch.tensor([1, 2]), id='words0-no-launch'),
+    pytest.param((12, 2, 3), torch.tensor([11, 0, 11]), id='bf16-rows-of-6-elements-3-words'),
+]
+
+
+@pytest.mark.parametrize('src_shape,idx', GATHER_CASES)
+def test_gather_rows_boundaries(src_shape, idx, device):
+    """ops.gather_rows and mmseg_gather_rows into a NaN buffer == index_select along the leading axis, bit for bit"""
+    src = rnd(*src_shape, seed=3)
+    if len(src_shape) == 3:
+        src = src.to(torch.bfloat16)
+    want = src.index_select(0, idx)
+    sd, idd = src.to(device), idx.to(device)
+    assert torch.equal(P.gather_rows(sd, idd).cpu(), want)
+    out = torch.full(want.shape, NAN, dtype=src.dtype).to(device)
+    words = (src.numel() // src_shape[0]) * src.element_size() // 4
+    _N().call('mmseg_gather_rows', sd, idd, out, idx.numel(), words, src_shape[0])
+    assert torch.equal(out.cpu(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('words', [8, 6], ids=['16-byte-branch', 'scalar-branch'])
+def test_gather_rows_skips_indices_outside_the_source(words):
+    """by direct call on the device (ops.gather_rows' callers validate their indices): an index of -1 or of src_rows leaves the output
+    row as it was and reads nothing (the kernel `continue`s in front of the row's address)"""
+    src = rnd(4, words, seed=4).to('cuda')
+    idx = torch.tensor([2, -1, 4, 0, 3], dtype=torch.int64, device='cuda')
+    out = torch.full((5, words), SENTINEL, device='cuda')
+    _N().call('mmseg_gather_rows', src, idx, out, 5, words, 4)
+    got, s = out.cpu(), src.cpu()
+    assert torch.equal(got[[0, 3, 4]], s[[2, 0, 3]])
+    assert bool((got[[1, 2]] == SENTINEL).all())
+
+
+@pytest.mark.parametrize('M,C', [
+    pytest.param(1, 1, id='M1-C1'), pytest.param(1, 4, id='M1-C4'), pytest.param(7, 4, id='M7-C4'), pytest.param(300, 1, id='M300-C1-two-blocks'),
+    pytest.param(1048577, 1, id='M1048577-C1-wraps-by-one-row'),                 # grid16(M) = 4096 blocks x 256 rows = 1 048 576
+])
+def test_add_residual_boundaries(M, C, device):
+    """ops.add_residual and mmseg_add_residual into a NaN buffer: the background channel is 1 unless some mask equals 1 EXACTLY.  The
+    neighbours of 1 in fp32, 1, -1 and 0 are planted in the first row, the last row of the first trip and the first wrapped row"""
+    import numpy as np
+    base = (torch.rand(M, C, generator=torch.Generator().manual_seed(3)) > 0.8).float()
+    anchors = sorted({0, min(M, 1048576) - 1, M - 1})
+    vals = [float(np.nextafter(np.float32(1), np.float32(0))), float(np.nextafter(np.float32(1), np.float32(2))), 1.0, -1.0, 0.0]
+    for j, v in enumerate(vals):
+        m = base.clone()
+        for r in anchors:
+            m[r] = 0.5
+            m[r, j % C] = v
+        assert m[0, j % C].item() == v
+        want = torch.cat([m, 1.0 - (m == 1).any(-1, keepdim=True).float()], -1)
+        for r in anchors:
+            assert want[r, C].item() == (0.0 if v == 1.0 else 1.0)
+        md = m.to(device)
+        assert torch.equal(P.add_residual(md).cpu(), want), 'planted %r' % v
+        out = torch.full((M, C + 1), NAN).to(device)
+        _N().call('mmseg_add_residual', md, out, M, C)
+        assert torch.equal(out.cpu(), want), 'planted %r (direct)' % v
+
+
+def test_add_residual_rejects_zero_channels(device):
+    with pytest.raises(_native_error()):
+        _N().call('mmseg_add_residual', torch.zeros(4, 1).to(device), torch.zeros(4, 1).to(device), 4, 0)

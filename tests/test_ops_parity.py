@@ -1035,6 +1035,9 @@ BN_EDGES = [
     pytest.param((1, 1, 1, 64), id='v4-M1-variance-0'),                         # batch variance exactly 0, dx exactly 0
     pytest.param((2, 16, 16, 192), id='v4-C192-three-column-blocks'),
     pytest.param((1, 130, 127, 256), id='v4-n4-1056640-apply-wraps'),           # 16510 * 64 float4 > 4096 * 256 = 1 048 576: bn_apply / bn_bwd_apply wrap
+    # M = 16385: v4_row_blocks = min(512, 1024 / 4, 257) = 256 blocks of ceil(16385 / 256) = 65 rows: blocks 0..251 full, block 252 holds
+    # 5 rows, blocks 253..255 are EMPTY (r0 >= M) and write zero partials that bn_stats_final / bn_bwd_final sum; n4 = 1 048 640 wraps by 64
+    pytest.param((1, 145, 113, 256), id='v4-M16385-rpb65-three-empty-row-blocks'),
 ]
 
 
