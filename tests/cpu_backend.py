@@ -83,6 +83,8 @@ def conv2d_wprep(w, out, KH, KW, Cin, Cout, mode):
 
 def conv2d_fwd(x1, x2, w, wt, bias, y, y2, B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, ups, transposed, act,
                alpha, nsplit1):
+    if w is None and (wt is None or transposed or C1 % 32 or C2 % 32 or Cout % 4):
+        return 1       # the library's own argument check (csrc/conv.hip, conv_dispatch): only the fast path reads `wt`
     xin = _logical_input(x1, x2, B, H, W, C1, C2, ups).permute(0, 3, 1, 2)
     if w is None:      # only the fast layout was supplied: [Cout][KH*KW][Cin]
         w = wt.reshape(Cout, KH * KW, C1 + C2).permute(1, 2, 0)

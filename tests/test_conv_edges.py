@@ -1,0 +1,454 @@
+"""The fp32 implicit-GEMM convolutions (csrc/conv.hip) at their tile, slab and dispatch edges.
+
+Continues tests/test_ops_edges.py with the same conventions: every operator case runs on the device (`-m gpu`) and through
+tests/cpu_backend.py against the fp64 oracle on the same seeded fp32 inputs, gradient buffers start NON-ZERO (gbuf_pattern), and the
+id of a case gives the arithmetic it exercises.  On the device every case also asserts which kernel template its three launches took
+(mmseg_conv2d_last_kernel: family * 1000000 + 500000 * flag + M-or-K tile * 1000 + N tile), so a dispatcher change cannot move a
+case off the kernel it was written for without this file failing.  Everything runs in fp32 with mmseg_conv16_mode 1 (the default).
+
+Launch arithmetic, recomputed from the launchers (M = B * Ho * Wo output pixels, K = KH * KW * Cin):
+
+  conv_dispatch           fast = a prepared weight image + C1 % 32 == 0, C2 % 32 == 0, Cout % 4 == 0 (conv_fast_kernel), otherwise the generic
+                          conv_fwd_kernel with a 16-byte gather (C1 % 4 == 0, C2 % 4 == 0; flag 500000) or a scalar one.  Tile on both:
+                          tiles_big = ceil(M / 128) * ceil(Cout / 128), tiles_mid = ceil(M / 128) * ceil(Cout / 64);
+                          Cout > 64 and tiles_big >= 384 -> <128,128>; Cout > 32: tiles_mid >= 384 -> <128,64>, else <64,64>; Cout <= 32 -> <128,32>.
+                          3x3 'same' with W % 32 == 0, H % 8 == 0, Cout > 32 and a filled grid leaves the stack for conv16h_kernel (family 17).
+  ops._Conv2d.backward    data gradient: stride 2, one input, Cout % 32 == 0, Cin % 4 == 0 -> the four parity classes in one
+                          conv_fast_batched_kernel launch (family 4; tile as above with N = Cin and tiles * 4 classes of maxM pixels, class z
+                          runs nblk[z] = ceil(M_z / BM) * ceil(Cin / BN) of the gridDim.x = max nblk blocks); stride 1 with Cin <= 16, Cin % 4 == 0
+                          and Cout % 32 == 0 -> a 1x1 product over the taps on the fast path + tap sum; else a convolution with the flipped kernel
+                          (fast when Cout % 32 == 0, Cin % 4 == 0 and stride 1, otherwise generic, fractionally strided when stride 2).
+  conv2d_wgrad_impl       fast = C1 % 4 == 0, C2 % 4 == 0, Cout % 4 == 0.
+                          tr   = fast, stride 1, Wo % 4 == 0 (8 -> 8 excluded): conv_wgrad_tr_kernel (family 6, flag = two inputs), K tile 192 when
+                                 K % 192 == 0, K % 128 != 0 and Cout > 32, else 128; N tile 128 / 64 / 32 for Cout > 64 / > 32 / <= 32.
+                          anyw = fast, not tr, stride 1 or 2, one input, no up-sampling, Cout > 32, K tile 128: conv_wgrad_tr_anyw_kernel (family 14).
+                          Both split M by the cost model of wgrad_tr_splits (chunks are multiples of 32, S = ceil(M / chunk) exactly: no empty slab).
+                          Otherwise conv_wgrad_fast_kernel (fast; family 7, 1-D grid through xcd_remap) or conv_wgrad_kernel (family 8, flag = 16-byte
+                          gather) with S = min(ceil(3072 / (ceil(K / 128) * ceil(Cout / BN))), ceil(M / 512)) and chunk = ceil(M / S) rounded up to 32
+                          WITHOUT recomputing S: when S is not limited by ceil(M / 512) the last slabs can start beyond M and must be written as zeros.
+                          3x3 'same' with W % 32 == 0 and channels % 32 == 0 leaves for wgrad32h_kernel (family 18); 8 -> 8 with H % 8 == 0, W % 64 == 0
+                          and S > 1 runs conv_wgrad_c8m_kernel (family 9) on min(S, tiles) slabs.
+  slab reduction          S == 1 and accumulate == 0: the kernel writes dW itself, the workspace is not touched.  Otherwise S slabs of K * Cout
+                          floats are staged and slab_reduce_kernel adds them (to dW when accumulate == 1): float4 body, scalar tail for
+                          K * Cout % 4 != 0; S > 64: first ceil(S / 32) groups of 32 slabs (the last one partial) into ws[S * K * Cout ...], then those.
+
+Every fp32 instantiation the dispatchers can select, and the case that reaches it (old = CONV_CASES of tests/test_ops_parity.py, whose kernels
+test_conv_cases_run_on_the_kernels_recorded_for_them pins; new = CONV_EDGES below):
+  conv_fast_kernel          <128,128> new 1x100x99 32->516   <128,64> new 1x78x79 32->516, 1x157x157 32->68, 1x316x316 32->80
+                            <64,64> old 2x16x16 64->64   <128,32> old 3x17x19 64->8
+  conv_fwd_kernel  16-byte  <128,128> new 1x160x154 4->132   <128,64> new 1x446x446 4->64   <64,64> old 2x34x30 4->64   <128,32> old 2x33x33 16->32
+                   scalar   <128,128> new 1x160x154 3->130   <128,64> new 1x222x222 3->36   <64,64> new 2x15x17 3->40   <128,32> new 3x41x39 6->10
+  conv_fast_batched_kernel  <128,128> new 1x221x221 96->32   <128,64> new 1x223x223 64->32   <64,64> old 2x31x31 64->128   <128,32> old 2x33x33 16->32
+  conv_wgrad_tr_kernel      one input:  <192,128> new 2x18x20 64->128   <192,64> old 2x16x16 64->64   <128,128> old 2x8x8 256->512
+                                        <128,64> old 2x16x16 128->64 (up-sampled), new 1x26x44 16->48 (up-sampled)   <128,32> old 2x16x20 4->32, new 2x96x92 16->20
+                            two inputs: <192,128> new 2x18x20 32+32->72   <192,64> new 1x22x36 32+32->64   <128,128> new 2x22x12 64+64->96 (up-sampled)
+                                        <128,64> old 1x16x16 64+64->64   <128,32> new 2x14x20 8+8->20
+  conv_wgrad_tr_anyw_kernel <128,128> old 2x16x16 64->128 (stride 2), new 1x100x99 32->516   <128,64> old 2x34x30 4->64, new 1x446x446 4->64
+  conv_wgrad_fast_kernel    <128,128> new 2x35x35 64->128   <128,64> new 1x135x135 64->64, 2x91x91 32+32->64   <128,32> old 2x33x33 16->32, new 4x67x67 16->32
+  conv_wgrad_kernel 16-byte <128,64> new 2x21x19 8->34   <128,32> old 3x17x19 8->5, new 3x41x39 8->6
+                    scalar  <128,64> new 1x160x154 3->130   <128,32> new 3x41x39 6->10
+  outside this stack (their own tests are CONV_CASES and tests/test_act16.py): conv_direct_mfma_kernel 3, conv_dgrad_s2k4_smallc_kernel 5,
+  conv_wgrad_c8m_kernel 9 (new 3x128x128 8->8: 96 slabs), pw_reduce 10 / 12, smallk 11 / 13, s2k3c9 21 / 22, locnet5 23 / 24, wgrad32h_kernel 18
+  (old 3x128x128 64->128); conv16h_kernel<PREC 0> (17) needs >= 192 blocks of 256 pixels in mode 1, i.e. M >= 49152 at 64+ channels (above the
+  size limit of this file): tests/test_act16.py forces it onto small problems with mode 2.  The measurement-build instances (conv_direct_kernel,
+  conv_wgrad_c8_kernel, forced tiles) are selected by environment switches only and are not part of the product's dispatch.
+
+Size: no case holds more than about 45 MB of operands and results on the device or costs the oracle more than about 2.1 GFLOP per pass, except the
+empty-slab case of conv_wgrad_fast_kernel (256 -> 20, 5x5: 8.2 GFLOP, under a second in the oracle; direct call, device only).
+
+Tolerances: those of the neighbours -- RTOL = 2e-4 of the tensor's largest magnitude through `check`, 2e-5 of the largest magnitude for the direct
+weight-gradient calls (as tests/test_act16.py).
+  case                          | tolerance | differs from the neighbour
+  ------------------------------+-----------+---------------------------
+  (none)                        |           | no case needed another tolerance
+"""
+import contextlib
+import functools
+
+import pytest
+import torch
+
+from oracle import ops as O
+from multimodal_segmentation_amd import ops as P
+from multimodal_segmentation_amd import _native as N
+from tests.test_ops_parity import CONV_CASES, _anchor, _native_error, check, device, gbuf_pattern, rnd  # noqa: F401 (device: fixture)
+
+
+@contextlib.contextmanager
+def _fp32_default_mode():
+    """fp32 products and the default large-tile mode while the block runs; both restored (as tests/test_act16.py does)"""
+    prevp = P.set_conv_precision('fp32')
+    prev = N.call('mmseg_conv16_mode', 1)
+    try:
+        yield
+    finally:
+        N.call('mmseg_conv16_mode', prev)
+        P.set_conv_precision(prevp)
+
+
+def _last():
+    return N.call('mmseg_conv2d_last_kernel')
+
+
+def _conv_inputs(B, H, W, C1, C2, Cout, k, ups):
+    x1 = rnd(B, H // 2 if ups else H, W // 2 if ups else W, C1, seed=1)
+    w = rnd(k, k, C1 + C2, Cout, seed=2, scale=(2.0 / (k * k * (C1 + C2))) ** 0.5)
+    b = rnd(Cout, seed=3, scale=0.1)
+    return [x1, w, b] + ([rnd(B, H, W, C2, seed=4)] if C2 else [])
+
+
+def _launch_codes(B, H, W, C1, C2, Cout, k, stride, padding, act, ups, dev='cuda'):
+    """(forward, weight gradient, data gradient) kernel codes of ops.conv2d, read the way test_modality_encoder_first_layer_runs_on_its_own_kernels
+    does: after the forward, after a backward without an input gradient (its last launch is the weight gradient), after one with"""
+    inputs = [t.to(dev) for t in _conv_inputs(B, H, W, C1, C2, Cout, k, ups)]
+    x1, w, b = inputs[:3]
+    x2 = inputs[3] if C2 else None
+    codes = []
+    for need_dx in (False, True):
+        xa = x1.clone().requires_grad_(need_dx)
+        wg, bg = torch.zeros_like(w), torch.zeros_like(b)
+        y = P.conv2d(xa, w, b, stride=stride, padding=padding, act=act, alpha=0.2 if act == 'leaky' else 0.0, x2=x2, upsample=ups,
+                     wgrad=wg, bgrad=bg, anchor=_anchor(x1))
+        fwd = _last()
+        y.backward(torch.ones_like(y))
+        codes.append((fwd, _last()))
+    assert codes[0][0] == codes[1][0]
+    return codes[0][0], codes[0][1], codes[1][1]
+
+
+# ======================================================================================================================
+# 1. operator level, both backends
+# ======================================================================================================================
+# B, H, W, C1, C2, Cout, k, stride, padding, act, ups | kernel codes: forward, weight gradient, data gradient (asserted on the device)
+CONV_EDGES = [
+    # ---- forward tiles with ragged edges --------------------------------------------------------------------------------------------
+    # M = 9900: 78 M tiles, the last holds 44 rows; 5 N tiles, the last holds 4 columns; tiles_big = 390.  Weight gradient: any-width
+    # <128,128>, S = 45, chunk 224, last slab 44 pixels, 225 blocks.  Data gradient 516 -> 32: 516 % 32 != 0 -> flipped kernel, generic 16-byte <128,32>
+    pytest.param(1, 100, 99, 32, 0, 516, 1, 1, 'same', None, False, 1128128, 14128128, 2628032, id='fast-128x128-M%128=44-Cout%128=4-tiles_big390'),
+    # M = 6162: tiles_big = 245 < 384, tiles_mid = 49 * 9 = 441; last M tile 18 rows, last N tile 4 columns.  Weight gradient S = 39, chunk 160, last 82
+    pytest.param(1, 78, 79, 32, 0, 516, 1, 1, 'same', 'leaky', False, 1128064, 14128128, 2628032, id='fast-128x64-M%128=18-Cout%64=4-tiles_mid441'),
+    # M = 24649: tiles_mid = 193 * 2 = 386; the second N tile holds 4 live columns.  Weight gradient: any-width <128,128>, S = 155, chunk 160, last 9
+    pytest.param(1, 157, 157, 32, 0, 68, 3, 1, 'same', 'relu', False, 1128064, 14128128, 2628032, id='fast-128x64-M%128=73-second-N-tile-4-columns'),
+    # a discriminator layer (4x4, stride 2, 'valid') with ragged M on <128,64>: Ho = Wo = 157, M = 24649, tiles_mid = 386; Cout % 64 = 16.  Data gradient:
+    # Cout % 32 != 0 -> no parity classes: the fractionally strided generic launch (M = 99856, 781 blocks).  Weight gradient: S = 111, chunk 224, last 9
+    pytest.param(1, 316, 316, 32, 0, 80, 4, 2, 'valid', 'leaky', False, 1128064, 14128128, 2628032, id='fast-128x64-k4s2-M24649-M%128=73-dgrad-transposed'),
+    # D_Mask's first layer at the smallest size that still picks the production tile: M = 222 * 222 = 49284, tiles_mid = 386, last M tile 4 rows.
+    # Weight gradient: any-width <128,64>, S = 221, chunk 224, last slab 4 pixels (two-level reduction: 7 groups, the last of 29)
+    pytest.param(1, 446, 446, 4, 0, 64, 4, 2, 'valid', 'leaky', False, 2628064, 14128064, 5004064, id='generic-vec-128x64-k4s2-M49284-M%128=4'),
+    # M = 24640: tiles_big = 193 * 2 = 386, last M tile 64 rows, second N tile 4 (132) / 2 (130) columns; 130 % 4 != 0 on the scalar case.
+    # Weight gradients: any-width S = 110, chunk 224 (exact) / generic scalar <128,64>, S = 49, chunk 512, last 64
+    pytest.param(1, 160, 154, 4, 0, 132, 3, 1, 'same', None, False, 2628128, 14128128, 2628032, id='generic-vec-128x128-M%128=64-Cout%128=4-tiles_big386'),
+    pytest.param(1, 160, 154, 3, 0, 130, 3, 1, 'same', 'relu', False, 2128128, 8128064, 2128032, id='generic-scalar-128x128-M%128=64-Cout%128=2-wgrad-S49'),
+    # the scalar gather on the two remaining tiles: M = 49284, tiles_mid = 386, Cout % 64 = 36 (weight gradient: generic, S = 97 -> groups 32, 32, 32, 1,
+    # K * Cout = 972); M = 510: <64,64>, last M tile 62 rows, Cout % 64 = 40
+    pytest.param(1, 222, 222, 3, 0, 36, 3, 1, 'same', None, False, 2128064, 8128064, 2628032, id='generic-scalar-128x64-M%128=4-wgrad-S97-last-group-1'),
+    pytest.param(2, 15, 17, 3, 0, 40, 3, 1, 'same', 'leaky', False, 2064064, 8128064, 2628032, id='generic-scalar-64x64-M%64=62-Cout40'),
+    # ---- batched parity classes of a stride-2 data gradient (odd input: classes of different sizes, nblk[z] < gridDim.x for the small ones) -------
+    # N = Cin = 64; classes 112x112, 112x111, 111x112, 111x111: maxM = 12544 -> tiles_mid = 98 * 1 * 4 = 392; nblk = 98, 98, 98, 97; the last input row and
+    # column are reached by no tap.  Weight gradient: family 7 <128,32>, S = 24, chunk 512, last 324, 8 K tiles -> 192 blocks
+    pytest.param(1, 223, 223, 64, 0, 32, 4, 2, 'valid', 'leaky', False, 1128032, 7128032, 4128064, id='batched-128x64-classes-12544-12432-12432-12321'),
+    # N = Cin = 96 on the 128-wide tile (32 dead columns); classes 111x111 ... 110x110: maxM = 12321 -> tiles_big = 97 * 1 * 4 = 388; nblk = 97, 96, 96, 95.
+    # Weight gradient: family 7 <128,32>, S = 24, chunk 512, last 105, 288 blocks
+    pytest.param(1, 221, 221, 96, 0, 32, 4, 2, 'valid', None, False, 1128032, 7128032, 4128128, id='batched-128x128-Cin96-classes-12321-12210-12210-12100'),
+    # ---- conv_wgrad_fast_kernel: several slabs, grids that are no multiple of 8 (xcd_remap with r != 0 and bz > 0) ---------------------
+    # K = 576 would take the 192-row transposed kernel, stride 2 sends it here: M = 4489, S = 9, chunk 512, last 393, 5 K tiles -> 45 blocks
+    pytest.param(1, 135, 135, 64, 0, 64, 3, 2, 'valid', 'leaky', False, 1064064, 7128064, 4064064, id='wgrad-fast-128x64-S9-last393-45-blocks'),
+    # two inputs: M = 4050, S = 8, chunk 512, last 466, 40 blocks; data gradient of two inputs: fractionally strided generic launch with a split store
+    pytest.param(2, 91, 91, 32, 32, 64, 3, 2, 'valid', None, False, 1064064, 7128064, 2564064, id='wgrad-fast-128x64-two-inputs-S8-last466-40-blocks'),
+    pytest.param(4, 67, 67, 16, 0, 32, 3, 2, 'valid', 'leaky', False, 2628032, 7128032, 4128032, id='wgrad-fast-128x32-S9-last260-18-blocks'),  # M = 4356, K = 144
+    pytest.param(2, 35, 35, 64, 0, 128, 3, 2, 'valid', None, False, 1064064, 7128128, 4064064, id='wgrad-fast-128x128-S2-last258-10-blocks'),    # M = 578, chunk 320
+    # ---- conv_wgrad_kernel (generic) with more than two slabs: M = 4797, S = 10, chunk 480, last 477 ---------------------------------
+    pytest.param(3, 41, 39, 6, 0, 10, 3, 1, 'same', None, False, 2128032, 8128032, 2128032, id='wgrad-generic-scalar-128x32-S10-last477'),        # K * Cout = 540
+    pytest.param(3, 41, 39, 8, 0, 6, 3, 1, 'same', 'leaky', False, 2628032, 8628032, 2128032, id='wgrad-generic-vec-128x32-Cout6-S10-last477'),  # Cout % 4 = 2
+    pytest.param(2, 21, 19, 8, 0, 34, 3, 1, 'same', None, False, 2564064, 8628064, 2128032, id='wgrad-generic-vec-128x64-Cout34-S2-last382'),    # M = 798, chunk 416
+    # ---- conv_wgrad_tr_kernel on its five tiles (W % 32 != 0: wgrad32h_kernel cannot take them; M no multiple of the chunk) -----------
+    pytest.param(2, 18, 20, 64, 0, 128, 3, 1, 'same', None, False, 1064064, 6192128, 1064064, id='wgrad-tr-192x128-S5-chunk160-last80'),          # M = 720, K = 576
+    pytest.param(2, 18, 20, 32, 32, 72, 3, 1, 'same', 'relu', False, 1064064, 6692128, 2564064, id='wgrad-tr-192x128-two-inputs-Cout72-S5-last80'),
+    pytest.param(1, 22, 36, 32, 32, 64, 3, 1, 'same', None, False, 1064064, 6692064, 1064064, id='wgrad-tr-192x64-two-inputs-S5-chunk160-last152'),  # M = 792
+    # up-sampled x1 (stored 11 x 6) + a second input: M = 528, K = 1152, S = 4, chunk 160, last 48, 9 K tiles -> 36 blocks
+    pytest.param(2, 22, 12, 64, 64, 96, 3, 1, 'same', None, True, 1064064, 6628128, 1064064, id='wgrad-tr-128x128-upsampled+second-input-S4-last48'),
+    pytest.param(1, 26, 44, 16, 0, 48, 3, 1, 'same', 'leaky', True, 2564064, 6128064, 2628032, id='wgrad-tr-128x64-upsampled-S8-chunk160-last24'),   # M = 1144, K = 144
+    # more than 64 slabs: M = 17664, S = 111, chunk 160, last 64, 2 K tiles -> 222 blocks; groups of 32, 32, 32, 15
+    pytest.param(2, 96, 92, 16, 0, 20, 3, 1, 'same', None, False, 2628032, 6128032, 2628032, id='wgrad-tr-128x32-S111-chunk160-last64-222-blocks'),
+    pytest.param(2, 14, 20, 8, 8, 20, 3, 1, 'same', None, False, 2628032, 6628032, 2628032, id='wgrad-tr-128x32-two-inputs-S4-chunk160-last80'),    # M = 560
+    # ---- 8 -> 8 weight gradient above 64 slabs: M = 49152, S = min(96, 3 * 16 * 2 tiles) = 96 -> groups 32, 32, 32 -----------------------
+    pytest.param(3, 128, 128, 8, 0, 8, 3, 1, 'same', 'leaky', False, 3008008, 9008008, 3008008, id='wgrad-c8-S96-two-level'),
+]
+
+
+@pytest.mark.parametrize('B,H,W,C1,C2,Cout,k,stride,padding,act,ups,k_fwd,k_wgrad,k_dgrad', CONV_EDGES)
+def test_conv2d_boundaries(B, H, W, C1, C2, Cout, k, stride, padding, act, ups, k_fwd, k_wgrad, k_dgrad, device):
+    alpha = 0.2 if act == 'leaky' else 0.0
+    seen = []
+
+    def f_prod(x1, w, b, x2=None):
+        y = P.conv2d(x1, w, b, stride=stride, padding=padding, act=act, alpha=alpha, x2=x2, upsample=ups,
+                     wgrad=w.gbuf, bgrad=b.gbuf, anchor=_anchor(x1))
+        if device == 'cuda':
+            seen.append(_last())
+        return y
+
+    def f_ref(x1, w, b, x2=None):
+        xin = O.upsample2(x1) if ups else x1
+        if x2 is not None:
+            xin = torch.cat([xin, x2], -1)
+        y = O.conv2d(xin, w, b, stride=stride, padding=padding)
+        f_ref.pre = y
+        if act == 'relu':
+            y = torch.relu(y)
+        elif act == 'leaky':
+            y = O.leaky_relu(y, alpha)
+        return y
+
+    with _fp32_default_mode():
+        check(f_prod, f_ref, _conv_inputs(B, H, W, C1, C2, Cout, k, ups), device, param_idx=(1, 2), gbuf_fill=gbuf_pattern)
+        if device == 'cuda':
+            seen.append(_last())       # the backward of `check` wants the input gradient: its last launch is the data gradient
+            assert tuple(seen) == (k_fwd, k_dgrad), 'forward / data gradient ran on %s' % (seen,)
+            got = _launch_codes(B, H, W, C1, C2, Cout, k, stride, padding, act, ups)
+            assert got == (k_fwd, k_wgrad, k_dgrad), 'forward / weight gradient / data gradient ran on %s' % (got,)
+
+
+# ======================================================================================================================
+# 2. direct weight-gradient calls: slabs, accumulation, the two-level reduction (device only)
+# ======================================================================================================================
+# B, H, W, C1, C2, Cout, k, stride, padding, ups | family, S (slabs the launch stages)
+WGRAD_DIRECT = [
+    # ---- conv_wgrad_kernel (generic)
+    pytest.param(1, 10, 12, 3, 0, 5, 3, 1, 'same', 0, 8, 1, id='generic-S1-M120-KN135'),
+    pytest.param(3, 41, 39, 6, 0, 10, 3, 1, 'same', 0, 8, 10, id='generic-S10-chunk480-last477'),
+    # S = 67: groups of 32, 32 and 3; K * Cout = 135 -> 33 float4 + a scalar tail of 3; chunk 512, last slab 408
+    pytest.param(1, 190, 180, 3, 0, 5, 3, 1, 'same', 0, 8, 67, id='generic-S67-groups-32-32-3-KN135-tail3'),
+    # M = 31862, K = 6400: 50 K tiles -> S = ceil(3072 / 50) = 62 < ceil(M / 512) = 63; chunk = ceil(31862 / 62) = 514 -> 544; 59 * 544 = 32096 > M:
+    # slab 58 holds 310 pixels, slabs 59..61 are empty and must be written as zeros
+    pytest.param(1, 183, 182, 256, 0, 5, 5, 1, 'valid', 0, 8, 62, id='generic-S62-chunk544-slabs-59-61-empty'),
+    # ---- conv_wgrad_fast_kernel
+    pytest.param(1, 9, 9, 16, 0, 8, 3, 2, 'valid', 0, 7, 1, id='fast-S1-M16-two-K-tiles'),
+    pytest.param(4, 67, 67, 16, 0, 32, 3, 2, 'valid', 0, 7, 9, id='fast-S9-last260-18-blocks'),
+    pytest.param(1, 183, 183, 16, 0, 8, 3, 1, 'same', 0, 7, 66, id='fast-S66-groups-32-32-2-chunk512-last209-132-blocks'),     # Wo % 4 = 3: not transposed
+    pytest.param(1, 221, 221, 16, 0, 8, 3, 1, 'same', 0, 7, 96, id='fast-S96-three-full-groups-chunk512-last201-192-blocks'),   # M = 48841
+    # the same empty slabs on the XCD-remapped 1-D grid: 50 K tiles * 62 slabs = 3100 blocks (3100 % 8 = 4); 8.2 GFLOP per pass of the fp64 oracle,
+    # 0.9 s on 16 threads
+    pytest.param(1, 183, 182, 256, 0, 20, 5, 1, 'valid', 0, 7, 62, id='fast-S62-chunk544-slabs-59-61-empty-3100-blocks'),
+    # ---- conv_wgrad_tr_kernel
+    pytest.param(1, 8, 12, 16, 0, 20, 3, 1, 'same', 0, 6, 1, id='tr-S1-M96'),
+    pytest.param(2, 18, 20, 32, 32, 72, 3, 1, 'same', 0, 6, 5, id='tr-192x128-two-inputs-S5-last80'),
+    pytest.param(1, 26, 44, 16, 0, 48, 3, 1, 'same', 1, 6, 8, id='tr-128x64-upsampled-S8-last24'),
+    pytest.param(2, 96, 92, 16, 0, 20, 3, 1, 'same', 0, 6, 111, id='tr-S111-groups-32-32-32-15-last64'),
+    # ---- conv_wgrad_tr_anyw_kernel
+    pytest.param(1, 16, 14, 32, 0, 64, 4, 2, 'valid', 0, 14, 1, id='anyw-S1-M42-stride2'),
+    pytest.param(1, 100, 99, 32, 0, 516, 1, 1, 'same', 0, 14, 45, id='anyw-S45-chunk224-last44'),
+    pytest.param(1, 160, 154, 4, 0, 132, 3, 1, 'same', 0, 14, 110, id='anyw-S110-groups-32-32-32-14-KN4752'),
+]
+
+
+def _wgrad_geometry(H, W, k, stride, padding):
+    return P._conv_geometry(H, W, k, k, stride, padding)
+
+
+@functools.lru_cache(maxsize=None)
+def _wgrad_problem(B, H, W, C1, C2, Cout, k, stride, padding, ups):
+    """operands (CPU, fp32) and the fp64 oracle's weight gradient of one geometry, computed once for accumulate = 0 and 1"""
+    Ho, Wo, _, _ = _wgrad_geometry(H, W, k, stride, padding)
+    x1 = rnd(B, H // 2 if ups else H, W // 2 if ups else W, C1, seed=1)
+    x2 = rnd(B, H, W, C2, seed=2) if C2 else None
+    dy = rnd(B, Ho, Wo, Cout, seed=3)
+    base = rnd(k, k, C1 + C2, Cout, seed=4) * 0.1
+    a = x1.double()
+    if ups:
+        a = O.upsample2(a)
+    if C2:
+        a = torch.cat([a, x2.double()], -1)
+    wref = torch.zeros(k, k, C1 + C2, Cout, dtype=torch.float64, requires_grad=True)
+    O.conv2d(a, wref, None, stride=stride, padding=padding).backward(dy.double())
+    return x1, x2, dy, base, wref.grad
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('acc', [0, 1], ids=['overwrite', 'accumulate'])
+@pytest.mark.parametrize('B,H,W,C1,C2,Cout,k,stride,padding,ups,family,S', WGRAD_DIRECT)
+def test_wgrad_slabs_direct(B, H, W, C1, C2, Cout, k, stride, padding, ups, family, S, acc):
+    """mmseg_conv2d_wgrad on the four weight-gradient families of the fp32 stack against the fp64 oracle's autograd: NaN-filled workspace of exactly
+    mmseg_conv2d_wgrad_workspace floats, dW NaN (accumulate 0) or a known base (accumulate 1).  The launch stages exactly the S slabs its id claims
+    (+ ceil(S / 32) partial sums above 64): that prefix of the workspace is finite afterwards, everything behind it still NaN, and with S = 1 and
+    accumulate 0 nothing is staged at all.  Slabs whose pixel range is empty hold zeros.  A second call is bitwise equal to the first."""
+    dev = 'cuda'
+    Ho, Wo, ph, pw = _wgrad_geometry(H, W, k, stride, padding)
+    x1c, x2c, dyc, basec, ref = _wgrad_problem(B, H, W, C1, C2, Cout, k, stride, padding, ups)
+    x1, dy, base = x1c.to(dev), dyc.to(dev), basec.to(dev)
+    x2 = x2c.to(dev) if C2 else None
+    Cin, M = C1 + C2, B * Ho * Wo
+    KN = k * k * Cin * Cout
+    with _fp32_default_mode():
+        need = N.call('mmseg_conv2d_wgrad_workspace', B, Ho, Wo, Cin, Cout, k, k)
+        staged = 0 if (S == 1 and not acc) else (S + ((S + 31) // 32 if S > 64 else 0)) * KN
+        assert need >= max(staged, KN)
+        outs = []
+        for _ in range(2):
+            ws = torch.full((need,), float('nan'), device=dev)
+            dw = base.clone() if acc else torch.full_like(base, float('nan'))
+            N.call('mmseg_conv2d_wgrad', x1, x2, dy, dw.view(-1), ws, ws.numel(), B, H, W, C1, C2, Ho, Wo, Cout, k, k, stride, ph, pw, ups, acc)
+            fam = _last() // 1000000
+            assert fam == family, 'launch went to kernel family %d' % fam
+            outs.append(dw)
+        nan = torch.isnan(ws)
+        assert not nan[:staged].any(), 'a staged slab (or first-level partial sum) was not written'
+        assert nan[staged:].all(), 'the launch wrote behind its %d slabs' % S
+        chunk = ((M + S - 1) // S + 31) // 32 * 32
+        if family in (7, 8) and S > 1:
+            for s in range(S):
+                if s * chunk >= M:
+                    assert not ws[s * KN:(s + 1) * KN].any(), 'slab %d covers no pixel and must hold zeros' % s
+        want = ref + (basec.double() if acc else 0.0)
+        scale = float(want.abs().max())
+        err = float((outs[0].cpu().double() - want).abs().max())
+        print('wgrad direct: max err %.3e, bound %.3e' % (err, 2e-5 * scale))
+        assert not torch.isnan(outs[0]).any()
+        assert err <= 2e-5 * scale
+        assert torch.equal(outs[0], outs[1]), 'fixed slab order and fixed-order reduction: bitwise reproducible'
+
+
+# ======================================================================================================================
+# 3. refusals: an error before any launch, outputs untouched
+# ======================================================================================================================
+def _untouched(t):
+    return bool(torch.isnan(t).all())
+
+
+def test_conv2d_fwd_refuses_a_missing_kernel_off_the_fast_path(device):
+    """a caller that only prepared the fast-path image `wt` must not fall through to the generic kernels, which read the Keras-layout `w`
+    (8 input channels: not a fast-path geometry)"""
+    B, H, W, C1, Cout = 1, 6, 8, 8, 12
+    x = rnd(B, H, W, C1, seed=1).to(device)
+    wt = rnd(Cout, 9, C1, seed=2).reshape(-1).to(device)
+    y = torch.full((B, H, W, Cout), float('nan'), device=device)
+    with _fp32_default_mode():
+        with pytest.raises(_native_error()):
+            N.call('mmseg_conv2d_fwd', x, None, None, wt, None, y, None, B, H, W, C1, 0, H, W, Cout, 3, 3, 1, 1, 1, 0, 0, 0, 0.0, 0)
+    assert _untouched(y)
+
+
+@pytest.mark.gpu
+def test_conv_entry_points_refuse_what_their_kernels_cannot_run():
+    dev = 'cuda'
+    nanlike = lambda *s: torch.full(s, float('nan'), device=dev)
+    with _fp32_default_mode():
+        # ---- a strided output mapping (one parity class of a data gradient) exists on the fast path only: 16 gradient channels are off it
+        B, Ho, Wo, Cout, H, W, Cin = 1, 5, 5, 16, 12, 12, 8
+        dy, wt, dx = rnd(B, Ho, Wo, Cout, seed=1).to(dev), rnd(4 * Cout * Cin, seed=2).to(dev), nanlike(B, H, W, Cin)
+        with pytest.raises(_native_error()):
+            N.call('mmseg_conv2d_dgrad_parity', dy, wt, dx, B, Ho, Wo, Cout, H, W, Cin, 2, 2, 2, 0, 0)
+        assert _untouched(dx)
+        # ---- 16-bit tensors with the fp32 precision set (io != 0), forward and weight gradient
+        B, H, W, C1, Cout = 1, 8, 8, 32, 32
+        xh, w = rnd(B, H, W, C1, seed=3).to(dev).bfloat16(), rnd(3, 3, C1, Cout, seed=4).to(dev)
+        wt, y = torch.empty(w.numel(), device=dev), nanlike(B, H, W, Cout)
+        N.call('mmseg_conv2d_wprep', w, wt, 3, 3, C1, Cout, 0)
+        with pytest.raises(_native_error()):
+            N.call('mmseg_conv2d_fwd_t', xh, None, w, wt, None, y, None, B, H, W, C1, 0, H, W, Cout, 3, 3, 1, 1, 1, 0, 0, 0, 0.0, 0, 1)
+        assert _untouched(y)
+        need = N.call('mmseg_conv2d_wgrad_workspace', B, H, W, C1, Cout, 3, 3)
+        ws, dw, g = nanlike(need), nanlike(3, 3, C1, Cout), rnd(B, H, W, Cout, seed=5).to(dev)
+        with pytest.raises(_native_error()):
+            N.call('mmseg_conv2d_wgrad_t', xh, None, g, dw.view(-1), ws, ws.numel(), B, H, W, C1, 0, H, W, Cout, 3, 3, 1, 1, 1, 0, 0, 1)
+        assert _untouched(dw) and _untouched(ws)
+        # ---- a workspace one float short of mmseg_conv2d_wgrad_workspace
+        x = rnd(B, H, W, C1, seed=3).to(dev)
+        with pytest.raises(_native_error()):
+            N.call('mmseg_conv2d_wgrad', x, None, g, dw.view(-1), ws[:need - 1], need - 1, B, H, W, C1, 0, H, W, Cout, 3, 3, 1, 1, 1, 0, 0)
+        assert _untouched(dw) and _untouched(ws)
+        # ---- a 16-bit input off the fast path (bf16 products set, so that io itself is allowed): 8 input channels
+        prev = P.set_conv_precision('bf16')
+        try:
+            x8, w8, y8 = rnd(B, H, W, 8, seed=6).to(dev).bfloat16(), rnd(3, 3, 8, 12, seed=7).to(dev), nanlike(B, H, W, 12)
+            with pytest.raises(_native_error()):
+                N.call('mmseg_conv2d_fwd_t', x8, None, w8, None, None, y8, None, B, H, W, 8, 0, H, W, 12, 3, 3, 1, 1, 1, 0, 0, 0, 0.0, 0, 1)
+            assert _untouched(y8)
+        finally:
+            P.set_conv_precision(prev)
+        # ---- the batched parity classes: stride 2, Cout % 32 == 0, Cin % 4 == 0 only
+        for (Cout, Cin, stride) in ((32, 8, 3), (48, 8, 2), (32, 6, 2)):
+            B, H, W = 1, 10, 10
+            Ho = (H - 4) // stride + 1
+            dy, wp, dx = rnd(B, Ho, Ho, Cout, seed=8).to(dev), rnd(16 * Cout * Cin, seed=9).to(dev), nanlike(B, H, W, Cin)
+            with pytest.raises(_native_error()):
+                N.call('mmseg_conv2d_dgrad_parity_all', dy, wp, dx, B, Ho, Ho, Cout, H, W, Cin, 4, 4, stride)
+            assert _untouched(dx)
+        # ---- the first discriminator layer's direct data gradient: Cout = 64 and Cin in {1, 4} only
+        for (Cout, Cin) in ((32, 4), (64, 2), (64, 8)):
+            B, H, W, Ho = 1, 10, 10, 4
+            dy, w, dx = rnd(B, Ho, Ho, Cout, seed=10).to(dev), rnd(4, 4, Cin, Cout, seed=11).to(dev), nanlike(B, H, W, Cin)
+            with pytest.raises(_native_error()):
+                N.call('mmseg_conv2d_dgrad_s2k4_smallc', dy, w, dx, B, H, W, Cin, Ho, Ho, Cout)
+            assert _untouched(dx)
+
+
+# ======================================================================================================================
+# 4. which kernel each case of CONV_CASES runs
+# ======================================================================================================================
+# (forward, weight gradient, data gradient) of CONV_CASES, in its order; recorded on an MI355X and checked by hand against conv_dispatch,
+# conv2d_wgrad_impl and ops._Conv2d.backward
+CONV_CASES_KERNELS = [
+    (1064064, 6192064, 1064064),       # 2x16x16 64->64 3x3
+    (11076001, 13076001, 2628032),     # 2x20x12 1->64 3x3: smallk<3,1,16>; data gradient 64 -> 1: flipped kernel, generic 16-byte <128,32>
+    (3008008, 7128032, 3008008),       # 2x16x16 8->8: direct kernel; W % 64 != 0 and S = 1 keep the weight gradient off conv_wgrad_c8m_kernel
+    (1064064, 6628064, 1064064),       # 1x16x16 64+64->64: K = 1152 -> 128-row K tile, two inputs
+    (1064064, 6128064, 1064064),       # 2x16x16 128->64 up-sampled
+    (21016016, 22016016, 21016009),    # 2x33x33 8+1->16 stride 2: s2conv.hpp
+    (2564064, 14128064, 5004064),      # 2x34x30 4->64 4x4 stride 2: generic 16-byte <64,64>, any-width weight gradient, D_Mask's direct data gradient
+    (1064064, 14128128, 4064064),      # 2x16x16 64->128 4x4 stride 2
+    (1064064, 14128128, 1064064),      # 2x9x9 64->128 4x4 stride 1: Wo = 6
+    (23016020, 24016020, 23020016),    # 2x20x20 8+8->20 5x5: locnet5 (data gradient: 20 -> 16 with a split store)
+    (23016020, 24016020, 23020016),    # 3x9x12
+    (23016020, 24016020, 23020016),    # 1x40x70
+    (23020020, 7128032, 23020020),     # 2x18x22 20->20 5x5: Wo = 18 -> conv_wgrad_fast_kernel, S = 1
+    (23020020, 6128032, 23020020),     # 1x13x80 20->20 5x5: Wo = 76 -> transposed staging
+    (10008008, 12008008, 11036008),    # 2x16x16 64->8 1x1: pw_reduce<8,8>; data gradient 8 -> 64 1x1: smallk<1,8,16>
+    (10016005, 12016005, 11036005),    # 2x16x16 64->5 1x1
+    (10002001, 12002001, 11022001),    # 2x16x16 8->1 1x1: data gradient 1 -> 8: smallk<1,1,2>
+    (11096001, 13096001, 5001064),     # 1x12x12 1->64 4x4 stride 2
+    (1064064, 6128128, 1064064),       # 2x8x8 256->512
+    (1128128, 18001004, 1128064),      # 3x128x128 64->128: tiles_big = 384; wgrad32h_kernel<1,4>; data gradient 128 -> 64: tiles_mid = 384 (H % 16 = 0 but
+                                       # 96 blocks of 512 pixels do not fill conv16h_kernel's grid)
+    (3008008, 9008008, 3008008),       # 2x128x128 8->8: 64 slabs
+    (3008008, 9008008, 3008008),       # 3x16x192 8->8
+    (10016005, 12016005, 11036005),    # 2x96x96 64->5 1x1
+    (11096001, 13096001, 5001064),     # 2x33x31 1->64 4x4 stride 2
+    (2628032, 7128032, 4128032),       # 2x33x33 16->32 stride 2: S = 1, 2 blocks
+    (1064064, 14128128, 4064064),      # 2x31x31 64->128 4x4 stride 2
+    (2564064, 14128064, 1064064),      # 2x18x22 8->64: Wo = 22; data gradient: 1x1 product 64 -> 72 over the taps + tap sum
+    (1128032, 7128032, 2564064),       # 3x17x19 64->8: data gradient 8 -> 64 3x3 with the flipped kernel (8 % 32 != 0: generic)
+    (2628032, 8628032, 11022005),      # 3x17x19 8->5 1x1: generic 16-byte forward and weight gradient (5 % 4 != 0); data gradient 5 -> 8: smallk<1,5,2>
+    (2564064, 14128064, 1064064),      # 2x20x21 8->64 'valid': Wo = 19
+    (2628032, 6128032, 1064064),       # 2x16x20 4->32: data gradient 32 -> 36 over the taps
+    (2564064, 6128128, 1064064),       # 1x24x24 16->128: data gradient 128 -> 144 over the taps on <64,64>
+    (10016005, 12016005, 11036005),    # 3x17x19 64->5 1x1
+    (10008008, 12008008, 11036008),    # 3x17x19 64->8 1x1
+    (10002001, 12002001, 11022001),    # 5x13x11 8->1 1x1
+    (10004001, 12004001, 11024001),    # 3x15x9 16->1 1x1: data gradient 1 -> 16: smallk<1,1,4>
+    (11076001, 13076001, 2628032),     # 3x17x19 1->64 3x3
+    (11096001, 13096001, 5001064),     # 2x37x41 1->64 4x4 stride 2
+    (11064001, 13064001, 2628032),     # 2x19x23 1->16 3x3: smallk<3,1,4>
+    (10016005, 12016005, 11036005),    # 1x70x70 64->5 1x1
+    (1064064, 14128128, 4064064),      # 3x64x60 64->128 4x4 stride 2
+    (1064064, 14128128, 1064064),      # 3x30x30 64->256 4x4 stride 1: Wo = 27
+    (21016016, 22016016, 21016009),    # 3x20x37 8+1->16 stride 2
+    (21016016, 22016016, 21016009),    # 1x64x64
+    (21016016, 22016016, 21016009),    # 5x7x9
+]
+
+
+@pytest.mark.gpu
+def test_conv_cases_run_on_the_kernels_recorded_for_them():
+    """CONV_CASES of tests/test_ops_parity.py, unchanged, against the committed table of the kernels their forward, weight-gradient and
+    data-gradient launches take: a dispatcher change that moves a case onto another kernel (and leaves the kernel it was written for without a
+    test) fails here and has to move the table -- and find the orphaned kernel a case -- on purpose"""
+    assert len(CONV_CASES_KERNELS) == len(CONV_CASES)
+    moved = []
+    with _fp32_default_mode():
+        for case, want in zip(CONV_CASES, CONV_CASES_KERNELS):
+            got = _launch_codes(*case)
+            print(case, got)
+            if got != want:
+                moved.append((case, got, want))
+    assert not moved, 'cases that run on other kernels than recorded (case, got, recorded): %s' % (moved,)
