@@ -649,7 +649,8 @@ def test_node_of_the_8_channel_conv_uses_the_one_launch_kernel_and_matches_the_i
         N.call('mmseg_conv16_mode', prev)
 
 
-@pytest.mark.parametrize('B,H,W,act', [(2, 20, 23, 2), (1, 64, 64, 2), (3, 9, 12, 0), (1, 5, 5, 2)])
+@pytest.mark.parametrize('B,H,W,act', [(2, 20, 23, 2), (1, 64, 64, 2), (3, 9, 12, 0), (1, 5, 5, 2),
+                                       (130, 13, 69, 2)])      # 520 tiles on the 512 blocks of the grid: blocks 0 .. 7 walk a second tile
 def test_locnet_first_layer_in_the_16bit_modes(B, H, W, act, mode):
     """locnet5_fwd_kernel (s2conv.hpp): Conv2D(20, 5, 'valid') + LeakyReLU(0.3) over Concatenate([anatomy 1, anatomy 2]) (stn_spline.py:102-107) --
     fp32 tensors, operands rounded to the 16-bit type on the way into v_mfma_f32_16x16x32_*: against the fp64 oracle on the rounded operands
@@ -675,7 +676,10 @@ def test_locnet_first_layer_in_the_16bit_modes(B, H, W, act, mode):
     assert float((y.cpu().double() - ref0).abs().max()) <= 2e-5 * float(ref0.abs().max())
 
 
-@pytest.mark.parametrize('B,H,W,C,Cout,pad,split', [(2, 18, 22, 20, 20, 0, False), (1, 13, 80, 20, 20, 4, False), (2, 16, 19, 20, 16, 4, True)])
+@pytest.mark.parametrize('B,H,W,C,Cout,pad,split', [(2, 18, 22, 20, 20, 0, False), (1, 13, 80, 20, 20, 4, False), (2, 16, 19, 20, 16, 4, True),
+                                                    # 130 x 2 x 2 = 520 tiles of 8 x 64 on 512 blocks (Ho x Wo = 9 x 65 and, padded, 13 x 69): a second trip
+                                                    # (the last: the split store of the first layer's data gradient, 8 + 8, on a second trip)
+                                                    (130, 13, 69, 20, 20, 0, False), (130, 9, 65, 20, 20, 4, False), (130, 9, 65, 20, 16, 4, True)])
 def test_locnet_other_layers_round_their_operands_in_the_16bit_modes(B, H, W, C, Cout, pad, split, mode):
     """locnet5_f32_kernel<..., PREC> (s2conv.hpp): the second / third 5 x 5 layer, its data gradient (padding 4) and the first layer's data
     gradient (16 outputs written to two 8-channel tensors) multiply on the fp32 MFMA in every mode; in the 16-bit modes their operands are

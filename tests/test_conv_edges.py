@@ -47,9 +47,10 @@ test_conv_cases_run_on_the_kernels_recorded_for_them pins; new = CONV_EDGES belo
   conv_wgrad_fast_kernel    <128,128> new 2x35x35 64->128   <128,64> new 1x135x135 64->64, 2x91x91 32+32->64   <128,32> old 2x33x33 16->32, new 4x67x67 16->32
   conv_wgrad_kernel 16-byte <128,64> new 2x21x19 8->34   <128,32> old 3x17x19 8->5, new 3x41x39 8->6
                     scalar  <128,64> new 1x160x154 3->130   <128,32> new 3x41x39 6->10
-  outside this stack (their own tests are CONV_CASES and tests/test_act16.py): conv_direct_mfma_kernel 3, conv_dgrad_s2k4_smallc_kernel 5,
-  conv_wgrad_c8m_kernel 9 (new 3x128x128 8->8: 96 slabs), pw_reduce 10 / 12, smallk 11 / 13, s2k3c9 21 / 22, locnet5 23 / 24, wgrad32h_kernel 18
-  (old 3x128x128 64->128); conv16h_kernel<PREC 0> (17) needs >= 192 blocks of 256 pixels in mode 1, i.e. M >= 49152 at 64+ channels (above the
+  outside this stack: conv_direct_mfma_kernel 3, conv_dgrad_s2k4_smallc_kernel 5, pw_reduce 10 / 12, smallk 11 / 13, s2k3c9 21 / 22 and
+  locnet5 23 / 24 have tests/test_special_conv_edges.py (capped grids, second trips of the tile loops, their own slab counts; besides CONV_CASES
+  and tests/test_act16.py); conv_wgrad_c8m_kernel 9 (new 3x128x128 8->8: 96 slabs), wgrad32h_kernel 18 (old 3x128x128 64->128);
+  conv16h_kernel<PREC 0> (17) needs >= 192 blocks of 256 pixels in mode 1, i.e. M >= 49152 at 64+ channels (above the
   size limit of this file): tests/test_act16.py forces it onto small problems with mode 2.  The measurement-build instances (conv_direct_kernel,
   conv_wgrad_c8_kernel, forced tiles) are selected by environment switches only and are not part of the product's dispatch.
 

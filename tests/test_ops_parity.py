@@ -631,7 +631,8 @@ def _bf16(t, dt=torch.bfloat16):
     (2, 16, 16, 64, 0, 64, 3, 1, 'same', False), (2, 32, 32, 128, 0, 128, 3, 1, 'same', False),
     (2, 16, 16, 64, 64, 64, 3, 1, 'same', False), (2, 16, 16, 128, 0, 64, 3, 1, 'same', True),
     (2, 8, 8, 256, 0, 512, 3, 1, 'same', False), (2, 16, 16, 64, 0, 128, 4, 2, 'valid', False),
-    (3, 24, 24, 64, 0, 8, 1, 1, 'same', False), (3, 17, 19, 64, 0, 5, 1, 1, 'same', False), (3, 17, 19, 8, 0, 1, 1, 1, 'same', False)])
+    (3, 24, 24, 64, 0, 8, 1, 1, 'same', False), (3, 17, 19, 64, 0, 5, 1, 1, 'same', False), (3, 17, 19, 8, 0, 1, 1, 1, 'same', False),
+    (1, 363, 363, 64, 0, 8, 1, 1, 'same', False)])     # round16 in pw_reduce_kernel (+ its 65-slab weight gradient) and in smallk_conv_kernel at the 2048-block cap
 def test_conv2d_bf16_precision(B, H, W, Cin, C2, Cout, k, stride, padding, ups, mode):
     """mmseg_set_conv_precision(1): forward and data gradient == the fp64 oracle on bf16-rounded operands (the products are
     then exact, only the fp32 accumulation differs); the same for the weight gradient."""
