@@ -103,6 +103,33 @@ int mmseg_conv2d_dgrad_s2k4_smallc(const float* dy, const float* w, float* dx, i
  * mmseg_conv2d_wprep_parity back to back in (ph, pw) raster order */
 int mmseg_conv2d_dgrad_parity_all(const float* dy, const float* wt_all, float* dx, int B, int Ho, int Wo, int Cout, int H, int W,
                                   int Cin, int KH, int KW, int stride, void* stream);
+/* ---- UpSampling2D(2) -> Conv2D(3, 'same') of the UNet up path (models/unet.py:67-82) with the up-sampling folded into the weights:
+ * output pixels of parity class (py, px) see 2 x 2 distinct pixels of x, so 4 of the 9 multiplications remain.
+ * Process-wide switch, modelled on mmseg_conv16_mode: 0 = never, 1 (default) = the inference forward only, where the channel conditions
+ * hold and the class grid fills the chip, 2 = every direction wherever the channel conditions hold.  (The folded sums round differently
+ * from the nine-tap ones; the default keeps the training directions' results bit for bit, while the inference passes end in the anatomy
+ * encoder's Rounding layer.)  Returns the previous mode; other values only query. */
+int mmseg_conv2d_ups_fold_mode(int mode);
+/* 1 when the layer x [B,H1,W1,C1] -> y [B,2H1,2W1,Cout] (models/unet.py:67-82) takes the folded route in direction dir (0 training
+ * forward, 1 data gradient, 2 weight gradient, 3 folded-BN inference forward): fp32 precision mode, C1 % 32 == 0, Cout % 32 == 0,
+ * Cout > 32, every tensor below 2^31 bytes; in mode 1 also dir == 3 and 4 * ceil(B*H1*W1 / 128) * ceil(Cout / 64) >= 384.  No launch. */
+int mmseg_conv2d_ups_fold_ok(int B, int H1, int W1, int C1, int Cout, int dir);
+/* weight images of such a layer (models/unet.py:67-82), w [3,3,C1,Cout], each element a sum of 1, 2 or 4 weights in a fixed order:
+ * which 0 = the four forward class images back to back in (py, px) raster order, each [Cout][2*2][C1] in the fast layout, tap (a, b) of
+ *           class (py, px) summing kernel rows R[py][a] and columns R[px][b], R[0] = [{0},{1,2}], R[1] = [{0,1},{2}];
+ * which 1 = the data-gradient image [C1][4*4][Cout], tap (u, v) summing rows U[u] and columns U[v], U = [{2},{1,2},{0,1},{0}]. */
+int mmseg_conv2d_wprep_ups(const float* w, float* out, int C1, int Cout, int which, void* stream);
+/* forward of such a layer (models/unet.py:67-82) as ONE batched launch of its four parity classes: class (py, px) is the 2 x 2 stride-1
+ * convolution of x with pad (1-py, 1-px) stored at y[:, 2i+py, 2j+px]; y = act(conv * oscale[c] + bias[c]) (oscale / bias may be NULL).
+ * wt_classes from mmseg_conv2d_wprep_ups(which 0).  fp32 mode only; C1 % 32 == 0, Cout % 4 == 0, 16-byte aligned x / wt_classes,
+ * tensors below 2^31 bytes -- otherwise refused.  The data gradient is mmseg_conv2d_fwd over dy with KH = KW = 4, stride 2, pad 1 and
+ * wt = mmseg_conv2d_wprep_ups(which 1); the weight gradient is mmseg_conv2d_wgrad of that convolution (x1 := dy, dy := x) followed by
+ * mmseg_conv2d_ups_wgrad_fold. */
+int mmseg_conv2d_fwd_ups_parity(const float* x, const float* wt_classes, const float* bias, const float* oscale, float* y, int B, int H1,
+                                int W1, int C1, int Cout, int act, float alpha, void* stream);
+/* weight gradient of such a layer (models/unet.py:67-82), second half: dW [3,3,C1,Cout] += sum_{u in KU[kh], v in KU[kw]} dWe[u][v][co][ci]
+ * with KU = [{2,3},{1,2},{0,1}] and dWe [4,4,Cout,C1] the weight gradient of the 4x4 stride-2 pad-1 convolution that maps dy to dx. */
+int mmseg_conv2d_ups_wgrad_fold(const float* dWe, float* dW, int C1, int Cout, void* stream);
 /* Data gradient of a stride-1 convolution with few input channels (segmentor c0 8 -> 64, the SPADE shared convolutions 8 -> 128:
  * model_components/segmentor.py:16, layers/spade.py:29), second half: dx = sum over the taps of the shifted planes of
  * T [B,Ho,Wo,KH*KW*Cin], which the caller computes with ONE 1x1 mmseg_conv2d_fwd over dy (wt = the Keras kernel itself read as

@@ -2301,6 +2301,70 @@ __global__ void wprep_parity_all_kernel(const float* __restrict__ w, float* __re
     }
 }
 
+// Weight images of an up-sampled 3x3 layer (mmseg_conv2d_fwd_ups_parity and its gradients).  One block = one 32 x 32 (ci, co) tile of
+// one image tap (blockIdx.z); every element is a sum of 1, 2 or 4 of the 3x3 weights, added kh-major in ascending order.
+//   which 0: the four forward classes back to back in (py, px) raster order, class image [Cout][2*2][C1]:
+//            out[cls][co][a*2+b][ci] = sum_{kh in R[py][a], kw in R[px][b]} w[kh][kw][ci][co], R[0] = [{0},{1,2}], R[1] = [{0,1},{2}]
+//            (blockIdx.z = cls * 4 + a * 2 + b; transposed through LDS)
+//   which 1: the 4x4 stride-2 data-gradient image [C1][4*4][Cout]:
+//            out[ci][u*4+v][co] = sum_{kh in U[u], kw in U[v]} w[kh][kw][ci][co], U = [{2},{1,2},{0,1},{0}]   (blockIdx.z = u * 4 + v)
+__global__ __launch_bounds__(256) void wprep_ups_kernel(const float* __restrict__ w, float* __restrict__ out, int C1, int Cout, int which) {
+    __shared__ float t[32][33];
+    const int co0 = blockIdx.x * 32, ci0 = blockIdx.y * 32, z = blockIdx.z;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    int h0, h1, w0, w1;
+    if (which == 0) {
+        const int py = z >> 3, px = (z >> 2) & 1, a = (z >> 1) & 1, b = z & 1;
+        h0 = a ? 1 + py : 0; h1 = a ? 2 : py;
+        w0 = b ? 1 + px : 0; w1 = b ? 2 : px;
+    } else {
+        const int u = z >> 2, v = z & 3;
+        h0 = u < 2 ? 2 - u : 0; h1 = u < 1 ? 2 : 3 - u;
+        w0 = v < 2 ? 2 - v : 0; w1 = v < 1 ? 2 : 3 - v;
+    }
+    for (int rr = ty; rr < 32; rr += 8) {
+        const int ci = ci0 + rr, co = co0 + tx;
+        float s = 0.f;
+        if (ci < C1 && co < Cout)
+            for (int kh = h0; kh <= h1; ++kh)
+                for (int kw = w0; kw <= w1; ++kw) s += w[((size_t)(kh * 3 + kw) * C1 + ci) * Cout + co];
+        if (which == 0) t[rr][tx] = s;
+        else if (ci < C1 && co < Cout) out[((size_t)ci * 16 + z) * Cout + co] = s;
+    }
+    if (which != 0) return;
+    __syncthreads();
+    const int cls = z >> 2, tap = z & 3;
+    float* o = out + (size_t)cls * 4 * C1 * Cout;
+    for (int rr = ty; rr < 32; rr += 8) {
+        const int co = co0 + rr, ci = ci0 + tx;
+        if (co < Cout && ci < C1) o[((size_t)co * 4 + tap) * C1 + ci] = t[tx][rr];
+    }
+}
+
+// dW[kh][kw][ci][co] += sum_{u in KU[kh], v in KU[kw]} dWe[u][v][co][ci], KU = [{2,3},{1,2},{0,1}]: the weight gradient of the 4x4 stride-2
+// convolution over the output gradient (dWe [4,4,Cout,C1]) folded back onto the 3x3 kernel; one block = one 32 x 32 tile of one tap
+// (blockIdx.z = kh * 3 + kw), transposed through LDS, the four terms added in (u, v) raster order
+__global__ __launch_bounds__(256) void ups_wgrad_fold_kernel(const float* __restrict__ dWe, float* __restrict__ dW, int C1, int Cout) {
+    __shared__ float t[32][33];
+    const int co0 = blockIdx.x * 32, ci0 = blockIdx.y * 32;
+    const int kh = blockIdx.z / 3, kw = blockIdx.z % 3;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int u0 = 2 - kh, v0 = 2 - kw;
+    for (int rr = ty; rr < 32; rr += 8) {
+        const int co = co0 + rr, ci = ci0 + tx;
+        float s = 0.f;
+        if (co < Cout && ci < C1)
+            for (int u = u0; u <= u0 + 1; ++u)
+                for (int v = v0; v <= v0 + 1; ++v) s += dWe[((size_t)(u * 4 + v) * Cout + co) * C1 + ci];
+        t[rr][tx] = s;
+    }
+    __syncthreads();
+    for (int rr = ty; rr < 32; rr += 8) {
+        const int ci = ci0 + rr, co = co0 + tx;
+        if (ci < C1 && co < Cout) dW[((size_t)blockIdx.z * C1 + ci) * Cout + co] += t[tx][rr];
+    }
+}
+
 #include "wgrad32h.hpp"
 
 extern "C" {
@@ -2475,6 +2539,68 @@ int mmseg_conv2d_dgrad_parity_all(const float* dy, const float* wt_all, float* d
         return launch_fast_batched<64, 64, 2, 2>(pb, n, st);
     }
     return launch_fast_batched<128, 32, 4, 1>(pb, n, st);
+}
+
+// ---- nearest x2 up-sampling folded into the 3x3 'same' convolution that follows it (the UNet up path u3..u0) ------------------
+// After the up-sampling neighbouring taps read the same source pixel: output pixels of parity class (py, px) see only 2 x 2 distinct
+// pixels of x, so each class is an exact 2 x 2 stride-1 convolution of x with sums of the 3 x 3 weights (4 of 9 multiplications).
+// 0 = never; 1 (default) = the inference forward only, where the channel conditions hold and the class grid fills the chip; 2 = every
+// direction wherever the channel conditions hold.  The default keeps the training directions on the nine-tap kernels because results must
+// stay what they were: the folded sums are exact algebra but round differently, and Adam's first steps turn last-bit differences of
+// noise-level gradients (the biases in front of a BatchNorm) into +-lr weight differences.  The inference passes (the fake pools) end in the
+// Rounding layer of the anatomy encoder, so their last-bit differences do not reach the step's losses or weights.
+static int g_ups_fold_mode = 1;
+int mmseg_conv2d_ups_fold_mode(int mode) {
+    const int old = g_ups_fold_mode;
+    if (mode >= 0 && mode <= 2) g_ups_fold_mode = mode;
+    return old;
+}
+// The one place that decides whether an up-sampled 3x3 layer x [B,H1,W1,C1] -> y [B,2H1,2W1,Cout] takes the folded route;
+// dir: 0 training forward, 1 data gradient, 2 weight gradient, 3 inference forward (BatchNorm folded into the epilogue).
+int mmseg_conv2d_ups_fold_ok(int B, int H1, int W1, int C1, int Cout, int dir) {
+    if (g_ups_fold_mode == 0 || g_conv_bf16 != 0 || dir < 0 || dir > 3) return 0;
+    if (B < 1 || H1 < 1 || W1 < 1 || C1 < 32 || C1 % 32 != 0 || Cout % 32 != 0 || Cout <= 32) return 0;
+    const long lim = (1L << 31) - 64;
+    const long M = (long)B * H1 * W1;
+    if (M * C1 * 4 >= lim || 4 * M * Cout * 4 >= lim || 16L * C1 * Cout * 4 >= lim) return 0;
+    if (g_ups_fold_mode == 2) return 1;
+    if (dir != 3) return 0;
+    // the dispatcher's bar for a grid that fills the chip, counted over the four classes
+    if (4 * ((M + 127) / 128) * ((Cout + 63) / 64) < 384) return 0;
+    return 1;
+}
+// Forward: the four parity classes in ONE launch.  Class (py, px) writes y[:, 2i+py, 2j+px] from rows {i-1+py, i+py} and columns
+// {j-1+px, j+px} of x: KH = KW = 2, pad = (1-py, 1-px), strided output mapping.  wt_classes = mmseg_conv2d_wprep_ups(which 0).
+// bias / oscale / act / alpha as in mmseg_conv2d_fwd_scaled (oscale NULL: plain bias + activation).
+int mmseg_conv2d_fwd_ups_parity(const float* x, const float* wt_classes, const float* bias, const float* oscale, float* y, int B, int H1,
+                                int W1, int C1, int Cout, int act, float alpha, void* stream) {
+    if (g_conv_bf16 != 0 || B < 1 || H1 < 1 || W1 < 1 || C1 < 32 || C1 % 32 != 0 || Cout < 4 || Cout % 4 != 0) return (int)hipErrorInvalidValue;
+    const long lim = (1L << 31) - 64;
+    const long M = (long)B * H1 * W1;
+    if (!aligned16(x) || !aligned16(wt_classes) || M * C1 * 4 >= lim || 4L * C1 * Cout * 4 >= lim || 4 * M >= (1L << 31))
+        return (int)hipErrorInvalidValue;
+    ConvBatch pb;
+    for (int c = 0; c < 4; ++c) {
+        const int py = c >> 1, px = c & 1;
+        ConvParams& p = pb.p[c];
+        p.oH = 2 * H1; p.oW = 2 * W1; p.osh = 2; p.osw = 2; p.ooh = py; p.oow = px;
+        p.x1 = x; p.x2 = nullptr; p.w = nullptr; p.wt = wt_classes + (size_t)c * 4 * C1 * Cout; p.bias = bias; p.oscale = oscale;
+        p.y = y; p.y2 = nullptr;
+        p.B = B; p.H = H1; p.W = W1; p.C1 = C1; p.C2 = 0; p.H1 = H1; p.W1 = W1;
+        p.Ho = H1; p.Wo = W1; p.Cout = Cout; p.KH = 2; p.KW = 2; p.stride = 1;
+        p.pad_h = 1 - py; p.pad_w = 1 - px; p.ups = 0; p.transposed = 0; p.act = act; p.alpha = alpha;
+        p.M = (int)M; p.K = 4 * C1; p.nsplit1 = 0; p.io = 0;
+        p.qepi = quad_epilogue_ok(p);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const long tiles_big = ((M + 127) / 128) * ((Cout + 127) / 128) * 4;
+    if (Cout > 64 && tiles_big >= 384) return launch_fast_batched<128, 128, 2, 2>(pb, 4, st);
+    if (Cout > 32) {
+        const long tiles_mid = ((M + 127) / 128) * ((Cout + 63) / 64) * 4;
+        if (tiles_mid >= 384) return launch_fast_batched<128, 64, 2, 2>(pb, 4, st);
+        return launch_fast_batched<64, 64, 2, 2>(pb, 4, st);
+    }
+    return launch_fast_batched<128, 32, 4, 1>(pb, 4, st);
 }
 
 // number of floats of workspace mmseg_conv2d_wgrad needs for this geometry (0: writes dW directly)
@@ -2816,6 +2942,21 @@ int mmseg_conv2d_wprep_parity_all(const float* w, float* out, int KH, int KW, in
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(wprep_parity_all_kernel, dim3((unsigned)blocks, stride * stride), dim3(256), 0, (hipStream_t)stream, w, out, KH, KW, Cin, Cout,
                        stride, g_conv_bf16);
+    return MMSEG_CHECK_LAUNCH();
+}
+// weight images of an up-sampled 3x3 layer, w [3,3,C1,Cout]: which 0 = the four forward class images (4 * Cout * 4 * C1 floats, what
+// mmseg_conv2d_fwd_ups_parity reads), which 1 = the 4x4 stride-2 data-gradient image [C1][16 * Cout] (the `wt` of mmseg_conv2d_fwd over dy)
+int mmseg_conv2d_wprep_ups(const float* w, float* out, int C1, int Cout, int which, void* stream) {
+    if (g_conv_bf16 != 0 || (which != 0 && which != 1) || C1 < 1 || Cout < 1 || (C1 + 31) / 32 > 65535) return (int)hipErrorInvalidValue;
+    const dim3 grid((Cout + 31) / 32, (C1 + 31) / 32, 16);
+    hipLaunchKernelGGL(wprep_ups_kernel, grid, dim3(256), 0, (hipStream_t)stream, w, out, C1, Cout, which);
+    return MMSEG_CHECK_LAUNCH();
+}
+// dW [3,3,C1,Cout] += fold of dWe [4,4,Cout,C1] (ups_wgrad_fold_kernel)
+int mmseg_conv2d_ups_wgrad_fold(const float* dWe, float* dW, int C1, int Cout, void* stream) {
+    if (C1 < 1 || Cout < 1 || (C1 + 31) / 32 > 65535) return (int)hipErrorInvalidValue;
+    const dim3 grid((Cout + 31) / 32, (C1 + 31) / 32, 9);
+    hipLaunchKernelGGL(ups_wgrad_fold_kernel, grid, dim3(256), 0, (hipStream_t)stream, dWe, dW, C1, Cout);
     return MMSEG_CHECK_LAUNCH();
 }
 int mmseg_conv2d_wflip(const float* w, float* wt, int KH, int KW, int Cin, int Cout, void* stream) {

@@ -319,6 +319,40 @@ def _wprep_parity_all(w, KH, KW, Cin, Cout, stride, taps, wkey=None):
     return out
 
 
+def _wprep_ups(w, C1, Cout, which, wkey=None):
+    """Weight images of an up-sampled 3x3 layer with the up-sampling folded in (mmseg_conv2d_wprep_ups): which 0 = the four forward
+    class images (operand of mmseg_conv2d_fwd_ups_parity), which 1 = the 4x4 stride-2 data-gradient image; cached per weight version
+    like _wprep_parity_all."""
+    n = 16 * C1 * Cout
+    key = (wkey, w.data_ptr(), 'ups', which, _sid(w.device))
+    ent = _wprep_cache.get(key) if wkey is not None else None
+    if ent is not None and ent[0] == _wver(wkey) and ent[1].numel() == n:
+        return ent[1]
+    if wkey is None:
+        out = _ws('wprep_ups%d' % which, n, w.device)[:n]
+    else:
+        out = ent[1] if (ent is not None and ent[1].numel() == n) else torch.empty(n, dtype=torch.float32, device=w.device)
+    N.call('mmseg_conv2d_wprep_ups', w, out, C1, Cout, which)
+    if wkey is not None:
+        _wprep_cache[key] = (_wver(wkey), out)
+    return out
+
+
+def _ups_fold(x1, x2, w, stride, padding, ups, out_dtype):
+    """the layer is one the folded up-sampling route may take (UpSampling2D(2) -> 3x3 'same' convolution, one fp32 input on the MFMA
+    fast path); mmseg_conv2d_ups_fold_ok then decides per direction"""
+    if not (ups and x2 is None and stride == 1 and padding == 'same' and tuple(w.shape[:2]) == (3, 3)):
+        return False
+    if not (x1.dtype == w.dtype == out_dtype == torch.float32):
+        return False
+    return bool(N.call('mmseg_conv2d_fast_path', x1.shape[3], 0, w.shape[3], 0))
+
+
+def _ups_fold_ok(x1, Cout, direction):
+    B, H1, W1, C1 = x1.shape
+    return bool(N.call('mmseg_conv2d_ups_fold_ok', B, H1, W1, C1, Cout, direction))
+
+
 def _conv_fwd_raw(x1, x2, w, wt, bias, y, y2, B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, ups, transposed,
                   act, alpha, nsplit1):
     # host-side shape checks: the kernel trusts these numbers
@@ -394,7 +428,12 @@ class _Conv2d(torch.autograd.Function):
         Ho, Wo, ph, pw = _conv_geometry(H, W, KH, KW, stride, padding)
         y = _new((B, Ho, Wo, Cout), x1, out_dtype)
         prec = N.call('mmseg_get_conv_precision')
-        if prec and C1 == 8 and C2 == 0 and KH == 3 and KW == 3 and stride == 1 and not ups and (Ho, Wo, ph, pw) == (H, W, 1, 1) \
+        fold = _ups_fold(x1, x2, w, stride, padding, ups, out_dtype)
+        if fold and _ups_fold_ok(x1, Cout, 0):
+            # nearest x2 + 3x3: four parity classes, each a 2x2 convolution of x with summed weights -- 4 of the 9 multiplications
+            N.call('mmseg_conv2d_fwd_ups_parity', x1, _wprep_ups(w, C1, Cout, 0, wkey), bias, None, y, B, H1, W1, C1, Cout,
+                   ACT[act], float(alpha))
+        elif prec and C1 == 8 and C2 == 0 and KH == 3 and KW == 3 and stride == 1 and not ups and (Ho, Wo, ph, pw) == (H, W, 1, 1) \
                 and Cout % 64 == 0 and _h(x1) in (0, prec) and B * H * W * 96 * 2 < (1 << 31) - 64:
             # reduced-precision modes, 8 input channels (the SPADE units' shared convolution, the segmentor's first): K = 72 is three
             # gathers of the generic kernel per output tile; instead the 72 (+24 zero) operand columns of every pixel are written
@@ -416,6 +455,7 @@ class _Conv2d(torch.autograd.Function):
                           ACT[act], alpha, 0)
         ctx.geom = (B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, int(ups), ACT[act], alpha)
         ctx.wgrad, ctx.bgrad, ctx.wkey = wgrad, bgrad, wkey
+        ctx.fold = fold
         ctx.w = w     # plain (non-leaf) weight view: not tracked by autograd
         ctx.save_for_backward(x1, x2, y if ACT[act] else None)
         return y
@@ -447,10 +487,24 @@ class _Conv2d(torch.autograd.Function):
         if ctx.bgrad is not None and not bias_done:
             ws = _ws('colsum', N.call('mmseg_colsum_workspace_floats', M, Cout), dy.device)
             N.call('mmseg_colsum', g if _h(g) == 0 else g.float(), ctx.bgrad, ws, M, Cout, 1.0, 1)
-        if ctx.wgrad is not None:
+        fold = ctx.fold and g.dtype == torch.float32
+        if ctx.wgrad is not None and fold and _ups_fold_ok(x1, Cout, 2):
+            # folded up-sampling: the weight gradient of the 4x4 stride-2 convolution g -> dx (x in the role of its output gradient)
+            # into scratch, then folded onto the 3x3 kernel and added to the gradient-arena view
+            dwe = _ws('ups_dwe', 16 * C1 * Cout, g.device)[:16 * C1 * Cout]
+            _wgrad_launch(g, None, x1, dwe, B, H, W, Cout, 0, H // 2, W // 2, C1, 4, 4, 2, 1, 1, 0, 0)
+            N.call('mmseg_conv2d_ups_wgrad_fold', dwe, ctx.wgrad.view(-1), C1, Cout)
+        elif ctx.wgrad is not None:
             # accumulates straight into the gradient-arena view (the final slab reduction adds to it)
             _wgrad_launch(x1, x2, g, ctx.wgrad.view(-1), B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, ups, 1)
         _grad_done(ctx.wgrad, ctx.bgrad)
+        if need_x1 and fold and _ups_fold_ok(x1, Cout, 1):
+            # folded up-sampling: dx at the low resolution directly, one 4x4 stride-2 convolution over g with summed weights (no
+            # full-resolution gradient, no pooling pass)
+            dx1 = _new((B, H // 2, W // 2, C1), dy, x1.dtype)
+            _conv_fwd_raw(g, None, None, _wprep_ups(w, C1, Cout, 1, ctx.wkey), None, dx1, None, B, H, W, Cout, 0, H // 2, W // 2, C1,
+                          4, 4, 2, 1, 1, 0, 0, 0, 0.0, 0)
+            return (dx1, None) + (None,) * 12
         if need_x1 or (x2 is not None and need_x2):
             Cin = C1 + C2
             tr = 1 if stride > 1 else 0
@@ -524,6 +578,10 @@ def conv2d_bn_infer(x, w, cbias, gamma, beta, mov_mean, mov_var, relu=False, x2=
         if wkey is not None:
             _bnfold_cache[key] = ((_wver(wkey), _bn_state_version[0]), ss)
     y = _new((B, Ho, Wo, Cout), x1, out_dtype)
+    if _ups_fold(x1, x2, w, 1, 'same', upsample, out_dtype) and _ups_fold_ok(x1, Cout, 3):
+        N.call('mmseg_conv2d_fwd_ups_parity', x1, _wprep_ups(w, C1, Cout, 0, wkey), ss[1], ss[0], y, B, H1, W1, C1, Cout,
+               ACT['relu' if relu else None], 0.0)
+        return y
     wt = _wprep(w, KH, KW, Cin, Cout, 0, wkey) if N.call('mmseg_conv2d_fast_path', C1, C2, Cout, 0) else None
     io = (1 if _h(x1) else 0) | (2 if _h(x2) else 0) | (4 if _h(y) else 0)
     if io:
