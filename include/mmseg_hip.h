@@ -497,6 +497,22 @@ long mmseg_keep_largest_workspace_bytes(int S, int H, int W, int K);
 int mmseg_keep_largest_components(const unsigned char* label, const int* values, unsigned char* out, int* stats, int* ws, int S, int H,
                                   int W, int K, int connectivity, void* stream);
 
+/* ---- enclosed holes of every organ (csrc/postprocess.hip; build-defined, the rule is in INTEGRATION.md section 5) -----------------------
+ * A hole of organ k is a connected component of the complement of (label == values[k]) that holds no border voxel; the complement
+ * is joined through faces only.  per_slice 0: six neighbours, the border is the six faces of the volume; per_slice 1: every slice
+ * on its own, four neighbours, the border is the four edges of the slice (scipy.ndimage.binary_fill_holes with its default
+ * structure, on the volume or slice by slice).  S * H * W < 2^31 - 1, 1 <= H, W, 1 <= K <= 16; anything else, another per_slice or a
+ * null pointer is refused (hipErrorInvalidValue, nothing is launched).  S == 0 does nothing. */
+/* bytes of ws for mmseg_fill_label_holes (about 5 per voxel); 0 for arguments that it would refuse */
+long mmseg_fill_label_holes_workspace_bytes(int S, int H, int W, int K);
+/* out [S,H,W] uint8 = label, except that a voxel which is 0 in label and lies in a hole of organ k becomes values[k]; holes are those
+ * of label itself, and where several organs enclose a voxel the lowest k wins.  Other grey values inside a hole are copied.  stats
+ * [K,3] int32 = (number of holes, voxels of values[k] before, voxels added), (0, 0, 0) for an organ without voxels.  Every byte of
+ * out and stats is written; out must not alias label.  ws (4-byte aligned) is the only scratch; integer atomics only and a canonical
+ * labelling, so two runs are bitwise equal.  No kernel waits for another block; no host synchronisation, allocation or copy. */
+int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W,
+                           int K, int per_slice, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,11 @@
 //   that is no organ's; all K organs in one pass (a union-find in comp itself, see the kernels).
 // mmseg_keep_largest_components: the components, their sizes (integer atomics on the root's slot), per organ one 64-bit atomicMax on
 //   (size << 32) | (0xffffffff - root), and a pass that zeroes the organ voxels outside their organ's winner.
+//
+// Enclosed holes of every organ (build-defined; the rule is in INTEGRATION.md section 5).
+// mmseg_fill_label_holes: per organ k, in order on the stream, the same union-find over the COMPLEMENT of the organ ("!= values[k]", faces
+//   only, in 3-D or slice by slice), a mark on the root of every set that holds a border voxel (an idempotent byte store), and a pass
+//   that gives the input's zeros in unmarked sets to the organ where `out` still holds 0: the lowest k wins.
 #include "common.hpp"
 #include <math.h>
 
@@ -433,7 +438,7 @@ __global__ void __launch_bounds__(PO_BLOCK) po_surface_final_kernel(const int* _
     }
 }
 
-// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep, PO_RED_BLOCKS
+// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep and the hole fill, PO_RED_BLOCKS
 // the reductions (po_surface_final_kernel adds that many partials with one block), OS_MAXBLK the order statistics, CC_MAXBLK the components
 static unsigned po_grid(long n, long cap) {
     const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
@@ -736,14 +741,20 @@ __device__ __forceinline__ void cc_member_init(unsigned* member, const int* __re
     }
 }
 
-// grid = number of tiles (x fastest), block PO_BLOCK: thread t owns the voxels (lz, t >> 5, t & 31), lz < 4
+// grid = number of tiles (x fastest), block PO_BLOCK: thread t owns the voxels (lz, t >> 5, t & 31), lz < 4.
+// COMPLEMENT (the hole filling): one class, the voxels whose grey value is not values[K]; K is then that organ's index.  nnb = 2 leaves
+// the link across slices out (cc_off[2]): every slice is a problem of its own.
+template <bool COMPLEMENT>
 __global__ void __launch_bounds__(PO_BLOCK) po_cc_local_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int K,
                                                                int* __restrict__ comp, int S, int H, int W, int ntx, int nty, int nnb) {
     __shared__ unsigned member[8];
-    __shared__ int grey[CC_TILE];          // the grey value of an organ voxel, -1 for everything else and outside the volume
-    __shared__ int par[CC_TILE];
-    cc_member_init(member, values, K);
-    __syncthreads();
+    __shared__ int grey[CC_TILE];          // the grey value of an organ voxel (COMPLEMENT: 0 for a voxel of the complement), -1 for
+    __shared__ int par[CC_TILE];           // everything else and outside the volume
+    const int organ = COMPLEMENT ? values[K] : 0;
+    if constexpr (!COMPLEMENT) {
+        cc_member_init(member, values, K);
+        __syncthreads();
+    }
     int tile = blockIdx.x;
     const int x0 = (tile % ntx) * CC_TX;
     tile /= ntx;
@@ -756,7 +767,8 @@ __global__ void __launch_bounds__(PO_BLOCK) po_cc_local_kernel(const unsigned ch
         int v = -1;
         if (x < W && y < H && z0 + lz < S) {
             v = lab[(long)(z0 + lz) * plane + (long)y * W + x];
-            if (!((member[v >> 5] >> (v & 31)) & 1u)) v = -1;
+            if constexpr (COMPLEMENT) v = v != organ ? 0 : -1;
+            else if (!((member[v >> 5] >> (v & 31)) & 1u)) v = -1;
         }
         grey[lz * PO_BLOCK + threadIdx.x] = v;
     }
@@ -797,7 +809,8 @@ __global__ void __launch_bounds__(PO_BLOCK) po_cc_local_kernel(const unsigned ch
     }
 }
 
-// grid-stride over the voxels: unions across tile faces
+// grid-stride over the voxels: unions across tile faces.  COMPLEMENT: every labelled voxel is of the one class (lab is not read)
+template <bool COMPLEMENT>
 __global__ void __launch_bounds__(PO_BLOCK) po_cc_merge_kernel(const unsigned char* __restrict__ lab, int* comp, int S, int H, int W, int nnb) {
     const long plane = (long)H * W, n = plane * S;
     for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
@@ -807,13 +820,13 @@ __global__ void __launch_bounds__(PO_BLOCK) po_cc_merge_kernel(const unsigned ch
         const int lx = x & (CC_TX - 1), ly = y & (CC_TY - 1);
         if (lx != 0 && lx != CC_TX - 1 && ly != 0 && ly != CC_TY - 1 && (z & (CC_TZ - 1)) != 0) continue;          // inside its tile
         if (comp[e] == 0) continue;          // no organ's voxel (comp[e] only changes between non-zero values)
-        const int v = lab[e];
+        const int v = COMPLEMENT ? 0 : lab[e];
         for (int i = 0; i < nnb; ++i) {
             const int nz = z + cc_off[i][0], ny = y + cc_off[i][1], nx = x + cc_off[i][2];
             if (nz < 0 || ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
             if (nz / CC_TZ == z / CC_TZ && ny / CC_TY == y / CC_TY && nx / CC_TX == x / CC_TX) continue;          // po_cc_local_kernel's
             const long m = (long)nz * plane + (long)ny * W + nx;
-            if (lab[m] == v) cc_union<__HIP_MEMORY_SCOPE_AGENT>(comp, (int)e, (int)m);
+            if (COMPLEMENT ? comp[m] != 0 : lab[m] == v) cc_union<__HIP_MEMORY_SCOPE_AGENT>(comp, (int)e, (int)m);
         }
     }
 }
@@ -895,12 +908,79 @@ static int po_components(const unsigned char* label, const int* values, int* com
     const long n = (long)S * H * W;
     const int ntx = (W + CC_TX - 1) / CC_TX, nty = (H + CC_TY - 1) / CC_TY, ntz = (S + CC_TZ - 1) / CC_TZ;
     const int nnb = connectivity == 26 ? 13 : 3;
-    hipLaunchKernelGGL(po_cc_local_kernel, dim3((unsigned)((long)ntx * nty * ntz)), dim3(PO_BLOCK), 0, st, label, values, K, comp, S, H, W,
+    hipLaunchKernelGGL(po_cc_local_kernel<false>, dim3((unsigned)((long)ntx * nty * ntz)), dim3(PO_BLOCK), 0, st, label, values, K, comp, S, H, W,
                        ntx, nty, nnb);
-    hipLaunchKernelGGL(po_cc_merge_kernel, dim3(po_grid(n, CC_MAXBLK)), dim3(PO_BLOCK), 0, st, label, comp, S, H, W, nnb);
+    hipLaunchKernelGGL(po_cc_merge_kernel<false>, dim3(po_grid(n, CC_MAXBLK)), dim3(PO_BLOCK), 0, st, label, comp, S, H, W, nnb);
     hipLaunchKernelGGL(po_cc_flatten_kernel, dim3(po_grid(n, CC_MAXBLK)), dim3(PO_BLOCK), 0, st, comp, n);
     return MMSEG_CHECK_LAUNCH();
 }
+
+// ---- enclosed holes of every organ ----------------------------------------------------------------------------------------------------------
+// comp[e] = 1 + root for every voxel of the complement, and mark[root] = 1 where e lies on the border: the six faces of the volume, or
+// with per_slice the four edges of its slice.  Every thread that marks a root stores the same byte; mark is zeroed before the launch.
+__global__ void __launch_bounds__(PO_BLOCK) po_fh_flatten_kernel(int* comp, unsigned char* __restrict__ mark, int S, int H, int W,
+                                                                 int per_slice) {
+    const long plane = (long)H * W, n = plane * S;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        if (comp[e] == 0) continue;
+        const int root = cc_find<__HIP_MEMORY_SCOPE_AGENT>(comp, (int)e);
+        comp[e] = root + 1;          // a racing reader: old or new parent, both valid
+        const int z = (int)(e / plane);
+        const int r = (int)(e - (long)z * plane);
+        const int y = r / W, x = r - y * W;
+        if (x == 0 || x == W - 1 || y == 0 || y == H - 1 || (!per_slice && (z == 0 || z == S - 1))) mark[root] = 1;
+    }
+}
+
+// stats[k] += (unmarked roots, voxels of values[k], voxels filled); a zero of the input in an unmarked set becomes values[k] where out
+// still holds 0.  FIRST (k == 0): out holds nothing yet, and every byte of it is written here.
+template <bool FIRST>
+__global__ void __launch_bounds__(PO_BLOCK) po_fh_fill_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int k,
+                                                              const int* __restrict__ comp, const unsigned char* __restrict__ mark,
+                                                              unsigned char* out, int* __restrict__ stats, long n) {
+    __shared__ int red[3];
+    if (threadIdx.x < 3) red[threadIdx.x] = 0;
+    __syncthreads();
+    const int v = values[k];
+    int holes = 0, before = 0, added = 0;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int g = lab[e], c = comp[e];
+        before += c == 0;          // comp is 0 on the organ's own voxels and nowhere else
+        bool enclosed = false;
+        if (c != 0) {
+            enclosed = mark[c - 1] == 0;
+            holes += enclosed && c == (int)e + 1;
+        }
+        bool fill = enclosed && g == 0;
+        if constexpr (FIRST) {
+            out[e] = (unsigned char)(fill ? v : g);
+        } else if (fill) {
+            fill = out[e] == 0;          // a lower k has been here first: this thread alone touches out[e]
+            if (fill) out[e] = (unsigned char)v;
+        }
+        added += fill;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        holes += __shfl_xor(holes, o, 64);
+        before += __shfl_xor(before, o, 64);
+        added += __shfl_xor(added, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (holes) atomicAdd(&red[0], holes);
+        if (before) atomicAdd(&red[1], before);
+        if (added) atomicAdd(&red[2], added);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && red[threadIdx.x]) atomicAdd(stats + 3 * k + threadIdx.x, red[threadIdx.x]);          // one per block and counter
+}
+
+static bool po_fh_args_ok(int S, int H, int W, int K, int per_slice) {
+    return po_problem_ok(S, H, W, K) && (per_slice == 0 || per_slice == 1);
+}
+
+// the workspace of mmseg_fill_label_holes: comp [n] int32, then mark [n] bytes
+static long po_fh_workspace_bytes(long n) { return (long)sizeof(int) * n + 4 * ((n + 3) / 4); }
 
 // the workspace of po_surface_walk, in this order; n = S * H * W
 struct po_walk_ws {
@@ -1110,6 +1190,42 @@ int mmseg_keep_largest_components(const unsigned char* label, const int* values,
     hipLaunchKernelGGL(po_cc_size_kernel, grid, block, 0, st, comp, size, n);
     hipLaunchKernelGGL(po_cc_winner_kernel, grid, block, 0, st, label, values, K, comp, size, keys, stats, n);
     hipLaunchKernelGGL(po_cc_keep_kernel, grid, block, 0, st, label, values, K, comp, keys, out, stats, n);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// bytes of workspace of mmseg_fill_label_holes: the parents of the n voxels and one byte each for the border marks
+long mmseg_fill_label_holes_workspace_bytes(int S, int H, int W, int K) {
+    if (S <= 0 || !po_fh_args_ok(S, H, W, K, 0)) return 0;
+    return po_fh_workspace_bytes((long)S * H * W);
+}
+
+// out [S,H,W] uint8 = label with the zeros that an organ encloses set to that organ's grey value (faces only; per_slice: every slice on
+// its own); stats [K,3] int32 = (holes, voxels of values[k] before, voxels added).  ws: mmseg_fill_label_holes_workspace_bytes(S, H, W, K)
+// bytes, 4-byte aligned.  Four launches and one memset per organ, all on the stream.
+int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W,
+                           int K, int per_slice, void* stream) {
+    if (S <= 0) return 0;
+    if (!label || !values || !out || !stats || !ws || label == out || !po_fh_args_ok(S, H, W, K, per_slice))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)S * H * W;
+    int* comp = reinterpret_cast<int*>(ws);
+    unsigned char* mark = reinterpret_cast<unsigned char*>(comp + n);
+    hipError_t rc = hipMemsetAsync(stats, 0, sizeof(int) * 3 * (size_t)K, st);
+    if (rc != hipSuccess) return (int)rc;
+    const int ntx = (W + CC_TX - 1) / CC_TX, nty = (H + CC_TY - 1) / CC_TY, ntz = (S + CC_TZ - 1) / CC_TZ;
+    const int nnb = per_slice ? 2 : 3;
+    const dim3 tiles((unsigned)((long)ntx * nty * ntz)), grid(po_grid(n, CC_MAXBLK)), block(PO_BLOCK);
+    const dim3 few(po_grid(n, PO_SURF_MAXBLK));          // the fill pass: every block ends with three atomics on the same three counters
+    for (int k = 0; k < K; ++k) {
+        rc = hipMemsetAsync(mark, 0, (size_t)n, st);
+        if (rc != hipSuccess) return (int)rc;
+        hipLaunchKernelGGL(po_cc_local_kernel<true>, tiles, block, 0, st, label, values, k, comp, S, H, W, ntx, nty, nnb);
+        hipLaunchKernelGGL(po_cc_merge_kernel<true>, grid, block, 0, st, label, comp, S, H, W, nnb);
+        hipLaunchKernelGGL(po_fh_flatten_kernel, grid, block, 0, st, comp, mark, S, H, W, per_slice);
+        if (k == 0) hipLaunchKernelGGL(po_fh_fill_kernel<true>, few, block, 0, st, label, values, k, comp, mark, out, stats, n);
+        else hipLaunchKernelGGL(po_fh_fill_kernel<false>, few, block, 0, st, label, values, k, comp, mark, out, stats, n);
+    }
     return MMSEG_CHECK_LAUNCH();
 }
 

@@ -5,6 +5,7 @@
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
+                         [--predict_fill_holes none|2d|3d]
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
@@ -61,6 +62,9 @@ def parse_arguments(argv=None):
                     help="largest: keep each organ's largest 3-D connected component in the predicted label volumes")
     ap.add_argument('--predict_connectivity', type=int, choices=[6, 26], default=6,
                     help='neighbours of --predict_components: faces / faces, edges and corners')
+    ap.add_argument('--predict_fill_holes', choices=['none', '2d', '3d'], default='none',
+                    help='fill the zeros that an organ encloses, after --predict_components: slice by slice / in the volume '
+                         '(results_holes_<modality>.csv)')
     ap.add_argument('--predict_robust', type=true_or_false, default=False, metavar='true|false',
                     help='also score them by HD (a percentile of the surface distances) and NSD (surface Dice at a tolerance): '
                          'results_robust_<modality>.csv')
@@ -227,7 +231,8 @@ class Experiment(object):
             VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
                                               surface=getattr(args, 'predict_surface', True),
                                               components={'largest': 'largest'}.get(getattr(args, 'predict_components', 'none')),
-                                              connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args))
+                                              connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args),
+                                              fill_holes={'2d': '2d', '3d': '3d'}.get(getattr(args, 'predict_fill_holes', 'none')))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 

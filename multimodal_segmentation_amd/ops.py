@@ -1814,6 +1814,27 @@ def keep_largest_components(label, values, connectivity=6):
     return out, stats
 
 
+HOLE_MODES = ('2d', '3d')
+
+
+def fill_label_holes(label, values, mode='3d'):
+    """label [S,H,W] uint8 on the device, values [K] int32 -> (uint8 [S,H,W], int32 [K,3]): the volume with the zeros that organ k
+    encloses set to values[k], and per organ (number of holes, voxels before, voxels added) (csrc/postprocess.hip).  A hole of organ k
+    is a connected component of the complement of (label == values[k]), joined through faces only, that holds no border voxel: of
+    the volume with mode '3d', of its slice with mode '2d', where every slice is a problem of its own.  Holes are those of the
+    input; only zeros are filled, and where several organs enclose a voxel the lowest k wins."""
+    if mode not in HOLE_MODES:
+        raise ValueError("fill_label_holes: mode must be '2d' (every slice on its own) or '3d', got %r" % (mode,))
+    K = _volume_args('fill_label_holes', label, values)
+    S, H, W = label.shape
+    out = _new((S, H, W), label, torch.uint8)
+    stats = torch.zeros((K, 3), dtype=torch.int32, device=label.device)
+    if S:
+        ws = _ws('fill_holes', (N.call('mmseg_fill_label_holes_workspace_bytes', S, H, W, K) + 3) // 4, label.device)
+        N.call('mmseg_fill_label_holes', _c(label), values, out, stats, ws, S, H, W, K, int(mode == '2d'))
+    return out, stats
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

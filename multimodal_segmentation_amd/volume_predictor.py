@@ -19,10 +19,16 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
                                            of the union of the organs and of every organ, one row per scored volume
     <out>/results_components_<modality>.csv   with components='largest': per organ the number of connected components, its voxels
                                            before the filter and the voxels kept, one row per volume
+    <out>/results_holes_<modality>.csv     with fill_holes='2d' or '3d': per organ the number of enclosed holes, its voxels before
+                                           the filling and the voxels added, one row per volume
 
 components='largest' (build-defined, off by default; the rule is in INTEGRATION.md section 5) keeps, per organ, the largest 3-D connected
 component: the prediction is scattered to the file grid [S_file,H,W] on the device and filtered there (ops.keep_largest_components),
 so that neighbours across slices are those of the file; the filtered volume is what is scored and written.
+
+fill_holes='2d' | '3d' (build-defined, off by default; the rule is in INTEGRATION.md section 5) then sets the zeros that an organ
+encloses to that organ's grey value (ops.fill_label_holes, on the file grid as well): slice by slice with '2d', in the volume with
+'3d'.  It runs after the component filter, so that an island which the filter turned into zeros inside an organ is closed again.
 
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
 from the counts summed over the organs, then the mean over the selected slices.
@@ -147,6 +153,26 @@ def keep_largest(pred, values, geometry, connectivity=6):
     return kept.index_select(0, where), stats
 
 
+FILL_HOLES = (None,) + ops.HOLE_MODES
+
+
+def check_fill_holes(fill_holes):
+    if fill_holes not in FILL_HOLES:
+        raise ValueError("fill_holes must be None, '2d' or '3d', got %r" % (fill_holes,))
+
+
+def fill_holes(pred, values, geometry, mode):
+    """pred: uint8 [S,H,W] on the device, the selected slices of one file in order -> (the same slices with the enclosed zeros of
+    every organ filled, stats [K,3] on the device).  Like keep_largest on the file grid [S_file,H,W] (unselected slices are zero): a
+    cavity whose lid is a slice that the file holds but the selection skips is open."""
+    on_grid, where = _on_file_grid(pred, geometry)
+    filled, stats = ops.fill_label_holes(on_grid, values, mode)
+    return filled.index_select(0, where), stats
+
+
+_fill_holes = fill_holes          # for score_folder and VolumePredictor.run, whose keyword carries the function's name
+
+
 def _write_table(path, rows, names, num_masks, fmt, union_first):
     """rows: (volume, one row of len(names) values per organ, then with union_first the union's) -> Vol, [names,] names of organ 0, ..."""
     cols = ['Vol'] + list(names if union_first else ()) + ['%s%d' % (name, k) for k in range(num_masks) for name in names]
@@ -164,6 +190,11 @@ def write_component_results(path, rows, num_masks):
     _write_table(path, rows, ('N', 'Before', 'Kept'), num_masks, '%d', False)
 
 
+def write_hole_results(path, rows, num_masks):
+    """rows: (volume, stats [K,3]) -> Vol, N0, Before0, Added0, N1, ..."""
+    _write_table(path, rows, ('N', 'Before', 'Added'), num_masks, '%d', False)
+
+
 def write_surface_results(path, rows, num_masks):
     """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
     _write_table(path, rows, ('RAVD', 'ASSD', 'MSSD'), num_masks, '%.3f', True)
@@ -177,7 +208,7 @@ def write_robust_results(path, rows, num_masks):
 class ScoreSheet(object):
     """the rows of one run's results_<kind>_<modality>.csv files: rows[kind][m] holds those of modality m; `scores` is score_volume's"""
     WRITERS = (('native', write_results), ('surface', write_surface_results), ('robust', write_robust_results),
-               ('components', write_component_results))
+               ('components', write_component_results), ('holes', write_hole_results))
 
     def __init__(self, modalities, num_masks, in_mm):
         self.modalities, self.num_masks, self.in_mm = list(modalities), num_masks, in_mm
@@ -199,6 +230,9 @@ class ScoreSheet(object):
     def add_components(self, m, volume, stats):
         self.rows['components'][m].append((volume, nn.to_numpy(stats)))
 
+    def add_holes(self, m, volume, stats):
+        self.rows['holes'][m].append((volume, nn.to_numpy(stats)))
+
     def write(self, out_folder):
         """one file per kind and modality that has rows"""
         for kind, writer in self.WRITERS:
@@ -210,13 +244,16 @@ class ScoreSheet(object):
         return {name: self.rows[kind][m] for m, name in enumerate(self.modalities)}
 
 
-def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6, robust=None):
+def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6, robust=None,
+                 fill_holes=None):
     """Score label volumes written earlier (by VolumePredictor.run or by another program: <file name of the input>.npz with `label`
     [S_file,H,W] uint8) against the labelled files of `data_folder`; writes the CSV files of VolumePredictor.run into out_folder
     (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json.
-    components='largest' filters every volume first (keep_largest): the scores that post-processing would give.
+    components='largest' filters every volume first (keep_largest), fill_holes='2d' | '3d' then fills the enclosed holes of every
+    organ (fill_holes): the scores that post-processing would give.
     robust=(percentile, tolerance in mm) also writes results_robust_<modality>.csv, and a third dictionary with its rows is returned."""
     check_components(components, connectivity)
+    check_fill_holes(fill_holes)
     robust = check_robust(robust)
     loader = VolumeFolderLoader(data_folder)
     out_folder = out_folder or pred_folder
@@ -249,6 +286,8 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
             pred = nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8)
             if components:
                 pred, _ = keep_largest(pred, values, geo, connectivity)
+            if fill_holes:
+                pred, _ = _fill_holes(pred, values, geo, fill_holes)
             scores = score_volume(pred, nn.host_to_device(np.ascontiguousarray(label[selected]), device, np.uint8), values, geo, surface,
                                   robust)
             sheet.add(m, v, scores, geo)
@@ -268,8 +307,10 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
-    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None):
+    def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
+            fill_holes=None):
         check_components(components, connectivity)
+        check_fill_holes(fill_holes)
         robust = check_robust(robust)
         if mode not in FUSION_MODES:
             raise ValueError('Unknown mode: %r (expected one of %s)' % (mode, ', '.join(FUSION_MODES)))
@@ -300,6 +341,9 @@ class VolumePredictor(object):
                 if components:
                     pred, stats = keep_largest(pred, values, geo, connectivity)
                     sheet.add_components(m, v, stats)
+                if fill_holes:
+                    pred, stats = _fill_holes(pred, values, geo, fill_holes)
+                    sheet.add_holes(m, v, stats)
                 if geo['label'] is not None:
                     scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface, robust)
                     sheet.add(m, v, scores, geo)
@@ -313,6 +357,8 @@ class VolumePredictor(object):
                         label_values=loader.label_values, files=files)
         if components:
             settings.update(components=components, connectivity=connectivity)
+        if fill_holes:
+            settings.update(fill_holes=fill_holes)
         if robust is not None:
             settings.update(percentile=robust[0], tolerance_mm=robust[1])
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:

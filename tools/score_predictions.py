@@ -12,9 +12,11 @@ within `--predict_tolerance` mm, default 1.0) into results_robust_<modality>.csv
 
 `--components largest` keeps each organ's largest 3-D connected component in every volume read from PRED_FOLDER before it is scored
 (`--connectivity 6|26`): the scores that `--predict_components largest` would have given, for volumes written without it.
+`--fill_holes 2d|3d` then fills the zeros that an organ encloses, slice by slice or in the volume, as `--predict_fill_holes` does;
+with both options the filter runs first.
 
     python tools/score_predictions.py PRED_FOLDER DATA_FOLDER [--out OUT] [--surface true|false] [--components largest]
-                                      [--connectivity 6|26] [--predict_robust true|false] [--predict_percentile Q]
+                                      [--connectivity 6|26] [--fill_holes 2d|3d] [--predict_robust true|false] [--predict_percentile Q]
                                       [--predict_tolerance MM]
 """
 import argparse
@@ -36,6 +38,7 @@ def main(argv=None):
     ap.add_argument('--surface', type=true_or_false, default=True, metavar='true|false', help='also the scores in mm')
     ap.add_argument('--components', choices=['largest'], help="filter the predicted volumes first: each organ's largest component")
     ap.add_argument('--connectivity', type=int, choices=[6, 26], default=6, help='neighbours of --components')
+    ap.add_argument('--fill_holes', choices=['2d', '3d'], help='then fill the holes of every organ: slice by slice / in the volume')
     ap.add_argument('--predict_robust', type=true_or_false, default=False, metavar='true|false', help='also HD and NSD')
     ap.add_argument('--predict_percentile', type=float, default=95.0, metavar='Q', help='percentile of --predict_robust, 0 to 100')
     ap.add_argument('--predict_tolerance', type=float, default=1.0, metavar='MM', help='tolerance of --predict_robust in mm, 0 or more')
@@ -46,7 +49,7 @@ def main(argv=None):
         ap.error('--predict_tolerance must be a finite number of mm >= 0, got %r' % a.predict_tolerance)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
     robust = (a.predict_percentile, a.predict_tolerance) if a.predict_robust else None
-    tables = score_folder(a.pred_folder, a.data_folder, a.out, a.surface, a.components, a.connectivity, robust)
+    tables = score_folder(a.pred_folder, a.data_folder, a.out, a.surface, a.components, a.connectivity, robust, a.fill_holes)
     rows, surface_rows = tables[:2]
     for name in rows:
         print('%s: %d volumes scored, %d of them in mm' % (name, len(rows[name]), len(surface_rows[name])))
