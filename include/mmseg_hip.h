@@ -513,6 +513,20 @@ long mmseg_fill_label_holes_workspace_bytes(int S, int H, int W, int K);
 int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W,
                            int K, int per_slice, void* stream);
 
+/* ---- tiles of a frame larger than the network's input (csrc/postprocess.hip; build-defined, the rule is in INTEGRATION.md section 5) ----
+ * prob [TR*TC,S,OH,OW,C] fp32: the segmentor's output for every tile of a TR x TC plan (tile tr * TC + tc), the K organ channels
+ * first.  rows [TR,3] and cols [TC,3] int32 = (lo, kept, before) per tile and axis, wr [TR,OH] and wc [TC,OW] fp32 weights, all on the
+ * device.  out [S,RH,RW,K] fp32, every element written: the blended map on the resampled frame.  Tile row tr covers frame row y when
+ * lo <= y < lo + kept (and the container row iy = y - lo + before lies inside [0, OH)); columns alike; a container's padding is never
+ * read.  Over the covering tiles in ascending (tr, tc) order, W = wr[tr][iy] * wc[tc][ix]: num_k = sum of W * p_k, den = sum of W, in
+ * fp32 in that order without contraction, out_k = num_k / den.  A pixel that exactly one tile covers takes that tile's value
+ * unchanged (no multiply, no divide); a pixel that no tile covers gets 0.  A gather without atomics: two runs are bitwise equal.
+ * 1 <= TR, TC <= 8, 1 <= K <= min(C, 16), extents >= 1, prob and out below 2^31 bytes each; anything else or a null pointer is refused
+ * (hipErrorInvalidValue, nothing is launched); out must not alias prob.  S == 0 does nothing.  No host synchronisation, allocation or
+ * copy. */
+int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const float* wr, const float* wc, float* out, int S, int TR,
+                      int TC, int OH, int OW, int C, int K, int RH, int RW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

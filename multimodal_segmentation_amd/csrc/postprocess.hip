@@ -58,6 +58,12 @@
 // mmseg_fill_label_holes: per organ k, in order on the stream, the same union-find over the COMPLEMENT of the organ ("!= values[k]", faces
 //   only, in 3-D or slice by slice), a mark on the root of every set that holds a border voxel (an idempotent byte store), and a pass
 //   that gives the input's zeros in unmarked sets to the organ where `out` still holds 0: the lowest k wins.
+//
+// Frames larger than the network's input (build-defined; the rule is in INTEGRATION.md section 5).
+// mmseg_blend_tiles: prob [TR*TC,S,OH,OW,C], the segmentor's output for every tile of a TR x TC plan -> out [S,RH,RW,K], the weighted mean of
+//   the covering tiles at every pixel of the resampled frame, weights wr[tr][iy] * wc[tc][ix].  A gather: every output element is
+//   written by one thread, the covering tiles are visited in ascending (tr, tc) order, so two runs are bitwise equal; a pixel that one
+//   tile covers is copied.  mmseg_restore_label then takes the whole frame as its window.
 #include "common.hpp"
 #include <math.h>
 
@@ -169,6 +175,62 @@ __global__ void __launch_bounds__(PO_BLOCK) po_restore_kernel(const float* __res
             dst[e] = (unsigned char)po_pixel<VEC4>(src, OW, C, K, vals, po_axis_tap(r, ry, RH, ar, order),
                                                    po_axis_tap(c, rx, RW, ac, order), order);
         }
+    }
+}
+
+// ---- tiles of a frame larger than the network's input, blended back into one probability map ------------------------------------------
+#define BT_MAXTILES 8          // per axis
+
+// VEC4: a thread owns one frame pixel, K == 4 channels as one 16-byte load per tile and one 16-byte store (C % 4 == 0, both pointers
+// 16-byte aligned).  Otherwise a thread owns one output float (pixel, k): consecutive lanes store consecutive floats and the lanes of a
+// pixel read consecutive channels of the same tile pixel.  Grid-stride over n = S * RH * RW [* K] elements, n < 2^29.
+// The sums run over the covering tiles in ascending (tr, tc) order, starting from 0, in fp32 without contraction.  A tile covers a
+// frame index y when lo <= y < lo + kept AND its container index y - lo + before lies inside [0, O): the tables come from the device,
+// so the second condition is what keeps every read inside `prob`.
+template <bool VEC4>
+__global__ void __launch_bounds__(PO_BLOCK) po_blend_kernel(const float* __restrict__ prob, const int* __restrict__ rows,
+                                                            const int* __restrict__ cols, const float* __restrict__ wr,
+                                                            const float* __restrict__ wc, float* __restrict__ out, int S, int TR, int TC,
+                                                            int OH, int OW, int C, int K, int RH, int RW, int n) {
+#pragma clang fp contract(off)
+    __shared__ int ar[BT_MAXTILES * 3], ac[BT_MAXTILES * 3];
+    if (threadIdx.x < TR * 3) ar[threadIdx.x] = rows[threadIdx.x];
+    if (threadIdx.x >= 32 && threadIdx.x < 32 + TC * 3) ac[threadIdx.x - 32] = cols[threadIdx.x - 32];
+    __syncthreads();
+    const int plane = RH * RW;
+    for (int e = blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += gridDim.x * PO_BLOCK) {
+        const int pix = VEC4 ? e : e / K, k = VEC4 ? 0 : e - pix * K;
+        const int s = pix / plane, r = pix - s * plane;
+        const int y = r / RW, x = r - y * RW;
+        int cnt = 0;
+        float den = 0.f;
+        f32x4 num4 = {0.f, 0.f, 0.f, 0.f}, first4 = {0.f, 0.f, 0.f, 0.f};
+        float num = 0.f, first = 0.f;
+        for (int tr = 0; tr < TR; ++tr) {
+            const int iy = y - ar[3 * tr] + ar[3 * tr + 2];
+            if (y < ar[3 * tr] || y >= ar[3 * tr] + ar[3 * tr + 1] || iy < 0 || iy >= OH) continue;
+            const float wy = wr[tr * OH + iy];
+            for (int tc = 0; tc < TC; ++tc) {
+                const int ix = x - ac[3 * tc] + ac[3 * tc + 2];
+                if (x < ac[3 * tc] || x >= ac[3 * tc] + ac[3 * tc + 1] || ix < 0 || ix >= OW) continue;
+                const float w = wy * wc[tc * OW + ix];
+                const float* p = prob + ((((size_t)(tr * TC + tc) * S + s) * OH + iy) * OW + ix) * C;
+                if constexpr (VEC4) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+                    if (cnt == 0) first4 = v;
+                    num4 = num4 + w * v;
+                } else {
+                    const float v = p[k];
+                    if (cnt == 0) first = v;
+                    num = num + w * v;
+                }
+                den = den + w;
+                ++cnt;
+            }
+        }
+        // one covering tile: its value as it is (no multiply, no divide); none: 0
+        if constexpr (VEC4) reinterpret_cast<f32x4*>(out)[e] = cnt == 1 ? first4 : cnt == 0 ? num4 : num4 / den;
+        else out[e] = cnt == 1 ? first : cnt == 0 ? 0.f : num / den;
     }
 }
 
@@ -438,7 +500,7 @@ __global__ void __launch_bounds__(PO_BLOCK) po_surface_final_kernel(const int* _
     }
 }
 
-// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep and the hole fill, PO_RED_BLOCKS
+// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep, the hole fill and the tile blend, PO_RED_BLOCKS
 // the reductions (po_surface_final_kernel adds that many partials with one block), OS_MAXBLK the order statistics, CC_MAXBLK the components
 static unsigned po_grid(long n, long cap) {
     const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
@@ -1059,6 +1121,34 @@ int mmseg_restore_label(const float* prob, const int* values, unsigned char* out
     else if (vec4) po_launch<true, false>(grid, st, prob, values, K, out, H, W, RH, RW, OH, OW, ar, ac, C, order);
     else if (pack) po_launch<false, true>(grid, st, prob, values, K, out, H, W, RH, RW, OH, OW, ar, ac, C, order);
     else po_launch<false, false>(grid, st, prob, values, K, out, H, W, RH, RW, OH, OW, ar, ac, C, order);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// prob [TR*TC,S,OH,OW,C] fp32 (tile tr * TC + tc), rows [TR,3] / cols [TC,3] int32 (lo, kept, before) and wr [TR,OH] / wc [TC,OW] fp32 on
+// the device, out [S,RH,RW,K] fp32: every element is written.  One launch; no atomics, nothing allocated or synchronised.
+int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const float* wr, const float* wc, float* out, int S, int TR,
+                      int TC, int OH, int OW, int C, int K, int RH, int RW, void* stream) {
+    if (S == 0) return 0;
+    const long lim = 0x80000000L;          // bytes of either tensor
+    if (!prob || !rows || !cols || !wr || !wc || !out || prob == out || S < 0 || TR < 1 || TR > BT_MAXTILES || TC < 1 || TC > BT_MAXTILES ||
+        OH < 1 || OW < 1 || RH < 1 || RW < 1 || C < 1 || K < 1 || K > C || K > PO_MAXVALUES)
+        return (int)hipErrorInvalidValue;
+    // the products are taken factor by factor, so that none of them overflows before it is compared
+    long in = (long)sizeof(float) * TR * TC, px = (long)sizeof(float) * S;
+    for (const int f : {S, OH, OW, C}) {
+        in *= f;
+        if (in >= lim) return (int)hipErrorInvalidValue;
+    }
+    for (const int f : {RH, RW, K}) {
+        px *= f;
+        if (px >= lim) return (int)hipErrorInvalidValue;
+    }
+    const bool vec4 = K == 4 && (C & 3) == 0 && ((uintptr_t)prob & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const int n = (int)((long)S * RH * RW * (vec4 ? 1 : K));
+    const dim3 grid(po_grid(n, PO_SURF_MAXBLK)), block(PO_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec4) hipLaunchKernelGGL(po_blend_kernel<true>, grid, block, 0, st, prob, rows, cols, wr, wc, out, S, TR, TC, OH, OW, C, K, RH, RW, n);
+    else hipLaunchKernelGGL(po_blend_kernel<false>, grid, block, 0, st, prob, rows, cols, wr, wc, out, S, TR, TC, OH, OW, C, K, RH, RW, n);
     return MMSEG_CHECK_LAUNCH();
 }
 

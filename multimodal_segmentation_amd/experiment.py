@@ -7,6 +7,7 @@
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
+                         [--predict_tiles true|false] [--predict_tile_overlap PIXELS]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
@@ -70,7 +71,15 @@ def parse_arguments(argv=None):
                          'results_robust_<modality>.csv')
     ap.add_argument('--predict_percentile', type=float, default=95.0, metavar='Q', help='percentile of --predict_robust, 0 to 100')
     ap.add_argument('--predict_tolerance', type=float, default=1.0, metavar='MM', help='tolerance of --predict_robust in mm, 0 or more')
+    ap.add_argument('--predict_tiles', type=true_or_false, default=False, metavar='true|false',
+                    help='predict the whole resampled frame of every slice: tiles of the input shape at several offsets, blended, '
+                         'instead of its centre window alone')
+    ap.add_argument('--predict_tile_overlap', type=int, default=None, metavar='PIXELS',
+                    help='least overlap of neighbouring tiles of --predict_tiles, 0 or more and below the input extent (default: half '
+                         'the input extent per axis)')
     args = ap.parse_args(argv)
+    if args.predict_tile_overlap is not None and args.predict_tile_overlap < 0:
+        ap.error('--predict_tile_overlap must be a number of pixels >= 0, got %r' % args.predict_tile_overlap)
     if not 0.0 <= args.predict_percentile <= 100.0:          # here, so that a bad value stops the run before the model is built
         ap.error('--predict_percentile must lie in [0, 100], got %r' % args.predict_percentile)
     if not 0.0 <= args.predict_tolerance < float('inf'):
@@ -232,7 +241,9 @@ class Experiment(object):
                                               surface=getattr(args, 'predict_surface', True),
                                               components={'largest': 'largest'}.get(getattr(args, 'predict_components', 'none')),
                                               connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args),
-                                              fill_holes={'2d': '2d', '3d': '3d'}.get(getattr(args, 'predict_fill_holes', 'none')))
+                                              fill_holes={'2d': '2d', '3d': '3d'}.get(getattr(args, 'predict_fill_holes', 'none')),
+                                              tiles=bool(getattr(args, 'predict_tiles', False)),
+                                              tile_overlap=getattr(args, 'predict_tile_overlap', None))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 
@@ -243,6 +254,9 @@ class Experiment(object):
         dp.init_from_env()
         conf = self.get_config(int(args.split), args)
         self.init_logging(conf)
+        if getattr(args, 'predict_tiles', False) or getattr(args, 'predict_tile_overlap', None) is not None:      # before the model is built
+            from .volume_predictor import check_tile_overlap
+            check_tile_overlap(getattr(args, 'predict_tile_overlap', None), conf.input_shape)
         if getattr(args, 'predict_folder', None) and args.test:
             from .volume_predictor import checkpoint_of
             if checkpoint_of(conf.folder) is None:          # before the test pass evaluates an untrained model

@@ -17,7 +17,10 @@ anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all mod
 slices.  S, H, W and the resolution may differ between volumes and between modalities.
 
 Per (volume, modality) the raw slices are uploaded once through pinned memory and three launches write the volume's share of the
-NHWC containers [N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map)."""
+NHWC containers [N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map).
+
+For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
+frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
 import json
 import logging
 import os
@@ -51,6 +54,67 @@ def crop_pad_map(resampled, target):
             raise ValueError('cropping %d pixels to %d leaves nothing (%d are removed from both ends)' % (r, n, lo))
         return lo, r - 2 * lo, 0
     return 0, r, int((n - r) / 2)
+
+
+MAX_TILES = ops.MAX_TILES          # per axis
+
+
+def tile_window(start, resampled, target):
+    """(lo, kept, before) of the window [start, start + target) of a frame of extent `resampled`, edge-padded where it leaves the frame
+    (pad_mode='edge'): container index o reads frame index clamp(start + o, 0, resampled - 1).  It satisfies the contract of
+    mmseg_preprocess_image: 0 <= lo, kept >= 1, lo + kept <= resampled, 0 <= before < target.  A window entirely outside the frame
+    repeats the nearest edge pixel."""
+    w, r, n = int(start), int(resampled), int(target)
+    if w >= r:
+        return r - 1, 1, 0
+    if w + n <= 0:
+        return 0, 1, 0
+    lo = max(w, 0)
+    return lo, min(w + n, r) - lo, max(-w, 0)
+
+
+def centre_start(resampled, target):
+    """signed start of crop_pad_map's centre window: lo when resampled > target, else -before"""
+    r, n = int(resampled), int(target)
+    return (r - n + 1) // 2 if r > n else -((n - r) // 2)
+
+
+def tile_axis(resampled, target, overlap):
+    """The tiles of one axis, a list of (lo, kept, before): one tile, crop_pad_map's padded one, when the frame fits the network's
+    extent; else n = ceil((R - overlap) / (O - overlap)) full tiles (a_i, O, 0) with a_i = (i * (R - O)) // (n - 1), so that the first
+    starts at 0, the last ends at R and neighbours share at least `overlap` pixels.  Integer arithmetic throughout."""
+    r, n, ov = int(resampled), int(target), int(overlap)
+    if r < 1 or n < 1 or not 0 <= ov < n:
+        raise ValueError('tile_overlap must lie in [0, %d) for an extent of %d pixels (frame %d), got %d' % (n, n, r, ov))
+    if r <= n:
+        return [crop_pad_map(r, n)]
+    count = -(-(r - ov) // (n - ov))
+    if count > MAX_TILES:
+        raise ValueError('a frame of %d pixels needs %d tiles of %d with tile_overlap %d (--predict_tile_overlap), more than the %d an '
+                         'axis may have: lower the overlap' % (r, count, n, ov, MAX_TILES))
+    return [((i * (r - n)) // (count - 1), n, 0) for i in range(count)]
+
+
+def tile_weights(tiles, target):
+    """fp32 [T, O], indexed by container index j: min(l, r) with l = j + 1 where the tile has a left neighbour, else O, and r = O - j
+    where it has a right neighbour, else O.  Integers (exact in fp32), strictly positive, tapering towards a neighbour only."""
+    n = int(target)
+    j = np.arange(n)
+    out = np.empty((len(tiles), n), np.float32)
+    for i in range(len(tiles)):
+        left = j + 1 if i > 0 else np.full(n, n)
+        right = n - j if i < len(tiles) - 1 else np.full(n, n)
+        out[i] = np.minimum(left, right)
+    return out
+
+
+def tiles_of_other(tiles, resampled, other_resampled, target):
+    """The windows of another modality (extent other_resampled) for the tiles planned on the predicted one (extent resampled): tile
+    i, whose window starts at s_i = lo - before on the predicted frame, reads the other frame from s_i - c(R_m) + c(R_j), c =
+    centre_start, so that the tile which coincides with the centre crop of one frame coincides with the centre crop of the other: the
+    pairing the model was trained on."""
+    shift = centre_start(other_resampled, target) - centre_start(resampled, target)
+    return [tile_window(lo - before + shift, other_resampled, target) for lo, kept, before in tiles]
 
 
 def has_data(name):
@@ -193,12 +257,61 @@ class VolumeFolderLoader(object):
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
                                  label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
-        counts = [g.shape[0] for g in images]
+        self._same_counts(volume, [g.shape[0] for g in images])
+        return images, geometry
+
+    def _same_counts(self, volume, counts):
         if len(set(counts)) != 1:
             raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the matching '
                              'ranges under "slices" in %s' % (volume, ', '.join('%s: %d' % mc for mc in zip(self.modalities, counts)),
                                                                MANIFEST))
-        return images, geometry
+
+    def upload_volume(self, volume):
+        """(raw, geometry) of one volume: per modality the selected raw slices [S,H,W] fp32 on the device, uploaded once, and the
+        record of load_volume_for_prediction.  What load_volume_tiles builds its containers from, for every predicted modality."""
+        device = nn.default_device()
+        raw, geometry = [], []
+        for mod in self.modalities:
+            image, label, res, selected, spacing = self._read_file(volume, mod, False)
+            S_file, H, W = image.shape
+            if selected is None:
+                selected = np.arange(S_file)
+            resampled, rows, cols = self.geometry(H, W, res)
+            raw.append(nn.host_to_device(image[selected], device, np.float32))
+            geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
+                                 slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
+                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
+        self._same_counts(volume, [x.shape[0] for x in raw])
+        return raw, geometry
+
+    def tile_plan(self, geometry, m, overlap):
+        """per modality (rows, cols): the tiles of the frame of the predicted modality m (tile_axis with overlap = (rows, columns)), and
+        for every other modality the windows that go with them (tiles_of_other)"""
+        OH, OW = self.input_shape[:2]
+        RH, RW = geometry[m]['resampled']
+        rows, cols = tile_axis(RH, OH, overlap[0]), tile_axis(RW, OW, overlap[1])
+        return [(rows, cols) if j == m else (tiles_of_other(rows, RH, g['resampled'][0], OH), tiles_of_other(cols, RW, g['resampled'][1], OW))
+                for j, g in enumerate(geometry)]
+
+    def load_volume_tiles(self, volume, m, overlap, uploaded=None):
+        """One volume cut into the tiles that cover the whole resampled frame of modality m: (images, geometry, plan).  images: per
+        modality a container [TR*TC*S,OH,OW,1] on the device, tile-major (tile tr * TC + tc is a contiguous [S,OH,OW,1] written by
+        ops.preprocess_images with that tile's index maps; the rescale is per whole resampled frame, so the tiles of a slice share
+        one intensity scale).  geometry: as load_volume_for_prediction.  plan: tile_plan's.  overlap = (rows, columns) in pixels;
+        uploaded: upload_volume's result, when the caller loads tiles for several modalities of one volume."""
+        raw, geometry = self.upload_volume(volume) if uploaded is None else uploaded
+        OH, OW = self.input_shape[:2]
+        plan = self.tile_plan(geometry, m, overlap)
+        images = []
+        for x, geo, (rows, cols) in zip(raw, geometry, plan):
+            S = x.shape[0]
+            container = torch.zeros((len(rows) * len(cols) * S, OH, OW, 1), dtype=torch.float32, device=x.device)
+            for tr, r in enumerate(rows):
+                for tc, c in enumerate(cols):
+                    t = tr * len(cols) + tc
+                    ops.preprocess_images(x, container[t * S:(t + 1) * S], geo['resampled'], r, c, 0)
+            images.append(container)
+        return images, geometry, plan
 
     # ---- the reference's loading surface --------------------------------------------------------------------------------------
     def load_all_modalities_concatenated(self, split, split_type, downsample=1):

@@ -1835,6 +1835,40 @@ def fill_label_holes(label, values, mode='3d'):
     return out, stats
 
 
+MAX_TILES = 8          # per axis (csrc/postprocess.hip)
+
+
+def blend_tiles(prob, rows, cols, wr, wc, S, resampled, K):
+    """prob [TR*TC*S,OH,OW,C] fp32 on the device: a segmentor's output for the tiles of one volume, tile-major (tile tr * TC + tc holds
+    S slices), organ channels first -> fp32 [S,RH,RW,K], the blended map on the resampled frame `resampled` = (RH, RW)
+    (csrc/postprocess.hip).  rows [TR,3] / cols [TC,3]: per tile and axis (lo, kept, before) as given to preprocess_images; wr [TR,OH] /
+    wc [TC,OW]: the weights along each axis (loaders/volume_folder.tile_weights).  Host sequences or device tensors.  Every frame pixel
+    gets the mean of the tiles that cover it, weighted by wr * wc; one covering tile is copied as it is.  No gradient."""
+    RH, RW = int(resampled[0]), int(resampled[1])
+    S, K = int(S), int(K)
+
+    def table(x, dtype, width):
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=dtype)
+        if t.dim() != 2 or t.dtype != dtype or t.shape[1] != width or not 1 <= t.shape[0] <= MAX_TILES:
+            raise ValueError('blend_tiles: expected a [1..%d, %d] %s table, got %s %s' % (MAX_TILES, width, dtype, tuple(t.shape), t.dtype))
+        return _c(t.to(prob.device))
+    if prob.dim() != 4 or prob.dtype != torch.float32 or S < 0 or RH < 1 or RW < 1 or not 1 <= K <= min(16, prob.shape[3]):
+        raise ValueError('blend_tiles: prob %s %s, S = %d, resampled %s, K = %d' % (tuple(prob.shape), prob.dtype, S, (RH, RW), K))
+    N_, OH, OW, C = prob.shape
+    rows, cols = table(rows, torch.int32, 3), table(cols, torch.int32, 3)
+    wr, wc = table(wr, torch.float32, OH), table(wc, torch.float32, OW)
+    TR, TC = rows.shape[0], cols.shape[0]
+    if wr.shape[0] != TR or wc.shape[0] != TC or N_ != TR * TC * S:
+        raise ValueError('blend_tiles: prob %s does not hold %d x %d tiles of %d slices (weights %s, %s)'
+                         % (tuple(prob.shape), TR, TC, S, tuple(wr.shape), tuple(wc.shape)))
+    if max(prob.numel(), S * RH * RW * K) * 4 >= 2 ** 31:
+        raise ValueError('blend_tiles: prob %s or the map %s holds 2^31 bytes or more' % (tuple(prob.shape), (S, RH, RW, K)))
+    out = _new((S, RH, RW, K), prob)
+    if S:
+        N.call('mmseg_blend_tiles', _c(prob), rows, cols, wr, wc, out, S, TR, TC, OH, OW, C, K, RH, RW)
+    return out
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

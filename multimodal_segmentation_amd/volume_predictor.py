@@ -30,6 +30,13 @@ fill_holes='2d' | '3d' (build-defined, off by default; the rule is in INTEGRATIO
 encloses to that organ's grey value (ops.fill_label_holes, on the file grid as well): slice by slice with '2d', in the volume with
 '3d'.  It runs after the component filter, so that an island which the filter turned into zeros inside an organ is closed again.
 
+tiles=True (build-defined, off by default; the rule is in INTEGRATION.md section 5) predicts the whole resampled frame instead of its
+centre input_shape window: per volume and predicted modality the frame is cut into overlapping tiles (loaders/volume_folder.tile_axis,
+tile_overlap pixels at least, default half the input extent), the tiles of every modality go through predict_mask as one batch of
+TR*TC*S slices, ops.blend_tiles blends the probability maps on the frame and ops.restore_label takes the whole frame as its window, so
+that no raw pixel is cropped away.  A frame that one tile holds takes the path without the option.  predictions.json then carries
+`tiles`, `tile_overlap` and per file `tile_origins`.
+
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
 from the counts summed over the organs, then the mean over the selected slices.
 
@@ -48,7 +55,7 @@ import numpy as np
 import torch
 
 from . import nn, ops
-from .loaders.volume_folder import VolumeFolderLoader
+from .loaders.volume_folder import VolumeFolderLoader, tile_weights
 from .model_tester import FUSION_MODES, write_results
 
 log = logging.getLogger('volume_predictor')
@@ -168,6 +175,20 @@ def fill_holes(pred, values, geometry, mode):
     on_grid, where = _on_file_grid(pred, geometry)
     filled, stats = ops.fill_label_holes(on_grid, values, mode)
     return filled.index_select(0, where), stats
+
+
+def check_tile_overlap(tile_overlap, input_shape):
+    """tile_overlap: None (half the input extent per axis), one number of pixels for both axes or (rows, columns) -> (rows, columns);
+    0 <= overlap < the input extent of its axis"""
+    extent = (int(input_shape[0]), int(input_shape[1]))
+    if tile_overlap is None:
+        return extent[0] // 2, extent[1] // 2
+    pair = tuple(tile_overlap) if isinstance(tile_overlap, (tuple, list)) else (tile_overlap, tile_overlap)
+    whole = len(pair) == 2 and all(isinstance(o, (int, np.integer)) and not isinstance(o, bool) for o in pair)
+    if not whole or any(not 0 <= int(o) < n for o, n in zip(pair, extent)):
+        raise ValueError('tile_overlap (--predict_tile_overlap) must be a whole number of pixels in [0, input extent) per axis: the input '
+                         'is %d x %d, got %r' % (extent[0], extent[1], tile_overlap))
+    return int(pair[0]), int(pair[1])
 
 
 _fill_holes = fill_holes          # for score_folder and VolumePredictor.run, whose keyword carries the function's name
@@ -307,8 +328,20 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
+    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded):
+        """the blended probability map [S,RH,RW,K] of modality m on its whole resampled frame: the tiles are loaded
+        (loader.load_volume_tiles), predicted as one batch of TR*TC*S slices and blended (ops.blend_tiles).  overlap = (rows, columns);
+        uploaded: loader.upload_volume(volume)"""
+        images, geometry, plan = loader.load_volume_tiles(volume, m, overlap, uploaded)
+        rows, cols = plan[m]
+        OH, OW = loader.input_shape[:2]
+        prob = self.predict_volume(m, mode, images)
+        S = images[m].shape[0] // (len(rows) * len(cols))
+        return ops.blend_tiles(prob, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'],
+                               loader.num_masks)
+
     def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
-            fill_holes=None):
+            fill_holes=None, tiles=False, tile_overlap=None):
         check_components(components, connectivity)
         check_fill_holes(fill_holes)
         robust = check_robust(robust)
@@ -324,6 +357,7 @@ class VolumePredictor(object):
             raise ValueError('%s is prepared for input_shape %s and %d organs, the model is built for %s and %d'
                              % (folder, loader.input_shape[:2], loader.num_masks, tuple(self.conf.input_shape[:2]),
                                 self.conf.num_masks))
+        overlap = check_tile_overlap(tile_overlap, loader.input_shape) if tiles else None
         volumes = list(loader.manifest['volumes']) if volumes is None else [str(v) for v in volumes]
         for v in volumes:
             if v not in loader.manifest['volumes']:
@@ -334,10 +368,25 @@ class VolumePredictor(object):
         sheet = ScoreSheet(loader.modalities, loader.num_masks, surface or robust is not None)
         files = {}
         for v in volumes:
-            images, geometry = loader.load_volume_for_prediction(v)
+            if tiles:
+                uploaded = loader.upload_volume(v)
+                images, geometry = None, uploaded[1]
+            else:
+                images, geometry = loader.load_volume_for_prediction(v)
             for m, geo in enumerate(geometry):
-                prob = self.predict_volume(m, mode, images)
-                pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
+                origins = None
+                if tiles:
+                    rows, cols = loader.tile_plan(geometry, m, overlap)[m]
+                    origins = dict(rows=[t[0] for t in rows], cols=[t[0] for t in cols])
+                if tiles and len(rows) * len(cols) > 1:
+                    RH, RW = geo['resampled']
+                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded)
+                    pred = ops.restore_label(prob, values, geo['raw_shape'][1:], (RH, RW), (0, RH, 0), (0, RW, 0), order)
+                else:          # one tile: the centre window of crop_pad_map, the path without the option
+                    if images is None:
+                        images, _ = loader.load_volume_for_prediction(v)
+                    prob = self.predict_volume(m, mode, images)
+                    pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
                 if components:
                     pred, stats = keep_largest(pred, values, geo, connectivity)
                     sheet.add_components(m, v, stats)
@@ -352,6 +401,8 @@ class VolumePredictor(object):
                 extra = {} if geo['slice_spacing'] is None else dict(slice_spacing=float(geo['slice_spacing']))
                 np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
                 files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
+                if origins is not None:
+                    files[geo['file']]['tile_origins'] = origins
         sheet.write(out_folder)
         settings = dict(source_folder=folder, mode=mode, order=order, model_folder=self.conf.get('folder'),
                         label_values=loader.label_values, files=files)
@@ -361,6 +412,8 @@ class VolumePredictor(object):
             settings.update(fill_holes=fill_holes)
         if robust is not None:
             settings.update(percentile=robust[0], tolerance_mm=robust[1])
+        if tiles:
+            settings.update(tiles=True, tile_overlap=list(overlap))
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
         return sheet.by_name('native')
