@@ -527,6 +527,20 @@ int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsign
 int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const float* wr, const float* wc, float* out, int S, int TR,
                       int TC, int OH, int OW, int C, int K, int RH, int RW, void* stream);
 
+/* ---- views of a slice, merged: test-time augmentation (csrc/postprocess.hip; build-defined, the rule is in INTEGRATION.md section 5) ----
+ * prob [V*N,OH,OW,C] fp32: the segmentor's output for V views of N slices, view-major (view v holds slices v * N ..), the K organ channels
+ * first.  back [V,6] fp64 on the device: per view the matrix that takes an image pixel (r, c) to the view pixel that shows it, in
+ * mmseg_augment_gather's convention.  out [N,OH,OW,K] fp32, every element written.  Per output pixel and view, in ascending v:
+ * sr = (b0 * r + b1 * c) + b2, sc = (b3 * r + b4 * c) + b5 in fp64 without contraction; the view covers the pixel iff 0 <= sr <= OH - 1
+ * and 0 <= sc <= OW - 1 (a NaN covers nothing); its sample is bilinear on the taps floor and floor + 1 (limited to the container), the
+ * fractions cast to fp32, v = (1-fy)*((1-fx)*a00 + fx*a01) + fy*((1-fx)*a10 + fx*a11) in fp32 in that order, a zero fraction skipping
+ * its taps: an integer coordinate returns the tap bit for bit.  num = the sum of the covering views' samples from 0 in that order,
+ * in fp32 without contraction; out = num / (float)cnt; cnt == 1 copies the sample unchanged, cnt == 0 gives 0.  A gather without
+ * atomics: two runs are bitwise equal.  1 <= V <= 16, 1 <= K <= min(C, 16), extents >= 1, N * OH * OW < 2^29; anything else or a null
+ * pointer is refused (hipErrorInvalidValue, nothing is launched); out must not alias prob.  N == 0 does nothing.  No host
+ * synchronisation, allocation or copy. */
+int mmseg_merge_views(const float* prob, const double* back, float* out, int V, int N, int OH, int OW, int C, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

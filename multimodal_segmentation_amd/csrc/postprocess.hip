@@ -64,6 +64,12 @@
 //   the covering tiles at every pixel of the resampled frame, weights wr[tr][iy] * wc[tc][ix].  A gather: every output element is
 //   written by one thread, the covering tiles are visited in ascending (tr, tc) order, so two runs are bitwise equal; a pixel that one
 //   tile covers is copied.  mmseg_restore_label then takes the whole frame as its window.
+//
+// Views of a slice, merged (test-time augmentation; build-defined; the rule is in INTEGRATION.md section 5).
+// mmseg_merge_views: prob [V*N,OH,OW,C], the segmentor's output for V views of N slices, view-major -> out [N,OH,OW,K], at every pixel the
+//   mean over the views that cover it of the view's map sampled bilinearly at back[v] (r, c), an fp64 2 x 3 matrix per view.  A gather
+//   like the blend: one thread per output element, the views in ascending order, two runs bitwise equal; a pixel that one view covers
+//   is that view's sample, and an integer coordinate (every flip and right-angle turn) is a tap, copied.
 #include "common.hpp"
 #include <math.h>
 
@@ -231,6 +237,84 @@ __global__ void __launch_bounds__(PO_BLOCK) po_blend_kernel(const float* __restr
         // one covering tile: its value as it is (no multiply, no divide); none: 0
         if constexpr (VEC4) reinterpret_cast<f32x4*>(out)[e] = cnt == 1 ? first4 : cnt == 0 ? num4 : num4 / den;
         else out[e] = cnt == 1 ? first : cnt == 0 ? 0.f : num / den;
+    }
+}
+
+// ---- views of one slice (test-time augmentation), brought back and averaged -----------------------------------------------------------------
+#define MV_MAXVIEWS 16
+
+// one axis of one view's coordinate: taps i0 <= i1 inside [0, n), weight f of i1.  Only called for 0 <= s <= n - 1.
+__device__ __forceinline__ void mv_axis(double s, int n, int& i0, int& i1, float& f) {
+    const double fl = floor(s);
+    i0 = (int)fl;
+    i1 = min(i0 + 1, n - 1);
+    f = (float)(s - fl);
+}
+
+// augment_gather_kernel's order: a zero fraction skips its taps, so an integer coordinate returns the tap bit for bit; otherwise po_mix's
+// expression.  T = float (channel k of a pixel) or f32x4 (its four channels).
+template <typename T>
+__device__ __forceinline__ T mv_sample(const float* __restrict__ src, int OW, int C, int r0, int r1, int c0, int c1, float fy, float fx) {
+#pragma clang fp contract(off)
+    const T a00 = *reinterpret_cast<const T*>(src + ((size_t)r0 * OW + c0) * C);
+    T top = a00;
+    if (fx != 0.f) top = (1.f - fx) * a00 + fx * *reinterpret_cast<const T*>(src + ((size_t)r0 * OW + c1) * C);
+    if (fy == 0.f) return top;
+    const T a10 = *reinterpret_cast<const T*>(src + ((size_t)r1 * OW + c0) * C);
+    T bot = a10;
+    if (fx != 0.f) bot = (1.f - fx) * a10 + fx * *reinterpret_cast<const T*>(src + ((size_t)r1 * OW + c1) * C);
+    return (1.f - fy) * top + fy * bot;
+}
+
+// VEC4: a thread owns one pixel of the merged map, K == 4 channels as one 16-byte load per tap and one 16-byte store (C % 4 == 0, both
+// pointers 16-byte aligned).  Otherwise a thread owns one output float (pixel, k): consecutive lanes store consecutive floats and the
+// lanes of a pixel read consecutive channels of the same taps.  Grid-stride over total = N * OH * OW [* K] elements; N * OH * OW < 2^29,
+// so a pixel index fits an int, and `small` (total < 2^31, a launch constant) keeps the scalar path's division by K in 32 bits.
+// The sum runs over the covering views in ascending order, starting from 0, in fp32 without contraction.  A view covers the pixel iff
+// its fp64 coordinate lies inside [0, OH-1] x [0, OW-1] (a NaN fails every comparison), which also keeps every read inside `prob`.
+// A flip or a half turn reads rows backwards (whole cache lines all the same); a transposing view reads with a stride of one container
+// row between neighbouring lanes, out of L2, which holds a slice's container.
+template <bool VEC4>
+__global__ void __launch_bounds__(PO_BLOCK) po_merge_kernel(const float* __restrict__ prob, const double* __restrict__ back,
+                                                            float* __restrict__ out, int V, int N, int OH, int OW, int C, int K, long total,
+                                                            bool small) {
+#pragma clang fp contract(off)
+    __shared__ double mb[MV_MAXVIEWS * 6];
+    if (threadIdx.x < V * 6) mb[threadIdx.x] = back[threadIdx.x];
+    __syncthreads();
+    const int plane = OH * OW;
+    const double hr = (double)(OH - 1), hc = (double)(OW - 1);
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < total; e += (long)gridDim.x * PO_BLOCK) {
+        const int pix = VEC4 ? (int)e : small ? (int)((unsigned)e / (unsigned)K) : (int)(e / K);
+        const int k = VEC4 ? 0 : (int)(e - (long)pix * K);
+        const int s = pix / plane, q = pix - s * plane;
+        const int r = q / OW, c = q - r * OW;
+        int cnt = 0;
+        f32x4 num4 = {0.f, 0.f, 0.f, 0.f}, first4 = {0.f, 0.f, 0.f, 0.f};
+        float num = 0.f, first = 0.f;
+        for (int v = 0; v < V; ++v) {
+            const double* b = mb + 6 * v;
+            const double sr = (b[0] * r + b[1] * c) + b[2], sc = (b[3] * r + b[4] * c) + b[5];
+            if (!(sr >= 0.0 && sr <= hr && sc >= 0.0 && sc <= hc)) continue;
+            int r0, r1, c0, c1;
+            float fy, fx;
+            mv_axis(sr, OH, r0, r1, fy);
+            mv_axis(sc, OW, c0, c1, fx);
+            const float* src = prob + ((size_t)v * N + s) * plane * C;
+            if constexpr (VEC4) {
+                const f32x4 x = mv_sample<f32x4>(src, OW, C, r0, r1, c0, c1, fy, fx);
+                if (cnt == 0) first4 = x;
+                num4 = num4 + x;
+            } else {
+                const float x = mv_sample<float>(src + k, OW, C, r0, r1, c0, c1, fy, fx);
+                if (cnt == 0) first = x;
+                num = num + x;
+            }
+            ++cnt;
+        }
+        // one covering view: its sample as it is (no add, no divide); none: 0
+        if constexpr (VEC4) reinterpret_cast<f32x4*>(out)[e] = cnt == 1 ? first4 : cnt == 0 ? num4 : num4 / (float)cnt;
+        else out[e] = cnt == 1 ? first : cnt == 0 ? 0.f : num / (float)cnt;
     }
 }
 
@@ -500,7 +584,7 @@ __global__ void __launch_bounds__(PO_BLOCK) po_surface_final_kernel(const int* _
     }
 }
 
-// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep, the hole fill and the tile blend, PO_RED_BLOCKS
+// blocks of PO_BLOCK threads for n >= 1 elements, at most `cap`: PO_MAXBLK restore / overlap, PO_SURF_MAXBLK the surface sweep, the hole fill, the tile blend and the merge of views, PO_RED_BLOCKS
 // the reductions (po_surface_final_kernel adds that many partials with one block), OS_MAXBLK the order statistics, CC_MAXBLK the components
 static unsigned po_grid(long n, long cap) {
     const long b = (n + PO_BLOCK - 1) / PO_BLOCK;
@@ -1149,6 +1233,28 @@ int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const
     const hipStream_t st = (hipStream_t)stream;
     if (vec4) hipLaunchKernelGGL(po_blend_kernel<true>, grid, block, 0, st, prob, rows, cols, wr, wc, out, S, TR, TC, OH, OW, C, K, RH, RW, n);
     else hipLaunchKernelGGL(po_blend_kernel<false>, grid, block, 0, st, prob, rows, cols, wr, wc, out, S, TR, TC, OH, OW, C, K, RH, RW, n);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// prob [V*N,OH,OW,C] fp32 (view v holds slices v * N .. v * N + N - 1), back [V,6] fp64 on the device, out [N,OH,OW,K] fp32: every element is
+// written.  One launch; no atomics, nothing allocated or synchronised.
+int mmseg_merge_views(const float* prob, const double* back, float* out, int V, int N, int OH, int OW, int C, int K, void* stream) {
+    if (N == 0) return 0;
+    if (!prob || !back || !out || prob == out || N < 0 || V < 1 || V > MV_MAXVIEWS || OH < 1 || OW < 1 || C < 1 || K < 1 || K > C ||
+        K > PO_MAXVALUES)
+        return (int)hipErrorInvalidValue;
+    // factor by factor, so that the product does not overflow before it is compared
+    long pixels = N;
+    for (const int f : {OH, OW}) {
+        pixels *= f;
+        if (pixels >= (1L << 29)) return (int)hipErrorInvalidValue;
+    }
+    const bool vec4 = K == 4 && (C & 3) == 0 && ((uintptr_t)prob & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const long total = pixels * (vec4 ? 1 : K);
+    const dim3 grid(po_grid(total, PO_SURF_MAXBLK)), block(PO_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec4) hipLaunchKernelGGL(po_merge_kernel<true>, grid, block, 0, st, prob, back, out, V, N, OH, OW, C, K, total, true);
+    else hipLaunchKernelGGL(po_merge_kernel<false>, grid, block, 0, st, prob, back, out, V, N, OH, OW, C, K, total, total < 0x7fffffffL);
     return MMSEG_CHECK_LAUNCH();
 }
 

@@ -7,7 +7,7 @@
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
-                         [--predict_tiles true|false] [--predict_tile_overlap PIXELS]
+                         [--predict_tiles true|false] [--predict_tile_overlap PIXELS] [--predict_tta LIST]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
@@ -77,6 +77,10 @@ def parse_arguments(argv=None):
     ap.add_argument('--predict_tile_overlap', type=int, default=None, metavar='PIXELS',
                     help='least overlap of neighbouring tiles of --predict_tiles, 0 or more and below the input extent (default: half '
                          'the input extent per axis)')
+    ap.add_argument('--predict_tta', default='none', metavar='LIST',
+                    help='test-time augmentation: predict every slice under these views and average the maps brought back, e.g. '
+                         'id,fliplr,flipud,rot180 (= flips), d4 (the eight flips and right-angle turns) or id,rot10,rot-10 (degrees); '
+                         'the first view is id')
     args = ap.parse_args(argv)
     if args.predict_tile_overlap is not None and args.predict_tile_overlap < 0:
         ap.error('--predict_tile_overlap must be a number of pixels >= 0, got %r' % args.predict_tile_overlap)
@@ -243,7 +247,8 @@ class Experiment(object):
                                               connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args),
                                               fill_holes={'2d': '2d', '3d': '3d'}.get(getattr(args, 'predict_fill_holes', 'none')),
                                               tiles=bool(getattr(args, 'predict_tiles', False)),
-                                              tile_overlap=getattr(args, 'predict_tile_overlap', None))
+                                              tile_overlap=getattr(args, 'predict_tile_overlap', None),
+                                              tta=getattr(args, 'predict_tta', None))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 
@@ -257,6 +262,9 @@ class Experiment(object):
         if getattr(args, 'predict_tiles', False) or getattr(args, 'predict_tile_overlap', None) is not None:      # before the model is built
             from .volume_predictor import check_tile_overlap
             check_tile_overlap(getattr(args, 'predict_tile_overlap', None), conf.input_shape)
+        if getattr(args, 'predict_tta', 'none') not in (None, 'none'):          # before the model is built as well
+            from .volume_predictor import check_tta
+            check_tta(args.predict_tta, conf.input_shape)
         if getattr(args, 'predict_folder', None) and args.test:
             from .volume_predictor import checkpoint_of
             if checkpoint_of(conf.folder) is None:          # before the test pass evaluates an untrained model

@@ -1869,6 +1869,32 @@ def blend_tiles(prob, rows, cols, wr, wc, S, resampled, K):
     return out
 
 
+MAX_VIEWS = 16          # csrc/postprocess.hip
+
+
+def merge_views(prob, back, N_, K):
+    """prob [V*N,OH,OW,C] fp32 on the device: a segmentor's output for V views of N slices, view-major (view v holds slices v * N ..),
+    organ channels first -> fp32 [N,OH,OW,K], at every pixel the mean over the views that cover it of the view's map sampled at
+    back[v] (r, c) (csrc/postprocess.hip).  back [V,6] fp64: per view the matrix from an image pixel to the view pixel that shows it,
+    in augment_gather's convention; a host array or a device tensor.  A pixel that one view covers is that view's sample as it is, a
+    pixel that none covers gets 0, and an integer coordinate is a copy.  No gradient."""
+    n, K = int(N_), int(K)
+    b = back if isinstance(back, torch.Tensor) else torch.as_tensor(back, dtype=torch.float64)
+    if b.dim() != 2 or b.dtype != torch.float64 or b.shape[1] != 6 or not 1 <= b.shape[0] <= MAX_VIEWS:
+        raise ValueError('merge_views: expected a [1..%d, 6] float64 table of views, got %s %s' % (MAX_VIEWS, tuple(b.shape), b.dtype))
+    if prob.dim() != 4 or prob.dtype != torch.float32 or n < 0 or not 1 <= K <= min(16, prob.shape[3]):
+        raise ValueError('merge_views: prob %s %s, N = %d, K = %d' % (tuple(prob.shape), prob.dtype, n, K))
+    V, (M, OH, OW, C) = b.shape[0], prob.shape
+    if M != V * n:
+        raise ValueError('merge_views: prob %s does not hold %d views of %d slices' % (tuple(prob.shape), V, n))
+    if prob.numel() * 4 >= 2 ** 31:
+        raise ValueError('merge_views: prob %s holds 2^31 bytes or more' % (tuple(prob.shape),))
+    out = _new((n, OH, OW, K), prob)
+    if n:
+        N.call('mmseg_merge_views', _c(prob), _c(b.to(prob.device)), out, V, n, OH, OW, C, K)
+    return out
+
+
 def _sum_n(gs, like):
     """sum of 1..n same-shaped tensors in as few launches as possible (8 operands per launch, left to right)"""
     gs = [_c(g) for g in gs]

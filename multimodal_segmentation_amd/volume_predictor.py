@@ -37,6 +37,12 @@ TR*TC*S slices, ops.blend_tiles blends the probability maps on the frame and ops
 that no raw pixel is cropped away.  A frame that one tile holds takes the path without the option.  predictions.json then carries
 `tiles`, `tile_overlap` and per file `tile_origins`.
 
+tta='id,fliplr,...' (build-defined, off by default; the rule and the table of views are in INTEGRATION.md section 5) predicts every
+slice under several views (flips, right-angle turns, small rotations: the transformations the models are trained under), brings every
+view's probability map back and averages them: ops.augment_gather makes the V*N views of the N containers of every modality,
+predict_mask runs over them in batches, ops.merge_views merges the maps on the device, and the way back goes on from the merged map.
+With tiles=True the views act on the tile containers, and the merged tiles are blended.  predictions.json then carries `tta`.
+
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
 from the counts summed over the organs, then the mean over the selected slices.
 
@@ -47,8 +53,10 @@ thing that leaves the device.  With robust=(percentile, tolerance) (build-define
 section 5) ops.surface_scores takes its place: the same table with two more columns, from the same distance transforms, so that one
 call serves both CSV files.  `score_volume` and `ScoreSheet` are shared with tools/score_predictions.py, which scores label
 volumes written earlier (`score_folder`)."""
+import collections
 import json
 import logging
+import math
 import os
 
 import numpy as np
@@ -191,6 +199,107 @@ def check_tile_overlap(tile_overlap, input_shape):
     return int(pair[0]), int(pair[1])
 
 
+MAX_VIEWS = ops.MAX_VIEWS
+EXACT_VIEWS = ('id', 'fliplr', 'flipud', 'rot180', 'transpose', 'antitranspose', 'rot90', 'rot270')
+TRANSPOSING_VIEWS = EXACT_VIEWS[4:]
+VIEW_PRESETS = dict(flips=EXACT_VIEWS[:4], d4=EXACT_VIEWS)
+# tokens: the expanded list; forward / back: [V,6] fp64, per view the matrices F (view pixel -> the image pixel it shows) and B (image pixel
+# -> the view pixel that shows it) in ops.augment_gather's convention (m0*r + m1*c + m2, m3*r + m4*c + m5)
+Views = collections.namedtuple('Views', ('tokens', 'forward', 'back'))
+
+
+def _rotation(theta, cy, cx):
+    """the turn by theta about the centre (cy, cx) of the container"""
+    cos, sin = math.cos(theta), math.sin(theta)
+    return [cos, -sin, cy - cos * cy + sin * cx, sin, cos, cx - sin * cy - cos * cx]
+
+
+def view_matrices(token, OH, OW):
+    """(F, B) of one token (the table of INTEGRATION.md section 5), each six floats; written out per token, never inverted numerically.
+    The eight exact tokens hold 0, +-1 and whole offsets only.  Raises ValueError for a token the table does not have."""
+    h, w = float(OH - 1), float(OW - 1)
+    same = dict(id=[1., 0., 0., 0., 1., 0.], fliplr=[1., 0., 0., 0., -1., w], flipud=[-1., 0., h, 0., 1., 0.],
+                rot180=[-1., 0., h, 0., -1., w], transpose=[0., 1., 0., 1., 0., 0.], antitranspose=[0., -1., w, -1., 0., h])
+    if token in same:
+        return same[token], list(same[token])
+    quarter, three = [0., 1., 0., -1., 0., w], [0., -1., h, 1., 0., 0.]          # (c, OW-1-r) and (OH-1-c, r)
+    if token == 'rot90':
+        return quarter, three
+    if token == 'rot270':
+        return three, quarter
+    try:
+        if not token.startswith('rot'):
+            raise ValueError(token)
+        degrees = float(token[3:])
+    except ValueError:
+        raise ValueError('unknown view %r' % (token,))
+    if not math.isfinite(degrees) or math.fmod(degrees, 360.0) == 0.0:
+        raise ValueError('view %r: the angle must be finite and no multiple of 360 degrees' % (token,))
+    theta = degrees * math.pi / 180
+    return _rotation(theta, h / 2, w / 2), _rotation(-theta, h / 2, w / 2)
+
+
+def check_tta(tta, input_shape):
+    """tta: None, 'none' or 'id' (off) -> None; else a comma-separated list or a sequence of tokens and presets (EXACT_VIEWS, 'rotA' with A
+    in degrees, VIEW_PRESETS) -> Views for containers of input_shape: 1 to 16 distinct views, the identity first (it covers every
+    pixel, so the mean over the covering views never divides by nothing), transposing views on square inputs only"""
+    OH, OW = int(input_shape[0]), int(input_shape[1])
+
+    def refuse(why):
+        raise ValueError('tta (--predict_tta) must be a list of views (%s, rotA with A in degrees; presets %s) that begins with id: the '
+                         'input is %d x %d, got %r: %s' % (', '.join(EXACT_VIEWS), ', '.join(sorted(VIEW_PRESETS)), OH, OW, tta, why))
+    if tta is None:
+        return None
+    if isinstance(tta, str):
+        listed = tta.split(',')
+    else:
+        try:
+            listed = list(tta)
+        except TypeError:
+            refuse('neither a string nor a sequence')
+    tokens = []
+    for t in listed:
+        if not isinstance(t, str):
+            refuse('%r is no token' % (t,))
+        t = t.strip().lower()
+        tokens.extend(VIEW_PRESETS.get(t, (t,)))
+    if tokens in (['none'], ['id']):
+        return None
+    if not tokens or tokens[0] != 'id':
+        refuse('the first view must be id')
+    if len(tokens) > MAX_VIEWS:
+        refuse('%d views, at most %d' % (len(tokens), MAX_VIEWS))
+    forward, back, seen = [], [], set()
+    for t in tokens:
+        try:
+            F, B = view_matrices(t, OH, OW)
+        except ValueError as e:
+            refuse(str(e))
+        key = t if t in EXACT_VIEWS else float(t[3:])
+        if key in seen:
+            refuse('view %r is listed twice' % (t,))
+        seen.add(key)
+        if t in TRANSPOSING_VIEWS and OH != OW:
+            refuse('view %r needs a square input' % (t,))
+        forward.append(F)
+        back.append(B)
+    return Views(tuple(tokens), np.asarray(forward, np.float64), np.asarray(back, np.float64))
+
+
+def views_in(images, views):
+    """images: per modality a container [N,OH,OW,1] on the device -> per modality [V*N,OH,OW,1], view-major: every modality under the
+    same views (ops.augment_gather with F, order 1, edge repeated).  The exact views are permutations of the input, bit for bit."""
+    N, OH, OW = (int(n) for n in images[0].shape[:3])
+    V = len(views.tokens)
+    if V * N > 65535 or max(V * x.numel() for x in images) * 4 >= 2 ** 31:
+        raise ValueError('tta (--predict_tta): %d views of %d slices of %d x %d make %d containers: at most 65535, of less than 2^31 '
+                         'bytes together, go through the network at once' % (V, N, OH, OW, V * N))
+    device = images[0].device
+    rows = nn.host_to_device(np.tile(np.arange(N), V), device, np.int32)
+    mats = nn.host_to_device(np.repeat(views.forward, N, axis=0), device, np.float64)
+    return [ops.augment_gather(ops._c(x), rows, mats, None, 1, 'nearest') for x in images]
+
+
 _fill_holes = fill_holes          # for score_folder and VolumePredictor.run, whose keyword carries the function's name
 
 
@@ -328,20 +437,32 @@ class VolumePredictor(object):
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
-    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded):
+    def predict_views(self, modality_index, mode, images, views):
+        """the merged probability map [N,OH,OW,K] of the N slices of `images` (per modality a container [N,OH,OW,1]): every slice is
+        shown to the network under each of the V views (views_in; all modalities alike), predict_volume runs over the V*N slices, and
+        ops.merge_views brings every view's map back and averages them.  views: check_tta's."""
+        N = int(images[0].shape[0])
+        prob = self.predict_volume(modality_index, mode, views_in(images, views))
+        if prob.numel() * 4 >= 2 ** 31:
+            raise ValueError('tta (--predict_tta): the maps of %d views of %d slices, %s, hold 2^31 bytes or more'
+                             % (len(views.tokens), N, tuple(prob.shape)))
+        return ops.merge_views(prob, views.back, N, int(self.conf.num_masks))
+
+    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded, views=None):
         """the blended probability map [S,RH,RW,K] of modality m on its whole resampled frame: the tiles are loaded
         (loader.load_volume_tiles), predicted as one batch of TR*TC*S slices and blended (ops.blend_tiles).  overlap = (rows, columns);
-        uploaded: loader.upload_volume(volume)"""
+        uploaded: loader.upload_volume(volume).  With views (check_tta's) every tile is predicted under each view, turned about its own
+        centre, and merged (predict_views) before the blend, which then sees the K organ channels alone."""
         images, geometry, plan = loader.load_volume_tiles(volume, m, overlap, uploaded)
         rows, cols = plan[m]
         OH, OW = loader.input_shape[:2]
-        prob = self.predict_volume(m, mode, images)
+        prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
         S = images[m].shape[0] // (len(rows) * len(cols))
         return ops.blend_tiles(prob, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'],
                                loader.num_masks)
 
     def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
-            fill_holes=None, tiles=False, tile_overlap=None):
+            fill_holes=None, tiles=False, tile_overlap=None, tta=None):
         check_components(components, connectivity)
         check_fill_holes(fill_holes)
         robust = check_robust(robust)
@@ -358,6 +479,7 @@ class VolumePredictor(object):
                              % (folder, loader.input_shape[:2], loader.num_masks, tuple(self.conf.input_shape[:2]),
                                 self.conf.num_masks))
         overlap = check_tile_overlap(tile_overlap, loader.input_shape) if tiles else None
+        views = check_tta(tta, loader.input_shape)
         volumes = list(loader.manifest['volumes']) if volumes is None else [str(v) for v in volumes]
         for v in volumes:
             if v not in loader.manifest['volumes']:
@@ -380,12 +502,12 @@ class VolumePredictor(object):
                     origins = dict(rows=[t[0] for t in rows], cols=[t[0] for t in cols])
                 if tiles and len(rows) * len(cols) > 1:
                     RH, RW = geo['resampled']
-                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded)
+                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded, views)
                     pred = ops.restore_label(prob, values, geo['raw_shape'][1:], (RH, RW), (0, RH, 0), (0, RW, 0), order)
                 else:          # one tile: the centre window of crop_pad_map, the path without the option
                     if images is None:
                         images, _ = loader.load_volume_for_prediction(v)
-                    prob = self.predict_volume(m, mode, images)
+                    prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
                     pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
                 if components:
                     pred, stats = keep_largest(pred, values, geo, connectivity)
@@ -414,6 +536,8 @@ class VolumePredictor(object):
             settings.update(percentile=robust[0], tolerance_mm=robust[1])
         if tiles:
             settings.update(tiles=True, tile_overlap=list(overlap))
+        if views is not None:
+            settings.update(tta=list(views.tokens))
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
         return sheet.by_name('native')
