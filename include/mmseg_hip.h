@@ -513,6 +513,31 @@ long mmseg_fill_label_holes_workspace_bytes(int S, int H, int W, int K);
 int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W,
                            int K, int per_slice, void* stream);
 
+/* ---- opening, closing and smoothing of every organ by a ball in mm (csrc/postprocess.hip; build-defined, the rule is in INTEGRATION.md
+ * section 5) ------------------------------------------------------------------------------------------------------------------------------
+ * The ball.  For an integer offset o = (oz, oy, ox), t(o) in fp64 without contraction other than the fmas named: a = dx * ox, t = a * a;
+ * b = dy * oy, t = fma(b, b, t); c = dz * oz, t = fma(c, c, t): the order of the W, H and S passes of mmseg_distance_to_sites.
+ * B = { o : t(o) <= radius * radius }, the rounded fp64 product.  per_slice 1: only oz == 0 belongs to B and dz is not read.
+ * For a set X of voxels of the volume: erode(X) keeps p in X iff no voxel q OF THE VOLUME outside X has q - p in B (what lies outside the
+ * volume is no background: scipy.ndimage.binary_erosion(X, B, border_value=1)); dilate(X) holds p iff some q in X has q - p in B
+ * (scipy.ndimage.binary_dilation(X, B)); open(X) = dilate(erode(X)), a subset of X; close(X) = erode(dilate(X)), a superset of X.
+ * With X_k = (label == values[k]):
+ *   op 0, open    a voxel of values[k] outside open(X_k) becomes 0
+ *   op 1, close   a voxel that is 0 in label and lies in close(X_k) becomes values[k]; where several organs claim it the lowest k wins;
+ *                 other organs and foreign grey values are never overwritten, and do not stop a dilation from passing
+ *   op 2, smooth  op 0 on label gives L1, then op 1 with L1 as its input
+ * radius and the spacings in use finite and > 0; the reach floor(radius / spacing) per axis in use at most 32; S * H * W < 2^31 - 1,
+ * 1 <= H, W, 1 <= K <= 16; anything else, another op or per_slice or a null pointer is refused (hipErrorInvalidValue, nothing is
+ * launched).  S == 0 does nothing.  A radius below every spacing in use gives B = {0}: out = label. */
+/* bytes of ws for mmseg_smooth_label (about 3 per voxel); 0 for arguments that it would refuse */
+long mmseg_smooth_label_workspace_bytes(int S, int H, int W, int K);
+/* out [S,H,W] uint8 as above; stats [K,3] int32 = (voxels of values[k] in label, voxels removed, voxels added), (0, 0, 0) for an organ
+ * without voxels.  Every byte of out and stats is written; out must not alias label.  ws is the only scratch.  Work per voxel follows
+ * the window of the ball (2 * reach + 1 per axis), an axis of reach 0 costs no pass.  Integer atomics only, so two runs are bitwise
+ * equal.  No kernel waits for another block; no host synchronisation, allocation or copy. */
+int mmseg_smooth_label(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W, int K,
+                       double dz, double dy, double dx, double radius, int op, int per_slice, void* stream);
+
 /* ---- tiles of a frame larger than the network's input (csrc/postprocess.hip; build-defined, the rule is in INTEGRATION.md section 5) ----
  * prob [TR*TC,S,OH,OW,C] fp32: the segmentor's output for every tile of a TR x TC plan (tile tr * TC + tc), the K organ channels
  * first.  rows [TR,3] and cols [TC,3] int32 = (lo, kept, before) per tile and axis, wr [TR,OH] and wc [TC,OW] fp32 weights, all on the

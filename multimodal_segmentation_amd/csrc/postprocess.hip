@@ -59,6 +59,16 @@
 //   only, in 3-D or slice by slice), a mark on the root of every set that holds a border voxel (an idempotent byte store), and a pass
 //   that gives the input's zeros in unmarked sets to the organ where `out` still holds 0: the lowest k wins.
 //
+// Opening, closing and smoothing of every organ by a ball in mm (build-defined; the rule is in INTEGRATION.md section 5 and the header).
+// mmseg_smooth_label: a windowed kernel pair, not po_edt: the cost follows the reach of the ball, not the extent of the volume.  One
+//   block writes the row table of the ball (per (|oz|, |oy|) the largest ox inside it, from t(o) in the order of po_edt's passes); then,
+//   per organ and erosion or dilation, po_mo_run_kernel maps every voxel to the distance along x to the nearest site of its row (a byte,
+//   capped at the reach) and po_mo_ball_kernel asks, per row of the ball inside the volume, whether that byte is within the row's reach:
+//   (2 rz + 1)(2 ry + 1) bytes per voxel at most, read by consecutive lanes from consecutive addresses, with an early exit, and only for
+//   the voxels whose answer is open.  "min over sites of the separable squared distance <= r^2" and "a site at an offset in the ball" are
+//   the same statement bit for bit, fma(b, b, v) being monotone in v.  An axis of reach 0 adds nothing: no run map along x, one row
+//   along y or z.  Erosion never looks outside the volume, so the volume's faces erode nothing.
+//
 // Frames larger than the network's input (build-defined; the rule is in INTEGRATION.md section 5).
 // mmseg_blend_tiles: prob [TR*TC,S,OH,OW,C], the segmentor's output for every tile of a TR x TC plan -> out [S,RH,RW,K], the weighted mean of
 //   the covering tiles at every pixel of the resampled frame, weights wr[tr][iy] * wc[tc][ix].  A gather: every output element is
@@ -1128,6 +1138,207 @@ static bool po_fh_args_ok(int S, int H, int W, int K, int per_slice) {
 // the workspace of mmseg_fill_label_holes: comp [n] int32, then mark [n] bytes
 static long po_fh_workspace_bytes(long n) { return (long)sizeof(int) * n + 4 * ((n + 3) / 4); }
 
+// ---- opening, closing and smoothing of every organ by a ball in mm ------------------------------------------------------------------------
+#define MO_MAXREACH 32          // voxels per axis; the row table below has (MO_MAXREACH + 1)^2 entries
+#define MO_TABLE ((MO_MAXREACH + 1) * (MO_MAXREACH + 1))
+#define MO_TABLE_BYTES 2048     // of the workspace, a multiple of 8 above MO_TABLE
+#define MO_NONE 255             // a run: no site within the reach along x
+
+// t(o) of the rule, in the order of the W, H and S passes of po_edt; flat (one slice at a time): dz is not read
+__host__ __device__ static inline double mo_t(double dz, double dy, double dx, int oz, int oy, int ox, bool flat) {
+#pragma clang fp contract(off)
+    const double a = dx * (double)ox;
+    double t = a * a;
+    const double b = dy * (double)oy;
+    t = __builtin_fma(b, b, t);
+    if (!flat) {
+        const double c = dz * (double)oz;
+        t = __builtin_fma(c, c, t);
+    }
+    return t;
+}
+
+// table[oz * (ry + 1) + oy] = the largest ox <= rx with (oz, oy, ox) in the ball, -1 when the row holds none; t grows with |ox|.  One block.
+__global__ void __launch_bounds__(PO_BLOCK) po_mo_table_kernel(signed char* __restrict__ table, double dz, double dy, double dx, double r2,
+                                                               int rz, int ry, int rx, int flat) {
+    for (int i = threadIdx.x; i < (rz + 1) * (ry + 1); i += PO_BLOCK) {
+        const int oz = i / (ry + 1), oy = i - oz * (ry + 1);
+        int reach = -1;
+        for (int ox = 0; ox <= rx && mo_t(dz, dy, dx, oz, oy, ox, flat != 0) <= r2; ++ox) reach = ox;
+        table[i] = (signed char)reach;
+    }
+}
+
+// a voxel of src is a site when (src == v) == EQ; v = values[k], or 1 for a mask (k < 0)
+__device__ __forceinline__ int mo_value(const int* __restrict__ values, int k) { return k < 0 ? 1 : values[k]; }
+
+// run[e] = the distance in voxels along x from e to the nearest site of its row, MO_NONE when there is none within rx.  Grid-stride;
+// at most 2 rx + 1 bytes of the row are read per voxel, consecutive lanes read consecutive bytes.
+template <bool EQ>
+__global__ void __launch_bounds__(PO_BLOCK) po_mo_run_kernel(const unsigned char* __restrict__ src, const int* __restrict__ values, int k,
+                                                             unsigned char* __restrict__ run, int W, int rx, long n) {
+    const int v = mo_value(values, k);
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int x = (int)(e % W);
+        const unsigned char* row = src + (e - x);
+        const int lim = min(rx, max(x, W - 1 - x));
+        int d = MO_NONE;
+        for (int o = 0; o <= lim; ++o) {
+            const bool left = x - o >= 0 && ((row[x - o] == v) == EQ);
+            const bool right = x + o < W && ((row[x + o] == v) == EQ);
+            if (left || right) {
+                d = o;
+                break;
+            }
+        }
+        run[e] = (unsigned char)d;
+    }
+}
+
+// is there a site q inside the volume with q - (z, y, x) in the ball?  RUN: `from` is po_mo_run_kernel's map of the sites, one byte per
+// row of the ball; else rx == 0 and `from` is src itself.  Rows outside the volume are not visited.
+template <bool EQ, bool RUN>
+__device__ __forceinline__ bool mo_hit(const unsigned char* __restrict__ from, int v, const signed char* tab, int z, int y, int x, int S,
+                                       int H, int W, int rz, int ry) {
+    const int z0 = max(-rz, -z), z1 = min(rz, S - 1 - z), y0 = max(-ry, -y), y1 = min(ry, H - 1 - y);
+    for (int oz = z0; oz <= z1; ++oz) {
+        const signed char* trow = tab + abs(oz) * (ry + 1);
+        const unsigned char* col = from + ((long)(z + oz) * H + y) * W + x;
+        for (int oy = y0; oy <= y1; ++oy) {
+            const int reach = trow[abs(oy)];
+            if (reach < 0) continue;
+            const int b = col[(long)oy * W];
+            if (RUN ? b <= reach : (b == v) == EQ) return true;
+        }
+    }
+    return false;
+}
+
+// The four passes over the rows of the ball; v = values[k], m = the mask of the pass before.
+//   MO_ERODE   m[e]   = lab[e] == v and no voxel != v of the volume within the ball                       (sites: lab != v)
+//   MO_OPEN    out[e] = 0 where lab[e] == v and no voxel of m within the ball, else lab[e]                (sites: m)
+//   MO_DILATE  m[e]   = lab[e] == v or a voxel == v within the ball                                       (sites: lab == v)
+//   MO_CLOSE   out[e] = v where lab[e] == 0, m[e], no voxel outside m within the ball and out[e] is still 0; else lab[e]   (sites: not m)
+// first (k == 0): out holds nothing yet, and every byte of it is written here; later organs touch their own voxels (MO_OPEN) or
+// zeros (MO_CLOSE) only, and this thread alone touches out[e].  stats[k] += (voxels == v when `before`, removed, added).
+enum { MO_ERODE = 0, MO_OPEN = 1, MO_DILATE = 2, MO_CLOSE = 3 };
+
+template <int PASS, bool RUN>
+__global__ void __launch_bounds__(PO_BLOCK) po_mo_ball_kernel(const unsigned char* __restrict__ lab, const int* __restrict__ values, int k,
+                                                              const unsigned char* __restrict__ from, const unsigned char* __restrict__ m,
+                                                              unsigned char* dst, int* __restrict__ stats,
+                                                              const signed char* __restrict__ table, int S, int H, int W, int rz, int ry,
+                                                              int first, int before) {
+    __shared__ signed char tab[MO_TABLE];
+    __shared__ int red[3];
+    for (int i = threadIdx.x; i < (rz + 1) * (ry + 1); i += PO_BLOCK) tab[i] = table[i];
+    if (threadIdx.x < 3) red[threadIdx.x] = 0;
+    __syncthreads();
+    const int v = values[k];
+    const long plane = (long)H * W, n = plane * S;
+    int own = 0, removed = 0, added = 0;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const int z = (int)(e / plane);
+        const int r = (int)(e - (long)z * plane);
+        const int y = r / W, x = r - y * W;
+        const int g = lab[e];
+        if constexpr (PASS == MO_ERODE) {
+            dst[e] = g == v && !mo_hit<false, RUN>(from, v, tab, z, y, x, S, H, W, rz, ry);
+        } else if constexpr (PASS == MO_DILATE) {
+            dst[e] = g == v || mo_hit<true, RUN>(from, v, tab, z, y, x, S, H, W, rz, ry);
+        } else if constexpr (PASS == MO_OPEN) {
+            own += g == v;
+            const bool gone = g == v && !m[e] && !mo_hit<true, RUN>(from, 1, tab, z, y, x, S, H, W, rz, ry);
+            if (first) dst[e] = (unsigned char)(gone ? 0 : g);
+            else if (gone) dst[e] = 0;
+            removed += gone;
+        } else {
+            own += g == v;
+            bool fill = g == 0 && m[e] && (first || dst[e] == 0);
+            fill = fill && !mo_hit<false, RUN>(from, 1, tab, z, y, x, S, H, W, rz, ry);
+            if (first) dst[e] = (unsigned char)(fill ? v : g);
+            else if (fill) dst[e] = (unsigned char)v;
+            added += fill;
+        }
+    }
+    if constexpr (PASS == MO_OPEN || PASS == MO_CLOSE) {
+        if (!before) own = 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            own += __shfl_xor(own, o, 64);
+            removed += __shfl_xor(removed, o, 64);
+            added += __shfl_xor(added, o, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            if (own) atomicAdd(&red[0], own);
+            if (removed) atomicAdd(&red[1], removed);
+            if (added) atomicAdd(&red[2], added);
+        }
+        __syncthreads();
+        if (threadIdx.x < 3 && red[threadIdx.x]) atomicAdd(stats + 3 * k + threadIdx.x, red[threadIdx.x]);          // one per block and counter
+    }
+}
+
+// what mmseg_smooth_label works with: the reach per axis in voxels (0 along the slices with per_slice) and the squared radius
+struct mo_plan {
+    int rz, ry, rx;
+    double r2;
+};
+
+// the largest o <= MO_MAXREACH + 1 with t(o) <= r2 on an axis of spacing sp: every axis alone rounds (sp * o)^2 once
+static int mo_reach(double sp, double r2) {
+    int o = 0;
+    while (o <= MO_MAXREACH && mo_t(0.0, 0.0, sp, 0, 0, o + 1, true) <= r2) ++o;
+    return o;
+}
+
+static bool mo_axis_ok(double sp, double radius, double r2, int* reach) {
+    if (!po_spacing_ok(sp) || !(floor(radius / sp) <= (double)MO_MAXREACH)) return false;
+    *reach = mo_reach(sp, r2);
+    return *reach <= MO_MAXREACH;
+}
+
+static bool mo_args_ok(int S, int H, int W, int K, double dz, double dy, double dx, double radius, int op, int per_slice, mo_plan* p) {
+    if (!po_problem_ok(S, H, W, K) || op < 0 || op > 2 || (per_slice != 0 && per_slice != 1) || !po_spacing_ok(radius)) return false;
+    p->r2 = radius * radius;
+    p->rz = 0;
+    if (!per_slice && !mo_axis_ok(dz, radius, p->r2, &p->rz)) return false;
+    return mo_axis_ok(dy, radius, p->r2, &p->ry) && mo_axis_ok(dx, radius, p->r2, &p->rx);
+}
+
+// one map of the sites' runs along x (skipped when the ball is one voxel wide), then one pass over the rows of the ball
+template <int PASS>
+static void mo_pass(const unsigned char* lab, const int* values, int k, const unsigned char* sites, const unsigned char* m,
+                    unsigned char* dst, int* stats, const signed char* table, unsigned char* run, int S, int H, int W, const mo_plan& p,
+                    int first, int before, hipStream_t st) {
+    constexpr bool EQ = PASS == MO_OPEN || PASS == MO_DILATE;          // the sites are the voxels of the set, not of its complement
+    constexpr bool MASK = PASS == MO_OPEN || PASS == MO_CLOSE;        // the sites are read from the mask, not from the label volume
+    const long n = (long)S * H * W;
+    const dim3 grid(po_grid(n, CC_MAXBLK)), block(PO_BLOCK);
+    if (p.rx > 0) {
+        hipLaunchKernelGGL(po_mo_run_kernel<EQ>, grid, block, 0, st, sites, values, MASK ? -1 : k, run, W, p.rx, n);
+        hipLaunchKernelGGL((po_mo_ball_kernel<PASS, true>), grid, block, 0, st, lab, values, k, (const unsigned char*)run, m, dst, stats,
+                           table, S, H, W, p.rz, p.ry, first, before);
+    } else {
+        hipLaunchKernelGGL((po_mo_ball_kernel<PASS, false>), grid, block, 0, st, lab, values, k, sites, m, dst, stats, table, S, H, W, p.rz,
+                           p.ry, first, before);
+    }
+}
+
+// dst = lab opened (closing == false) or closed by the ball, organ after organ on the stream; dst must not be lab
+static void mo_apply(bool closing, const unsigned char* lab, const int* values, unsigned char* dst, int* stats, const signed char* table,
+                     unsigned char* run, unsigned char* mask, int S, int H, int W, int K, const mo_plan& p, int before, hipStream_t st) {
+    for (int k = 0; k < K; ++k) {
+        if (closing) {
+            mo_pass<MO_DILATE>(lab, values, k, lab, nullptr, mask, stats, table, run, S, H, W, p, 0, 0, st);
+            mo_pass<MO_CLOSE>(lab, values, k, mask, mask, dst, stats, table, run, S, H, W, p, k == 0, before, st);
+        } else {
+            mo_pass<MO_ERODE>(lab, values, k, lab, nullptr, mask, stats, table, run, S, H, W, p, 0, 0, st);
+            mo_pass<MO_OPEN>(lab, values, k, mask, mask, dst, stats, table, run, S, H, W, p, k == 0, before, st);
+        }
+    }
+}
+
 // the workspace of po_surface_walk, in this order; n = S * H * W
 struct po_walk_ws {
     double *da, *db;               // two distance maps [n]
@@ -1421,6 +1632,40 @@ int mmseg_fill_label_holes(const unsigned char* label, const int* values, unsign
         hipLaunchKernelGGL(po_fh_flatten_kernel, grid, block, 0, st, comp, mark, S, H, W, per_slice);
         if (k == 0) hipLaunchKernelGGL(po_fh_fill_kernel<true>, few, block, 0, st, label, values, k, comp, mark, out, stats, n);
         else hipLaunchKernelGGL(po_fh_fill_kernel<false>, few, block, 0, st, label, values, k, comp, mark, out, stats, n);
+    }
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// bytes of workspace of mmseg_smooth_label: the row table of the ball, then three bytes per voxel (the runs along x, the mask of the
+// pass before, and the opened volume that `smooth` closes)
+long mmseg_smooth_label_workspace_bytes(int S, int H, int W, int K) {
+    if (S <= 0 || !po_problem_ok(S, H, W, K)) return 0;
+    return MO_TABLE_BYTES + 3 * (long)S * H * W;
+}
+
+// out [S,H,W] uint8 = label opened (op 0), closed (1) or opened and then closed (2) by the ball of `radius` mm on the grid of spacings
+// (dz, dy, dx), organ by organ; per_slice: the ball lies in the slice and dz is not read.  stats [K,3] int32 = (voxels of values[k] in
+// label, removed, added).  ws: mmseg_smooth_label_workspace_bytes(S, H, W, K) bytes.  Per organ and opening or closing two passes over the
+// rows of the ball, each after one map of runs along x unless the ball is one voxel wide there; all on the stream.
+int mmseg_smooth_label(const unsigned char* label, const int* values, unsigned char* out, int* stats, void* ws, int S, int H, int W, int K,
+                       double dz, double dy, double dx, double radius, int op, int per_slice, void* stream) {
+    if (S <= 0) return 0;
+    mo_plan p;
+    if (!label || !values || !out || !stats || !ws || label == out || !mo_args_ok(S, H, W, K, dz, dy, dx, radius, op, per_slice, &p))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const long n = (long)S * H * W;
+    signed char* table = reinterpret_cast<signed char*>(ws);
+    unsigned char* run = reinterpret_cast<unsigned char*>(ws) + MO_TABLE_BYTES;
+    unsigned char *mask = run + n, *opened = mask + n;
+    hipError_t rc = hipMemsetAsync(stats, 0, sizeof(int) * 3 * (size_t)K, st);
+    if (rc != hipSuccess) return (int)rc;
+    hipLaunchKernelGGL(po_mo_table_kernel, dim3(1), dim3(PO_BLOCK), 0, st, table, dz, dy, dx, p.r2, p.rz, p.ry, p.rx, per_slice);
+    if (op == 2) {
+        mo_apply(false, label, values, opened, stats, table, run, mask, S, H, W, K, p, 1, st);
+        mo_apply(true, opened, values, out, stats, table, run, mask, S, H, W, K, p, 0, st);
+    } else {
+        mo_apply(op == 1, label, values, out, stats, table, run, mask, S, H, W, K, p, 1, st);
     }
     return MMSEG_CHECK_LAUNCH();
 }

@@ -6,6 +6,7 @@
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
+                         [--predict_smooth open|close|smooth] [--predict_smooth_radius MM] [--predict_smooth_extent 2d|3d]
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
                          [--predict_tiles true|false] [--predict_tile_overlap PIXELS] [--predict_tta LIST]
 
@@ -66,6 +67,13 @@ def parse_arguments(argv=None):
     ap.add_argument('--predict_fill_holes', choices=['none', '2d', '3d'], default='none',
                     help='fill the zeros that an organ encloses, after --predict_components: slice by slice / in the volume '
                          '(results_holes_<modality>.csv)')
+    ap.add_argument('--predict_smooth', choices=['open', 'close', 'smooth'], default=None,
+                    help='open, close or open and then close every organ by a ball of --predict_smooth_radius mm, before '
+                         '--predict_components and --predict_fill_holes (results_smooth_<modality>.csv)')
+    ap.add_argument('--predict_smooth_radius', type=float, default=None, metavar='MM',
+                    help='radius of the ball of --predict_smooth in mm, finite and above 0; there is no default')
+    ap.add_argument('--predict_smooth_extent', choices=['2d', '3d'], default='2d',
+                    help='the ball of --predict_smooth lies in the slice / reaches across slices (needs slice_spacing in the files)')
     ap.add_argument('--predict_robust', type=true_or_false, default=False, metavar='true|false',
                     help='also score them by HD (a percentile of the surface distances) and NSD (surface Dice at a tolerance): '
                          'results_robust_<modality>.csv')
@@ -88,6 +96,10 @@ def parse_arguments(argv=None):
         ap.error('--predict_percentile must lie in [0, 100], got %r' % args.predict_percentile)
     if not 0.0 <= args.predict_tolerance < float('inf'):
         ap.error('--predict_tolerance must be a finite number of mm >= 0, got %r' % args.predict_tolerance)
+    if args.predict_smooth is not None and args.predict_smooth_radius is None:
+        ap.error('--predict_smooth %s needs --predict_smooth_radius MM: there is no default radius' % args.predict_smooth)
+    if args.predict_smooth_radius is not None and not 0.0 < args.predict_smooth_radius < float('inf'):
+        ap.error('--predict_smooth_radius must be a finite number of mm > 0, got %r' % args.predict_smooth_radius)
     return args
 
 
@@ -248,7 +260,10 @@ class Experiment(object):
                                               fill_holes={'2d': '2d', '3d': '3d'}.get(getattr(args, 'predict_fill_holes', 'none')),
                                               tiles=bool(getattr(args, 'predict_tiles', False)),
                                               tile_overlap=getattr(args, 'predict_tile_overlap', None),
-                                              tta=getattr(args, 'predict_tta', None))
+                                              tta=getattr(args, 'predict_tta', None),
+                                              smooth=getattr(args, 'predict_smooth', None),
+                                              smooth_radius=getattr(args, 'predict_smooth_radius', None),
+                                              smooth_extent=getattr(args, 'predict_smooth_extent', '2d'))
             self.log.info('Predicted label volumes of %s written to %s' % (args.predict_folder, out))
         dp.host_barrier()
 

@@ -5,6 +5,8 @@ arithmetic operation on activations, gradients and weights is a kernel of csrc/*
 _native.call (C ABI, include/mmseg_hip.h).  Layout: NHWC fp32 (the reference's layout), weights in Keras
 layout (conv HWIO, dense [in, out]).
 """
+import math
+
 import torch
 
 from . import _native as N
@@ -1893,6 +1895,56 @@ def merge_views(prob, back, N_, K):
     if n:
         N.call('mmseg_merge_views', _c(prob), _c(b.to(prob.device)), out, V, n, OH, OW, C, K)
     return out
+
+
+SMOOTH_OPS = ('open', 'close', 'smooth')
+SMOOTH_EXTENTS = ('2d', '3d')
+SMOOTH_MAX_REACH = 32
+
+
+def smooth_reach(spacing, radius, extent='2d'):
+    """the reach of the ball in voxels per axis in use, floor(radius / spacing): (rows, columns) with extent '2d', (slices, rows,
+    columns) with '3d'; spacing = (mm between slices, rows, columns)"""
+    return tuple(int(math.floor(min(radius / s, 2.0 ** 31))) for s in (spacing[1:] if extent == '2d' else spacing))
+
+
+def smooth_label(label, values, spacing, radius, op='smooth', extent='2d'):
+    """label [S,H,W] uint8 on the device, values [K] int32, spacing (mm between slices, rows, columns), radius in mm -> (uint8 [S,H,W],
+    int32 [K,3]): every organ opened ('open'), closed ('close') or opened and then closed ('smooth') by the ball of that radius on the
+    volume's grid, and per organ (voxels before, removed, added) (csrc/postprocess.hip; the rule is in INTEGRATION.md section 5).  The
+    ball holds the offsets o with (dx ox)^2 + (dy oy)^2 + (dz oz)^2 <= radius^2; with extent '2d' it lies in the slice and the first
+    spacing is not read (it may be None).  Erosion does not see beyond the volume: open(X) = dilate(erode(X)) is a subset of X,
+    close(X) = erode(dilate(X)) a superset.  'open' zeroes the voxels of values[k] outside the opened organ; 'close' gives the input's
+    zeros inside the closed organ to it, the lowest k first, and overwrites nothing else.  At most 32 voxels of reach per axis."""
+    name = 'smooth_label'
+    if op not in SMOOTH_OPS:
+        raise ValueError("%s: op must be one of %s, got %r" % (name, ', '.join(SMOOTH_OPS), op))
+    if extent not in SMOOTH_EXTENTS:
+        raise ValueError("%s: extent must be '2d' (the ball lies in the slice) or '3d', got %r" % (name, extent))
+    K = _volume_args(name, label, values)
+    try:
+        sp = [0.0 if (extent == '2d' and i == 0) else float(v) for i, v in enumerate(spacing)]
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError('%s: spacing must be three numbers and radius one, got %r and %r' % (name, spacing, radius))
+    used = sp[1:] if extent == '2d' else sp
+    if len(sp) != 3 or any(not (v > 0 and v < float('inf')) for v in used):
+        raise ValueError('%s: spacing must be three finite positive numbers (mm between slices, rows, columns; the first is not read '
+                         "with extent '2d'), got %r" % (name, spacing))
+    if not (r > 0 and r < float('inf')):
+        raise ValueError('%s: radius must be a finite number of mm > 0, got %r' % (name, radius))
+    reach = smooth_reach(sp, r, extent)
+    if max(reach) > SMOOTH_MAX_REACH:
+        raise ValueError('%s: a radius of %r mm at spacing %r reaches %s voxels per axis, at most %d'
+                         % (name, radius, tuple(spacing), reach, SMOOTH_MAX_REACH))
+    S, H, W = label.shape
+    out = _new((S, H, W), label, torch.uint8)
+    stats = torch.zeros((K, 3), dtype=torch.int32, device=label.device)
+    if S:
+        ws = _ws('smooth_label', (N.call('mmseg_smooth_label_workspace_bytes', S, H, W, K) + 3) // 4, label.device)
+        N.call('mmseg_smooth_label', _c(label), values, out, stats, ws, S, H, W, K, sp[0], sp[1], sp[2], r, SMOOTH_OPS.index(op),
+               int(extent == '2d'))
+    return out, stats
 
 
 def _sum_n(gs, like):

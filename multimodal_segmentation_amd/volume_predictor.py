@@ -21,6 +21,8 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
                                            before the filter and the voxels kept, one row per volume
     <out>/results_holes_<modality>.csv     with fill_holes='2d' or '3d': per organ the number of enclosed holes, its voxels before
                                            the filling and the voxels added, one row per volume
+    <out>/results_smooth_<modality>.csv    with smooth='open', 'close' or 'smooth': per organ its voxels before, the voxels removed
+                                           and the voxels added, one row per volume
 
 components='largest' (build-defined, off by default; the rule is in INTEGRATION.md section 5) keeps, per organ, the largest 3-D connected
 component: the prediction is scattered to the file grid [S_file,H,W] on the device and filtered there (ops.keep_largest_components),
@@ -29,6 +31,14 @@ so that neighbours across slices are those of the file; the filtered volume is w
 fill_holes='2d' | '3d' (build-defined, off by default; the rule is in INTEGRATION.md section 5) then sets the zeros that an organ
 encloses to that organ's grey value (ops.fill_label_holes, on the file grid as well): slice by slice with '2d', in the volume with
 '3d'.  It runs after the component filter, so that an island which the filter turned into zeros inside an organ is closed again.
+
+smooth='open' | 'close' | 'smooth' with smooth_radius in mm (build-defined, off by default, no default radius; the rule is in
+INTEGRATION.md section 5) opens, closes or opens and then closes every organ by a ball of that radius (ops.smooth_label, on the file
+grid as well, with the file's own spacings: `resolution` in the slice and, with smooth_extent='3d', `slice_spacing` across slices;
+'2d', the default, keeps the ball in the slice).  Unselected slices of the file are zero there and count as background with '3d'.
+It runs FIRST, before the component filter and the hole filling: restore_label, smoothing, filter, filling, then scores and file.  An
+opening cuts a neck narrower than the ball before the filter looks, so that the filter drops the blob behind it; a fragment that a
+closing joins to its organ survives the filter.  What is scored is what is written.
 
 tiles=True (build-defined, off by default; the rule is in INTEGRATION.md section 5) predicts the whole resampled frame instead of its
 centre input_shape window: per volume and predicted modality the frame is cut into overlapping tiles (loaders/volume_folder.tile_axis,
@@ -185,6 +195,51 @@ def fill_holes(pred, values, geometry, mode):
     return filled.index_select(0, where), stats
 
 
+SMOOTH_OPS = (None,) + ops.SMOOTH_OPS
+
+
+def check_smooth(smooth, radius, extent='2d'):
+    """smooth: None or one of ops.SMOOTH_OPS, radius: mm, finite and > 0 (there is no default), extent: '2d' or '3d' -> the radius as a
+    float, None without smooth"""
+    if smooth not in SMOOTH_OPS:
+        raise ValueError("smooth (--predict_smooth) must be None, 'open', 'close' or 'smooth', got %r" % (smooth,))
+    if extent not in ops.SMOOTH_EXTENTS:
+        raise ValueError("smooth_extent (--predict_smooth_extent) must be '2d' or '3d', got %r" % (extent,))
+    if smooth is None:
+        return None
+    if radius is None:
+        raise ValueError('smooth=%r needs smooth_radius (--predict_smooth_radius), the radius of the ball in mm: there is no default'
+                         % (smooth,))
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        r = float('nan')
+    if isinstance(radius, bool) or not (r > 0 and r < float('inf')):
+        raise ValueError('smooth_radius (--predict_smooth_radius) must be a finite number of mm > 0, got %r' % (radius,))
+    return r
+
+
+def smooth(pred, values, geometry, op, radius, extent='2d'):
+    """pred: uint8 [S,H,W] on the device, the selected slices of one file in order -> (the same slices with every organ opened, closed
+    or smoothed by the ball of `radius` mm, stats [K,3] = (before, removed, added) on the device).  Like keep_largest on the file grid
+    [S_file,H,W] with the file's spacings: geometry['resolution'] in the slice and, with extent '3d', geometry['slice_spacing'] across
+    slices.  Unselected slices are zero: with '3d' they are background to an erosion and empty to a dilation; '2d' never looks at
+    them."""
+    r = check_smooth(op, radius, extent)
+    dz = geometry.get('slice_spacing')
+    if extent == '3d' and dz is None:
+        raise ValueError("%s holds no 'slice_spacing': smooth_extent='3d' (--predict_smooth_extent 3d) needs the mm between slices"
+                         % (geometry.get('file'),))
+    spacing = (None if dz is None else float(dz), float(geometry['resolution'][0]), float(geometry['resolution'][1]))
+    in_use = spacing[1:] if extent == '2d' else spacing
+    if all(s > 0 and s < float('inf') for s in in_use) and max(ops.smooth_reach(spacing, r, extent)) > ops.SMOOTH_MAX_REACH:
+        raise ValueError('%s: smooth_radius=%r mm (--predict_smooth_radius) reaches %s voxels at spacing %r, at most %d per axis'
+                         % (geometry.get('file'), r, ops.smooth_reach(spacing, r, extent), in_use, ops.SMOOTH_MAX_REACH))
+    on_grid, where = _on_file_grid(pred, geometry)
+    done, stats = ops.smooth_label(on_grid, values, spacing, r, op, extent)
+    return done.index_select(0, where), stats
+
+
 def check_tile_overlap(tile_overlap, input_shape):
     """tile_overlap: None (half the input extent per axis), one number of pixels for both axes or (rows, columns) -> (rows, columns);
     0 <= overlap < the input extent of its axis"""
@@ -300,7 +355,7 @@ def views_in(images, views):
     return [ops.augment_gather(ops._c(x), rows, mats, None, 1, 'nearest') for x in images]
 
 
-_fill_holes = fill_holes          # for score_folder and VolumePredictor.run, whose keyword carries the function's name
+_fill_holes, _smooth = fill_holes, smooth          # for score_folder and VolumePredictor.run, whose keywords carry the functions' names
 
 
 def _write_table(path, rows, names, num_masks, fmt, union_first):
@@ -325,6 +380,11 @@ def write_hole_results(path, rows, num_masks):
     _write_table(path, rows, ('N', 'Before', 'Added'), num_masks, '%d', False)
 
 
+def write_smooth_results(path, rows, num_masks):
+    """rows: (volume, stats [K,3]) -> Vol, Before0, Removed0, Added0, Before1, ..."""
+    _write_table(path, rows, ('Before', 'Removed', 'Added'), num_masks, '%d', False)
+
+
 def write_surface_results(path, rows, num_masks):
     """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
     _write_table(path, rows, ('RAVD', 'ASSD', 'MSSD'), num_masks, '%.3f', True)
@@ -338,7 +398,7 @@ def write_robust_results(path, rows, num_masks):
 class ScoreSheet(object):
     """the rows of one run's results_<kind>_<modality>.csv files: rows[kind][m] holds those of modality m; `scores` is score_volume's"""
     WRITERS = (('native', write_results), ('surface', write_surface_results), ('robust', write_robust_results),
-               ('components', write_component_results), ('holes', write_hole_results))
+               ('components', write_component_results), ('holes', write_hole_results), ('smooth', write_smooth_results))
 
     def __init__(self, modalities, num_masks, in_mm):
         self.modalities, self.num_masks, self.in_mm = list(modalities), num_masks, in_mm
@@ -363,6 +423,9 @@ class ScoreSheet(object):
     def add_holes(self, m, volume, stats):
         self.rows['holes'][m].append((volume, nn.to_numpy(stats)))
 
+    def add_smooth(self, m, volume, stats):
+        self.rows['smooth'][m].append((volume, nn.to_numpy(stats)))
+
     def write(self, out_folder):
         """one file per kind and modality that has rows"""
         for kind, writer in self.WRITERS:
@@ -375,15 +438,17 @@ class ScoreSheet(object):
 
 
 def score_folder(pred_folder, data_folder, out_folder=None, surface=True, components=None, connectivity=6, robust=None,
-                 fill_holes=None):
+                 fill_holes=None, smooth=None, smooth_radius=None, smooth_extent='2d'):
     """Score label volumes written earlier (by VolumePredictor.run or by another program: <file name of the input>.npz with `label`
     [S_file,H,W] uint8) against the labelled files of `data_folder`; writes the CSV files of VolumePredictor.run into out_folder
     (default: pred_folder).  Volumes in the order of pred_folder/predictions.json where there is one, else of dataset.json.
     components='largest' filters every volume first (keep_largest), fill_holes='2d' | '3d' then fills the enclosed holes of every
-    organ (fill_holes): the scores that post-processing would give.
+    organ (fill_holes): the scores that post-processing would give.  smooth='open' | 'close' | 'smooth' with smooth_radius in mm (and
+    smooth_extent) comes before both, as in VolumePredictor.run.
     robust=(percentile, tolerance in mm) also writes results_robust_<modality>.csv, and a third dictionary with its rows is returned."""
     check_components(components, connectivity)
     check_fill_holes(fill_holes)
+    smooth_radius = check_smooth(smooth, smooth_radius, smooth_extent)
     robust = check_robust(robust)
     loader = VolumeFolderLoader(data_folder)
     out_folder = out_folder or pred_folder
@@ -414,6 +479,8 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
             selected = np.arange(label.shape[0]) if selected is None else selected
             geo = dict(file=entry['file'], raw_shape=label.shape, slices=[int(i) for i in selected], resolution=res, slice_spacing=spacing)
             pred = nn.host_to_device(np.ascontiguousarray(pred[selected]), device, np.uint8)
+            if smooth:
+                pred, _ = _smooth(pred, values, geo, smooth, smooth_radius, smooth_extent)
             if components:
                 pred, _ = keep_largest(pred, values, geo, connectivity)
             if fill_holes:
@@ -462,9 +529,10 @@ class VolumePredictor(object):
                                loader.num_masks)
 
     def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
-            fill_holes=None, tiles=False, tile_overlap=None, tta=None):
+            fill_holes=None, tiles=False, tile_overlap=None, tta=None, smooth=None, smooth_radius=None, smooth_extent='2d'):
         check_components(components, connectivity)
         check_fill_holes(fill_holes)
+        smooth_radius = check_smooth(smooth, smooth_radius, smooth_extent)
         robust = check_robust(robust)
         if mode not in FUSION_MODES:
             raise ValueError('Unknown mode: %r (expected one of %s)' % (mode, ', '.join(FUSION_MODES)))
@@ -509,6 +577,9 @@ class VolumePredictor(object):
                         images, _ = loader.load_volume_for_prediction(v)
                     prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
                     pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
+                if smooth:
+                    pred, stats = _smooth(pred, values, geo, smooth, smooth_radius, smooth_extent)
+                    sheet.add_smooth(m, v, stats)
                 if components:
                     pred, stats = keep_largest(pred, values, geo, connectivity)
                     sheet.add_components(m, v, stats)
@@ -532,6 +603,8 @@ class VolumePredictor(object):
             settings.update(components=components, connectivity=connectivity)
         if fill_holes:
             settings.update(fill_holes=fill_holes)
+        if smooth:
+            settings.update(smooth=smooth, smooth_radius=smooth_radius, smooth_extent=smooth_extent)
         if robust is not None:
             settings.update(percentile=robust[0], tolerance_mm=robust[1])
         if tiles:
