@@ -323,6 +323,29 @@ long mmseg_augment_workspace_floats(int B, int H, int W, int C);
 int mmseg_augment_gather(const float* data, const int* rows, const double* mat, const float* shift, float* out, float* ws, int N,
                          int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream);
 
+/* ---- elastic deformation of training batches (csrc/augment.hip; build-defined: Simard 2003 / albumentations' ElasticTransform) ----
+ * A random smooth displacement field that depends on (seed, batch, sample, pixel) only:
+ *   noise  P = Philox4x32-10(counter (r*W + c, b, 0, 0), key (seed, batch)), multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments
+ *          0x9E3779B9 / 0xBB67AE85;  u_a = (P[a] >> 8) * 2^-23 - 1, a = 0 (row), 1 (column): exact in fp32, in [-1, 1 - 2^-23]
+ *   blur   g_a = scipy.ndimage.gaussian_filter(u_a[b], sigma, mode='reflect', truncate=4.0): separable, radius R = int(4 sigma + 0.5),
+ *          half-sample symmetric reflection of period 2n (right when R exceeds the extent); both passes multiply and add in fp64
+ *   field  disp[b][r][c][a] = (float)(scale[b] * g_a); a sample with scale[b] == 0 gets +0.0 everywhere and is not blurred
+ * scale [B] fp64 and weights [R+1] fp64 (w_0 .. w_R of the normalised kernel, w_-k = w_k) on the device, disp [B,H,W,2] fp32, ws:
+ * mmseg_elastic_workspace_doubles(B, H, W) doubles, 16-byte aligned (the query launches nothing and returns 0 for a refused shape).  seed and batch are read
+ * as 32-bit patterns.  1 <= R <= 128, B, H <= 65535, H*W < 2^30; anything else or a null pointer is refused (hipErrorInvalidValue, nothing
+ * is launched); B == 0 does nothing.  Two launches in a fixed summation order: two runs are bitwise equal.  No host synchronisation,
+ * allocation or copy. */
+long mmseg_elastic_workspace_doubles(int B, int H, int W);
+int mmseg_elastic_field(const double* scale, const double* weights, float* disp, double* ws, int seed, int batch, int B, int H, int W,
+                        int R, void* stream);
+/* mmseg_augment_gather with the field added to the output pixel before the matrix, in fp64:
+ *   sr = m0*(r + disp_r) + m1*(c + disp_c) + m2,  sc = m3*(r + disp_r) + m4*(c + disp_c) + m5
+ * i.e. z(p) = x(M (p + d(p))): an elastic warp of the affinely transformed sample with one interpolation and the boundary rule applied
+ * once.  Everything after the coordinates (fill modes, orders, zero-weight taps, NaN rows, channel shift) is mmseg_augment_gather's;
+ * an all-zero field gives its bits.  disp [B,H,W,2] fp32, not NULL. */
+int mmseg_elastic_gather(const float* data, const int* rows, const double* mat, const float* disp, const float* shift, float* out,
+                         float* ws, int N, int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream);
+
 /* ---- losses (csrc/loss.hip): costs.py:43-85,129-136, keras mae/mse, costs.ypred ---------------------------- */
 int mmseg_segloss_workspace_floats(int B);
 int mmseg_segloss_stats_floats(int B);

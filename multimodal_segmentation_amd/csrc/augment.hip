@@ -124,9 +124,12 @@ __device__ __forceinline__ void aug_minmax_block(float lo, float hi, float* part
 
 // grid (nblk, B), block AUG_MAXBLK; nblk <= AUG_MAXBLK blocks stride over the sample's per = H*W*C elements (NHWC order,
 // channel fastest: coalesced stores; neighbouring pixels' taps share cache lines)
+// FIELD: disp [B,H,W,2] fp32 (row, column) is added to the output pixel before the matrix (mmseg_elastic_gather); without it disp is
+// not read and the kernel is the plain affine gather
+template <bool FIELD>
 __global__ void __launch_bounds__(AUG_MAXBLK) augment_gather_kernel(
         const float* __restrict__ data, const int* __restrict__ rows, const double* __restrict__ mat, float* __restrict__ out,
-        float* __restrict__ part, int N, int H, int W, int C, int per, int order, int mode, float cval) {
+        float* __restrict__ part, int N, int H, int W, int C, int per, int order, int mode, float cval, const float* __restrict__ disp) {
     const int b = blockIdx.y;
     const int j = rows ? rows[b] : b;
     const double* m = mat + (size_t)b * 6;
@@ -140,8 +143,16 @@ __global__ void __launch_bounds__(AUG_MAXBLK) augment_gather_kernel(
         const int p = e / C;
         const int r = p / W, c = p - r * W;
         bool inside = row_ok;
-        const double sr = aug_map(m0 * r + m1 * c + m2, H, mode, inside);
-        const double sc = aug_map(m3 * r + m4 * c + m5, W, mode, inside);
+        double sr, sc;
+        if constexpr (FIELD) {
+            const float* d = disp + ((size_t)b * H * W + p) * 2;
+            const double pr = r + (double)d[0], pc = c + (double)d[1];
+            sr = aug_map(m0 * pr + m1 * pc + m2, H, mode, inside);
+            sc = aug_map(m3 * pr + m4 * pc + m5, W, mode, inside);
+        } else {
+            sr = aug_map(m0 * r + m1 * c + m2, H, mode, inside);
+            sc = aug_map(m3 * r + m4 * c + m5, W, mode, inside);
+        }
         float v = row_ok ? cval : __builtin_nanf("");
         if (inside) {
             const float* s = src + ch;
@@ -200,6 +211,30 @@ static int aug_blocks(long per) {
     return (int)(n < AUG_MAXBLK ? n : AUG_MAXBLK);
 }
 
+// the launches shared by mmseg_augment_gather (disp == nullptr) and mmseg_elastic_gather
+static int augment_launch(const float* data, const int* rows, const double* mat, const float* disp, const float* shift, float* out,
+                          float* ws, int N, int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream) {
+    if (B <= 0) return 0;
+    if (N < 1 || H < 1 || W < 1 || C < 1 || B > 65535 || order < 0 || order > 1 || fill_mode < AUG_NEAREST || fill_mode > AUG_WRAP ||
+        (shift && !ws))
+        return (int)hipErrorInvalidValue;
+    const long per = (long)H * W * C;
+    if (per > 0x7fffffffL - (long)AUG_MAXBLK * AUG_MAXBLK) return (int)hipErrorInvalidValue;      // 32-bit element indices
+    const dim3 grid((unsigned)aug_blocks(per), B);
+    if (disp)
+        hipLaunchKernelGGL(augment_gather_kernel<true>, grid, dim3(AUG_MAXBLK), 0, (hipStream_t)stream, data, rows, mat, out,
+                           shift ? ws : nullptr, N, H, W, C, (int)per, order, fill_mode, cval, disp);
+    else
+        hipLaunchKernelGGL(augment_gather_kernel<false>, grid, dim3(AUG_MAXBLK), 0, (hipStream_t)stream, data, rows, mat, out,
+                           shift ? ws : nullptr, N, H, W, C, (int)per, order, fill_mode, cval, (const float*)nullptr);
+    if (shift) {
+        const int rc = MMSEG_CHECK_LAUNCH();
+        if (rc) return rc;
+        hipLaunchKernelGGL(augment_shift_kernel, grid, dim3(AUG_MAXBLK), 0, (hipStream_t)stream, out, shift, ws, C, (int)per);
+    }
+    return MMSEG_CHECK_LAUNCH();
+}
+
 extern "C" {
 
 long mmseg_augment_workspace_floats(int B, int H, int W, int C) {
@@ -212,20 +247,175 @@ long mmseg_augment_workspace_floats(int B, int H, int W, int C) {
 // without shift).  fill_mode: 0 nearest, 1 constant (cval), 2 reflect, 3 wrap.
 int mmseg_augment_gather(const float* data, const int* rows, const double* mat, const float* shift, float* out, float* ws, int N, int B,
                          int H, int W, int C, int order, int fill_mode, float cval, void* stream) {
-    if (B <= 0) return 0;
-    if (N < 1 || H < 1 || W < 1 || C < 1 || B > 65535 || order < 0 || order > 1 || fill_mode < AUG_NEAREST || fill_mode > AUG_WRAP ||
-        (shift && !ws))
-        return (int)hipErrorInvalidValue;
-    const long per = (long)H * W * C;
-    if (per > 0x7fffffffL - (long)AUG_MAXBLK * AUG_MAXBLK) return (int)hipErrorInvalidValue;      // 32-bit element indices
-    const dim3 grid((unsigned)aug_blocks(per), B);
-    hipLaunchKernelGGL(augment_gather_kernel, grid, dim3(AUG_MAXBLK), 0, (hipStream_t)stream, data, rows, mat, out,
-                       shift ? ws : nullptr, N, H, W, C, (int)per, order, fill_mode, cval);
-    if (shift) {
-        const int rc = MMSEG_CHECK_LAUNCH();
-        if (rc) return rc;
-        hipLaunchKernelGGL(augment_shift_kernel, grid, dim3(AUG_MAXBLK), 0, (hipStream_t)stream, out, shift, ws, C, (int)per);
+    return augment_launch(data, rows, mat, nullptr, shift, out, ws, N, B, H, W, C, order, fill_mode, cval, stream);
+}
+
+// mmseg_augment_gather with a displacement field disp [B,H,W,2] fp32 (row, column) added to the output pixel before the matrix:
+//     sr = m0*(r + disp_r) + m1*(c + disp_c) + m2,   sc = m3*(r + disp_r) + m4*(c + disp_c) + m5      (fp64)
+// i.e. z(p) = x(M (p + d(p))), an elastic warp of the affinely transformed sample with ONE interpolation; everything after the
+// coordinates is the code of mmseg_augment_gather.  A zero field gives its bits.
+int mmseg_elastic_gather(const float* data, const int* rows, const double* mat, const float* disp, const float* shift, float* out,
+                         float* ws, int N, int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream) {
+    if (B > 0 && !disp) return (int)hipErrorInvalidValue;
+    return augment_launch(data, rows, mat, disp, shift, out, ws, N, B, H, W, C, order, fill_mode, cval, stream);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Elastic deformation (Simard 2003; albumentations' ElasticTransform): a random smooth displacement field, a function of
+// (seed, batch number, sample, pixel) only.
+//   noise   P = Philox4x32-10(counter (r*W + c, b, 0, 0), key (seed, batch));  u_a = (P[a] >> 8) * 2^-23 - 1 in [-1, 1 - 2^-23],
+//           exact in fp32, a = 0 (row) / 1 (column)
+//   blur    g_a = scipy.ndimage.gaussian_filter(u_a[b], sigma, mode='reflect', truncate=4): separable, radius R, the host's R+1
+//           fp64 weights w_0 .. w_R (w_-k = w_k), half-sample symmetric reflection of period 2n (right for R > n too)
+//   field   disp[b,r,c,a] = fp32(scale[b] * g_a), scale [B] fp64; scale[b] == 0 -> +0.0 and no blur for that sample
+// Two launches, both accumulating in fp64 in a fixed order (bitwise reproducible):
+//   elastic_blur_cols_kernel  grid (ceil(W / EL_TW), H, B), block EL_TW: the noise of columns c0-R .. c0+EL_TW-1+R of one row is drawn
+//                             once into LDS (Philox per staged pixel, not per tap), blurred along the row -> ws [B,H,W,2] fp64
+//   elastic_blur_rows_kernel  grid (ceil(W / EL_TC), ceil(H / EL_TH), B), block EL_TC x EL_TH/2: rows r0-R .. r0+EL_TH-1+R of EL_TC
+//                             columns of ws in LDS ((EL_TH + 2R) * EL_TC * 16 bytes: 40 KiB at R = 128), two output rows per thread
+#define EL_MAXR 128
+#define EL_TW 128
+#define EL_TH 64
+#define EL_TC 8
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t& o0, uint32_t& o1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
     }
+    o0 = c0;
+    o1 = c1;
+}
+
+// half-sample symmetric reflection, period 2n
+__device__ __forceinline__ int el_reflect(int i, int n) {
+    const int p = 2 * n;
+    int t = i % p;
+    if (t < 0) t += p;
+    return t >= n ? p - 1 - t : t;
+}
+
+__global__ void __launch_bounds__(EL_TW) elastic_blur_cols_kernel(const double* __restrict__ scale, const double* __restrict__ wts,
+                                                                  double* __restrict__ ws, uint32_t seed, uint32_t batch, int H, int W,
+                                                                  int R) {
+    __shared__ float nz[2][EL_TW + 2 * EL_MAXR];                    // fp32 holds the noise exactly; fp64 here was slower (LDS-bound)
+    __shared__ double wk[EL_MAXR + 1];
+    const int b = blockIdx.z, r = blockIdx.y, c0 = blockIdx.x * EL_TW;
+    if (scale[b] == 0.0) return;                                   // uniform over the block
+    for (int i = threadIdx.x; i <= R; i += EL_TW) wk[i] = wts[i];
+    for (int i = threadIdx.x; i < EL_TW + 2 * R; i += EL_TW) {
+        const int cc = el_reflect(c0 - R + i, W);
+        uint32_t p0, p1;
+        philox4x32_10((uint32_t)r * (uint32_t)W + (uint32_t)cc, (uint32_t)b, 0u, 0u, seed, batch, p0, p1);
+        nz[0][i] = (float)(p0 >> 8) * 0x1p-23f - 1.f;
+        nz[1][i] = (float)(p1 >> 8) * 0x1p-23f - 1.f;
+    }
+    __syncthreads();
+    const int c = c0 + threadIdx.x;
+    if (c >= W) return;
+    const int t = threadIdx.x + R;
+    double a0 = wk[0] * (double)nz[0][t], a1 = wk[0] * (double)nz[1][t];
+    for (int k = 1; k <= R; ++k) {
+        const double w = wk[k];
+        a0 += w * ((double)nz[0][t - k] + (double)nz[0][t + k]);
+        a1 += w * ((double)nz[1][t - k] + (double)nz[1][t + k]);
+    }
+    double* o = ws + (((size_t)b * H + r) * W + c) * 2;
+    o[0] = a0;
+    o[1] = a1;
+}
+
+__global__ void __launch_bounds__(EL_TC * EL_TH / 2) elastic_blur_rows_kernel(const double* __restrict__ scale,
+                                                                              const double* __restrict__ wts,
+                                                                              const double* __restrict__ ws, float* __restrict__ disp,
+                                                                              int H, int W, int R) {
+    extern __shared__ double2 el_lds[];                            // [(EL_TH + 2R)][EL_TC] (row, column) pairs, 16-byte reads; then R + 1 weights
+    const int b = blockIdx.z, r0 = blockIdx.y * EL_TH, c0 = blockIdx.x * EL_TC;
+    const int tc = threadIdx.x % EL_TC, tr = threadIdx.x / EL_TC;
+    const int nrow = EL_TH + 2 * R;
+    double* wk = reinterpret_cast<double*>(el_lds + (size_t)nrow * EL_TC);
+    const double s = scale[b];
+    const int c = c0 + tc;
+    if (s == 0.0) {                                                // uniform over the block
+        if (c < W)
+            for (int q = 0; q < 2; ++q) {
+                const int r = r0 + tr + q * (EL_TH / 2);
+                if (r < H) {
+                    float* o = disp + (((size_t)b * H + r) * W + c) * 2;
+                    o[0] = 0.f;
+                    o[1] = 0.f;
+                }
+            }
+        return;
+    }
+    for (int i = threadIdx.x; i <= R; i += blockDim.x) wk[i] = wts[i];
+    for (int i = tr; i < nrow; i += EL_TH / 2) {
+        double2 v = make_double2(0.0, 0.0);
+        if (c < W) v = reinterpret_cast<const double2*>(ws)[((size_t)b * H + el_reflect(r0 - R + i, H)) * W + c];
+        el_lds[i * EL_TC + tc] = v;
+    }
+    __syncthreads();
+    if (c >= W) return;
+    const double2* lo = el_lds + (size_t)(tr + R) * EL_TC + tc;              // output row r0 + tr
+    const double2* hi = lo + (size_t)(EL_TH / 2) * EL_TC;                    // output row r0 + tr + EL_TH / 2
+    double a0 = wk[0] * lo->x, a1 = wk[0] * lo->y, b0 = wk[0] * hi->x, b1 = wk[0] * hi->y;
+    for (int k = 1; k <= R; ++k) {
+        const double w = wk[k];
+        const int d = k * EL_TC;
+        const double2 lm = lo[-d], lp = lo[d], hm = hi[-d], hp = hi[d];
+        a0 += w * (lm.x + lp.x);
+        a1 += w * (lm.y + lp.y);
+        b0 += w * (hm.x + hp.x);
+        b1 += w * (hm.y + hp.y);
+    }
+    const int r = r0 + tr;
+    if (r < H) {
+        float* o = disp + (((size_t)b * H + r) * W + c) * 2;
+        o[0] = (float)(s * a0);
+        o[1] = (float)(s * a1);
+    }
+    if (r + EL_TH / 2 < H) {
+        float* o = disp + (((size_t)b * H + r + EL_TH / 2) * W + c) * 2;
+        o[0] = (float)(s * b0);
+        o[1] = (float)(s * b1);
+    }
+}
+
+static bool elastic_shape_ok(int B, int H, int W) {
+    return B >= 1 && H >= 1 && W >= 1 && B <= 65535 && H <= 65535 && (long)H * W <= 0x3fffffffL;
+}
+
+extern "C" {
+
+// doubles of the scratch buffer between the two passes; 0 for a shape mmseg_elastic_field refuses.  Launches nothing.
+long mmseg_elastic_workspace_doubles(int B, int H, int W) {
+    return elastic_shape_ok(B, H, W) ? 2L * B * H * W : 0;
+}
+
+// scale [B] fp64, weights [R+1] fp64 (w_0 .. w_R of the normalised kernel), disp [B,H,W,2] fp32, ws:
+// mmseg_elastic_workspace_doubles(B, H, W) doubles, 16-byte aligned; seed and batch are read as 32-bit patterns
+int mmseg_elastic_field(const double* scale, const double* weights, float* disp, double* ws, int seed, int batch, int B, int H, int W,
+                        int R, void* stream) {
+    if (R < 1 || R > EL_MAXR) return (int)hipErrorInvalidValue;
+    if (B <= 0) return 0;
+    if (!elastic_shape_ok(B, H, W) || !scale || !weights || !disp || !ws || ((uintptr_t)ws & 15)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(elastic_blur_cols_kernel, dim3((W + EL_TW - 1) / EL_TW, H, B), dim3(EL_TW), 0, (hipStream_t)stream, scale,
+                       weights, ws, (uint32_t)seed, (uint32_t)batch, H, W, R);
+    const int rc = MMSEG_CHECK_LAUNCH();
+    if (rc) return rc;
+    const size_t lds = ((size_t)(EL_TH + 2 * R) * EL_TC * 2 + R + 1) * sizeof(double);
+    hipLaunchKernelGGL(elastic_blur_rows_kernel, dim3((W + EL_TC - 1) / EL_TC, (H + EL_TH - 1) / EL_TH, B), dim3(EL_TC * EL_TH / 2), lds,
+                       (hipStream_t)stream, scale, weights, ws, disp, H, W, R);
     return MMSEG_CHECK_LAUNCH();
 }
 

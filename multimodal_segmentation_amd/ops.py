@@ -7,6 +7,7 @@ layout (conv HWIO, dense [in, out]).
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -223,6 +224,7 @@ def release_caches(workspaces=True):
     _pair_cache.clear()
     _bnfold_cache.clear()
     _wprep_batch.clear()
+    _elastic_weights.clear()
     if workspaces:
         _workspaces.clear()
 
@@ -1593,21 +1595,79 @@ def affine_gather(data, rows, mat, order=1):
 FILL_MODES = ('nearest', 'constant', 'reflect', 'wrap')
 
 
-def augment_gather(data, rows, mat, shift=None, order=1, fill_mode='nearest', cval=0.):
-    """out[b] = resample of data[rows[b]] with the fp64 2x3 matrix mat[b] in (row, col) coordinates, scipy.ndimage boundary rule
-    `fill_mode` (FILL_MODES; 'constant' fills with cval), order 0/1; with shift [B,C] then keras' random_channel_shift
-    clip(x_c + shift[b,c], min(x), max(x)) over the transformed sample (csrc/augment.hip).  No gradient (input pipeline)."""
+def _gather(data, rows, mat, disp, shift, order, fill_mode, cval):
+    """mmseg_augment_gather, or with a displacement field mmseg_elastic_gather"""
     if fill_mode not in FILL_MODES:
         raise ValueError('fill_mode must be one of %s, got %r' % (FILL_MODES, fill_mode))
     B, (Nd, H, W, C) = mat.shape[0], data.shape
+    if disp is not None and tuple(disp.shape) != (B, H, W, 2):
+        raise ValueError('elastic_gather: disp must be [B,H,W,2] = %r, got %r' % ((B, H, W, 2), tuple(disp.shape)))
     out = _new((B, H, W, C), data)
     ws = None
     if shift is not None:
         shift = _c(shift)
         ws = _ws('augment', N.call('mmseg_augment_workspace_floats', B, H, W, C), data.device)
-    N.call('mmseg_augment_gather', data, rows, _c(mat), shift, out, ws, Nd, B, H, W, C, int(order), FILL_MODES.index(fill_mode),
-           float(cval))
+    tail = (shift, out, ws, Nd, B, H, W, C, int(order), FILL_MODES.index(fill_mode), float(cval))
+    if disp is None:
+        N.call('mmseg_augment_gather', data, rows, _c(mat), *tail)
+    else:
+        N.call('mmseg_elastic_gather', data, rows, _c(mat), _c(disp), *tail)
     return out
+
+
+def augment_gather(data, rows, mat, shift=None, order=1, fill_mode='nearest', cval=0.):
+    """out[b] = resample of data[rows[b]] with the fp64 2x3 matrix mat[b] in (row, col) coordinates, scipy.ndimage boundary rule
+    `fill_mode` (FILL_MODES; 'constant' fills with cval), order 0/1; with shift [B,C] then keras' random_channel_shift
+    clip(x_c + shift[b,c], min(x), max(x)) over the transformed sample (csrc/augment.hip).  No gradient (input pipeline)."""
+    return _gather(data, rows, mat, None, shift, order, fill_mode, cval)
+
+
+ELASTIC_MAX_RADIUS = 128          # EL_MAXR of csrc/augment.hip
+_elastic_weights = {}
+
+
+def elastic_radius(sigma):
+    """the blur radius of scipy.ndimage.gaussian_filter(truncate=4.0)"""
+    return int(4.0 * float(sigma) + 0.5)
+
+
+def elastic_weights(sigma):
+    """w_0 .. w_R of gaussian_filter's normalised kernel, fp64, as scipy computes them"""
+    R, s2 = elastic_radius(sigma), float(sigma) * float(sigma)
+    x = np.arange(-R, R + 1)
+    w = np.exp(-0.5 / s2 * x ** 2)
+    return (w / w.sum())[R:]
+
+
+def _i32(v):
+    """the low 32 bits of an int as a C int"""
+    return ((int(v) & 0xffffffff) ^ 0x80000000) - 0x80000000
+
+
+def elastic_field(scale, sigma, seed, batch, H, W):
+    """disp [B,H,W,2] fp32 = scale[b] * gaussian_filter(u, sigma, mode='reflect') per axis (0 row, 1 column), u in [-1, 1) Philox4x32-10
+    noise keyed by (seed, batch) and counted by (pixel, sample); scale [B] fp64 on the device, a zero leaves its sample's field +0.0
+    (csrc/augment.hip; the definition is in include/mmseg_hip.h).  No gradient (input pipeline)."""
+    R = elastic_radius(sigma)
+    if not (float(sigma) > 0) or R < 1 or R > ELASTIC_MAX_RADIUS:
+        raise ValueError('elastic_field: int(4*sigma + 0.5) must lie in [1, %d], got sigma=%r' % (ELASTIC_MAX_RADIUS, sigma))
+    B, H, W = int(scale.shape[0]), int(H), int(W)
+    key = (float(sigma), scale.device)
+    wts = _elastic_weights.get(key)
+    if wts is None:
+        wts = _elastic_weights[key] = torch.from_numpy(elastic_weights(sigma)).to(scale.device)          # once per sigma
+    disp = _new((B, H, W, 2), scale)
+    ws = _ws('elastic', N.call('mmseg_elastic_workspace_doubles', B, H, W), scale.device, torch.float64)
+    N.call('mmseg_elastic_field', _c(scale), wts, disp, ws, _i32(seed), _i32(batch), B, H, W, R)
+    return disp
+
+
+def elastic_gather(data, rows, mat, disp, shift=None, order=1, fill_mode='nearest', cval=0.):
+    """augment_gather with the displacement field disp [B,H,W,2] (elastic_field) added to the output pixel before the matrix:
+    out[b](p) = data[rows[b]](mat[b] (p + disp[b](p))), one interpolation, the boundary rule applied once.  No gradient (input pipeline)."""
+    if disp is None:
+        raise ValueError('elastic_gather: disp must be a [B,H,W,2] tensor, got None')
+    return _gather(data, rows, mat, disp, shift, order, fill_mode, cval)
 
 
 def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod):

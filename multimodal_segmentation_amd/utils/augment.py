@@ -18,6 +18,9 @@ the global RNG right after `next(gen)`), keeps the arrays resident in HBM and pr
 
 `AugmentFlow` does the same for every other pixel key of ImageDataGenerator (shift, shear, zoom, flips, channel shift, fill
 modes; `KerasTransformStream` is keras' full random_transform draw sequence) with one `mmseg_augment_gather` launch per array.
+
+Elastic deformation (ELASTIC_KEYS; build-defined, not keras) adds a random smooth displacement field to the coordinates of that
+same resampling: one field per batch, computed on the device from (seed, batch number, sample, pixel) and shared by every array.
 """
 import numpy as np
 import torch
@@ -93,6 +96,15 @@ DATAGEN_KEYS = ('rotation_range', 'width_shift_range', 'height_shift_range', 'sh
                 'fill_mode', 'cval', 'horizontal_flip', 'vertical_flip')
 
 
+# build-defined keys (not keras'): elastic deformation in the Simard 2003 / albumentations convention,
+#     displacement = elastic_alpha * gaussian_filter(uniform(-1, 1), elastic_sigma)   per axis, in pixels;
+# its RMS is about alpha / (sigma * sqrt(12 pi)) pixels (measured on 64 x 64: 0.0856 alpha at sigma 2, 0.0273 alpha at sigma 8, against
+# the formula's 0.0814 and 0.0204 -- the formula neglects the reflecting border, whose share grows with sigma / extent).
+#   elastic_alpha  0 (off)          elastic_sigma  required when alpha != 0; int(4 sigma + 0.5) in [1, 128]
+#   elastic_prob   1.0: the probability that a sample is deformed          elastic_seed  the flow's seed: seed of the elastic stream
+ELASTIC_KEYS = ('elastic_alpha', 'elastic_sigma', 'elastic_prob', 'elastic_seed')
+
+
 # keras arguments outside the device path: accepted only at a value that switches them off
 _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center', 'featurewise_std_normalization',
                   'samplewise_std_normalization', 'zca_whitening', 'zca_epsilon', 'rescale', 'preprocessing_function', 'data_format')
@@ -101,7 +113,7 @@ _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center',
 def check_datagen_params(params):
     """ValueError with a clear message for a dict the device pipeline cannot honour exactly; returns the dict."""
     for k, v in params.items():
-        if k in DATAGEN_KEYS:
+        if k in DATAGEN_KEYS or k in ELASTIC_KEYS:
             continue
         if k in _OFF_PATH_KEYS:
             if k == 'zca_epsilon' or v is None or v is False or (k == 'data_format' and v == 'channels_last') or \
@@ -124,12 +136,62 @@ def check_datagen_params(params):
     fm = params.get('fill_mode', 'nearest')
     if fm not in ops.FILL_MODES:
         raise ValueError('fill_mode must be one of %s, got %r' % (', '.join(ops.FILL_MODES), fm))
+    elastic_params(params)
     return params
 
 
+def _number(v):
+    return not isinstance(v, (bool, str)) and np.isscalar(v) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def elastic_params(params, seed=None):
+    """(alpha, sigma, prob, seed) of the ELASTIC_KEYS of a datagen dict, validated: ValueError naming the key"""
+    alpha, sigma = params.get('elastic_alpha', 0), params.get('elastic_sigma', None)
+    prob, eseed = params.get('elastic_prob', 1.0), params.get('elastic_seed', None)
+    if not _number(alpha) or not np.isfinite(alpha) or alpha < 0:
+        raise ValueError('elastic_alpha must be a number >= 0 (pixels times the blurred noise), got %r' % (alpha,))
+    if sigma is not None:
+        if not _number(sigma) or not np.isfinite(sigma) or sigma <= 0:
+            raise ValueError('elastic_sigma must be a number > 0, got %r' % (sigma,))
+        if not 1 <= ops.elastic_radius(sigma) <= ops.ELASTIC_MAX_RADIUS:
+            raise ValueError('elastic_sigma=%r gives a blur radius int(4*sigma + 0.5) = %d outside [1, %d]'
+                             % (sigma, ops.elastic_radius(sigma), ops.ELASTIC_MAX_RADIUS))
+    elif alpha != 0:
+        raise ValueError('elastic_sigma is required when elastic_alpha != 0')
+    if not _number(prob) or not 0 <= prob <= 1:
+        raise ValueError('elastic_prob must be a number in [0, 1], got %r' % (prob,))
+    if eseed is not None and (isinstance(eseed, bool) or not isinstance(eseed, (int, np.integer))):
+        raise ValueError('elastic_seed must be an integer, got %r' % (eseed,))
+    eseed = (0 if seed is None else seed) if eseed is None else eseed
+    return float(alpha), (None if sigma is None else float(sigma)), float(prob), int(eseed)
+
+
+def elastic_on(params):
+    """alpha != 0 and prob != 0"""
+    return bool(params.get('elastic_alpha', 0)) and bool(params.get('elastic_prob', 1.0))
+
+
+def philox4x32(counter, key, rounds=10):
+    """Philox4x32-10 in plain Python: 4 counter words, 2 key words -> 4 output words (the generator of the device's elastic noise)"""
+    c0, c1, c2, c3 = (int(v) & 0xffffffff for v in counter)
+    k0, k1 = (int(v) & 0xffffffff for v in key)
+    for _ in range(rounds):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xffffffff, (p0 >> 32) ^ c3 ^ k1, p0 & 0xffffffff
+        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+    return c0, c1, c2, c3
+
+
+def elastic_scales(alpha, prob, seed, batch, B):
+    """scale[b] = alpha where u01 < prob, else 0; u01 = (Q[0] >> 8) * 2^-24, Q = Philox(counter (b, 0, 0, 1), key (seed, batch)) --
+    counter word 3 keeps these draws apart from the field's noise, and numpy's global RNG is not touched"""
+    return np.array([alpha if (philox4x32((b, 0, 0, 1), (seed, batch))[0] >> 8) * 2.0 ** -24 < prob else 0.0 for b in range(B)],
+                    np.float64)
+
+
 def rotation_only(params):
-    """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges"""
-    return params.get('fill_mode', 'nearest') == 'nearest' and not any(
+    """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges, no elastic deformation"""
+    return not elastic_on(params) and params.get('fill_mode', 'nearest') == 'nearest' and not any(
         params.get(k) for k in ('width_shift_range', 'height_shift_range', 'shear_range', 'channel_shift_range',
                                 'horizontal_flip', 'vertical_flip')) and zoom_bounds(params.get('zoom_range', 0.) or 0.) == (1., 1.)
 
@@ -243,7 +305,12 @@ class AugmentFlow(object):
     with channel_shift_range != 0 an image (C = 1) and its masks (C = num_masks) consume different numbers of draws and, from the
     second sample of a batch on, get different geometry and flips (the shuffle, the first draw after the reseed, stays shared).
     So one KerasTransformStream runs per distinct channel count (a single one when channel_shift_range == 0), and the stream of
-    the LAST array in zip order runs last: the global RNG is left where keras' zipped next() leaves it."""
+    the LAST array in zip order runs last: the global RNG is left where keras' zipped next() leaves it.
+
+    With elastic deformation on (ELASTIC_KEYS) batch k, counted from 0, gets one displacement field from ops.elastic_field(scale, sigma,
+    elastic_seed, k, H, W), scale = elastic_scales(...): every array of the batch is gathered through that same field (images and masks
+    are deformed alike even where the channel-shift quirk gives them different matrices), and its draws are Philox words on the host
+    and the device -- the global numpy RNG sees exactly the draws it sees with elastic off."""
 
     def __init__(self, arrays, batch_size, seed, device, params, order=1):
         self.device = torch.device(device)
@@ -266,6 +333,8 @@ class AugmentFlow(object):
                 distinct.append(k)
         self.streams = [(k, KerasTransformStream(n, batch_size, seed, params, self.H, self.W, k or 1)) for k in distinct + [last]]
         self.order = order
+        self.elastic = elastic_params(params, seed) if elastic_on(params) else None
+        self.elastic_batch = 0
 
     def __iter__(self):
         return self
@@ -278,8 +347,15 @@ class AugmentFlow(object):
                 rows_d = nn.host_to_device(rows, self.device, np.int32)
             mats[k] = nn.host_to_device(m, self.device, np.float64)
             shifts[k] = None if sh is None else nn.host_to_device(sh, self.device, np.float32)
-        out = tuple(ops.augment_gather(a, rows_d, mats[k], shifts[k], self.order, self.fill_mode, self.cval)
-                    for a, k in zip(self.arrays, self.keys))
+        if self.elastic is None:
+            gather = ops.augment_gather
+        else:
+            alpha, sigma, prob, eseed = self.elastic
+            scale = elastic_scales(alpha, prob, eseed, self.elastic_batch, len(rows))
+            disp = ops.elastic_field(nn.host_to_device(scale, self.device, np.float64), sigma, eseed, self.elastic_batch, self.H, self.W)
+            self.elastic_batch += 1
+            gather = lambda a, r, m, *rest: ops.elastic_gather(a, r, m, disp, *rest)      # one field for every array of the batch
+        out = tuple(gather(a, rows_d, mats[k], shifts[k], self.order, self.fill_mode, self.cval) for a, k in zip(self.arrays, self.keys))
         return out if len(out) > 1 else out[0]
 
     next = __next__
