@@ -36,7 +36,10 @@ __global__ void bn_partial_kernel(const float* __restrict__ x, const float* __re
                 for (long r = r0 + r_in; r < r1; r += rl) { const float d = x[r * C + c] - sh; s1 += d; s2 += d * d; }
             } else {
                 const float mu = mean[c], is = invstd[c];
-                const float sc = y ? 0.f : scale[c], sh = y ? 0.f : shift[c];
+                // scale / shift are read only to recompute a ReLU mask: without ReLU and without a saved output (synchronised
+                // BatchNorm, mmseg_bn_bwd_sums) both pointers are null
+                const bool remask = relu && !y;
+                const float sc = remask ? scale[c] : 0.f, sh = remask ? shift[c] : 0.f;
                 for (long r = r0 + r_in; r < r1; r += rl) {
                     float g = dy[r * C + c];
                     const float xv = x[r * C + c];

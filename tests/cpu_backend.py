@@ -127,15 +127,19 @@ def bn_infer_fold(gamma, beta, mm, mv, conv_bias, scale, shift, C, eps):
 
 def bn_stats_local(x, stat2, ws, M, C):
     xr = x.reshape(M, C)
-    stat2.copy_(torch.stack([xr.mean(0), xr.var(0, unbiased=False)]).reshape(stat2.shape)); return 0
+    mu = xr[0] + (xr - xr[0]).mean(0)          # shifted by the first row, as the kernels: a mean of 50 keeps its last bits
+    stat2.copy_(torch.stack([mu, xr.var(0, unbiased=False)]).reshape(stat2.shape)); return 0
 
 
 def bn_stats_combine(gathered, R, gamma, beta, mean, invstd, scale, shift, mov_mean, mov_var, M_total, C, eps, momentum):
+    if R < 1:
+        return 1       # the library's own argument check (csrc/norm.hip)
     g = gathered.reshape(R, 2, C)
     mu = g[:, 0].mean(0)
     var = (g[:, 1] + (g[:, 0] - mu) ** 2).mean(0)
     is_ = torch.rsqrt(var + eps)
-    mean.copy_(mu); invstd.copy_(is_); scale.copy_(gamma * is_); shift.copy_(beta - mu * gamma * is_)
+    sc = gamma * is_
+    mean.copy_(mu); invstd.copy_(is_); scale.copy_(sc); shift.copy_(beta - mu * sc)
     if mov_mean is not None:
         unb = var * (M_total / (M_total - 1.0)) if M_total > 1 else var
         mov_mean.sub_((mov_mean - mu) * (1.0 - momentum)); mov_var.sub_((mov_var - unb) * (1.0 - momentum))
@@ -164,6 +168,8 @@ def bn_bwd_finish(local, glob, gamma, mean, invstd, dgamma, dbeta, coef, C, M_to
 
 
 def bn_bwd_apply(dy, y, x, coef, dx, M, C, relu):
+    if C & 3:
+        return 1       # the library's own argument check (csrc/norm.hip): 16-byte accesses
     g = dy.reshape(M, C)
     if relu:
         g = g * (y.reshape(M, C) > 0)
@@ -432,6 +438,8 @@ def bn_infer_prep(gamma, beta, mov_mean, mov_var, scale, shift, C, eps):
 
 
 def bn_apply(x, scale, shift, y, M, C, relu):
+    if C & 3:
+        return 1       # the library's own argument check (csrc/norm.hip): 16-byte accesses
     v = x.reshape(M, C) * scale + shift
     if relu:
         v = torch.relu(v)
@@ -448,6 +456,10 @@ def bn_bwd(dy, y, x, gamma, mean, invstd, dx, dgamma, dbeta, coef, ws, M, C, rel
         dbeta.add_(db); dgamma.add_(dg)
     else:
         dbeta.copy_(db); dgamma.copy_(dg)
+    if coef is not None:       # dx = A * g + Bc * x + Cc, the coefficients bn_bwd_final_kernel leaves behind
+        A = gamma * invstd
+        Bc = -gamma * invstd * invstd * dg / M
+        coef[:3 * C].copy_(torch.cat([A, Bc, -A * db / M - Bc * mean]))
     dx.copy_((gamma * invstd * (g - db / M - xh * dg / M)).reshape(dx.shape)); return 0
 
 

@@ -84,7 +84,7 @@ def test_rccl_single_rank_step_is_bitwise_the_plain_step():
 def test_sync_batchnorm_kernels_single_rank_equal_plain_batchnorm():
     """conf.sync_bn over RCCL with one rank: the split kernels (local statistics -> all-gather -> combine; local sums -> all-reduce
     -> finish -> apply) must reproduce the fused BatchNorm kernels on the same batch (the exact multi-rank equivalence with the
-    global-batch step is tests/test_dp_gloo.py's, on the CPU stand-in)."""
+    global-batch step is tests/test_dp_gloo.py's, on the CPU stand-in; the kernels with SEVERAL shards: tests/test_sync_bn_kernels.py)."""
     import torch.distributed as dist
     from multimodal_segmentation_amd import nn
     from multimodal_segmentation_amd.configuration import dafnet_config_chaos
