@@ -346,6 +346,40 @@ int mmseg_elastic_field(const double* scale, const double* weights, float* disp,
 int mmseg_elastic_gather(const float* data, const int* rows, const double* mat, const float* disp, const float* shift, float* out,
                          float* ws, int N, int B, int H, int W, int C, int order, int fill_mode, float cval, void* stream);
 
+/* ---- MR intensity augmentation of a gathered batch (csrc/intensity.hip; build-defined, after nnU-Net's gamma / contrast / noise / blur
+ *      transforms and TorchIO's RandomBiasField) ----
+ * x [B,H,W,C] fp32 is an image array of one training batch as the gathers above wrote it.  lo, hi, mean are the minimum, maximum and mean
+ * of a sample measured ONCE, before any intensity operation.  In this order, in fp64, rounded to fp32 once at the end:
+ *   blur      v = scipy.ndimage.gaussian_filter(x, sigma, mode='reflect', truncate=4.0) over H and W per channel, rounded to fp32
+ *             (mmseg_intensity_blur; the steps below are mmseg_intensity_apply)
+ *   bias      v = lo + (v - lo) * exp(f[r][c]), f = component 0 of field [B,H,W,2] (an mmseg_elastic_field), one value for all channels
+ *   contrast  v = mean + (v - mean) * c
+ *   clip      v = min(max(v, lo), hi), only after bias or contrast
+ *   gamma     if hi > lo: t = clamp((v - lo) / (hi - lo), 0, 1); t = invert ? 1 - pow(1 - t, g) : pow(t, g); v = lo + t * (hi - lo)
+ *   noise     v += std * sqrt(-2 ln u1) * cos(2 pi u2), u1 = ((P[0] >> 8) + 1) * 2^-24 in (0, 1], u2 = (P[1] >> 8) * 2^-24,
+ *             P = Philox4x32-10(counter (e, b, array, 3), key (seed, batch)), e = (r*W + c)*C + ch; no clip afterwards
+ * Shapes: 1 <= B <= 65535, H*W*C <= 2^31 - 1 - 65536 (32-bit element indices; below the 2^32 of the noise counter); the blur also needs
+ * H <= 65535, B*C <= 65535 and H*W < 2^30.  Anything else or a null pointer is refused (hipErrorInvalidValue, nothing is launched); B == 0
+ * does nothing.  Every sum runs in a fixed order: two runs are bitwise equal.  No host synchronisation, allocation or copy.
+ *
+ * ws: mmseg_intensity_workspace_doubles(B, H, W, C) doubles serve either mmseg_intensity_stats or mmseg_intensity_blur (launches of one
+ * stream run in order); the query launches nothing and returns 0 for a refused shape. */
+long mmseg_intensity_workspace_doubles(int B, int H, int W, int C);
+/* stats [B,3] fp64 = (min, max, sum) of every sample: per-block partials (wave64 shuffles + LDS) in ws, then one block per sample folds
+ * them.  The table stays on the device for mmseg_intensity_apply. */
+int mmseg_intensity_stats(const float* x, double* stats, double* ws, int B, int H, int W, int C, void* stream);
+/* separable blur with a per-sample radius: radius [B] int32 (0: the sample is copied bit for bit; above 32 is read as 32), weights [B,33]
+ * fp64 (row b holds w_0 .. w_radius[b] of the normalised kernel, w_-k = w_k), half-sample symmetric reflection of period 2n (right when
+ * the radius exceeds the extent), fp64 sums along W into ws, then along H; out [B,H,W,C] fp32, not x. */
+int mmseg_intensity_blur(const float* x, const int* radius, const double* weights, float* out, double* ws, int B, int H, int W, int C,
+                         void* stream);
+/* in place on x.  params [B,5] fp64 per sample: flags (1 bias + 2 contrast + 4 gamma + 8 noise), c, g, invert (non-zero: the curve is
+ * applied to the inverted sample), std.  stats: the table of mmseg_intensity_stats taken BEFORE the blur.  field NULL: no sample is
+ * biased.  A sample whose flags are 0 is neither read nor written; the noise is drawn only where its flag is set.  seed, batch and array
+ * are read as 32-bit patterns. */
+int mmseg_intensity_apply(float* x, const double* params, const double* stats, const float* field, int seed, int batch, int array,
+                          int B, int H, int W, int C, void* stream);
+
 /* ---- losses (csrc/loss.hip): costs.py:43-85,129-136, keras mae/mse, costs.ypred ---------------------------- */
 int mmseg_segloss_workspace_floats(int B);
 int mmseg_segloss_stats_floats(int B);

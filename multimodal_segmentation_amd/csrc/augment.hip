@@ -9,6 +9,7 @@
 // HBM-bound: one read of ~B slices + one write.  One thread per output element; consecutive threads walk the
 // channel-fastest NHWC order, so stores are fully coalesced and the 4 taps of neighbouring pixels share cache lines.
 #include "common.hpp"
+#include "philox.hpp"
 
 __global__ void affine_gather_kernel(const float* __restrict__ data, const int* __restrict__ rows, const float* __restrict__ mat,
                                      float* __restrict__ out, int H, int W, int C, long per_sample, int order) {
@@ -280,30 +281,7 @@ int mmseg_elastic_gather(const float* data, const int* rows, const double* mat, 
 #define EL_TH 64
 #define EL_TC 8
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t& o0, uint32_t& o1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o0 = c0;
-    o1 = c1;
-}
-
-// half-sample symmetric reflection, period 2n
-__device__ __forceinline__ int el_reflect(int i, int n) {
-    const int p = 2 * n;
-    int t = i % p;
-    if (t < 0) t += p;
-    return t >= n ? p - 1 - t : t;
-}
+// philox4x32_10 and el_reflect (half-sample symmetric reflection, period 2n): philox.hpp
 
 __global__ void __launch_bounds__(EL_TW) elastic_blur_cols_kernel(const double* __restrict__ scale, const double* __restrict__ wts,
                                                                   double* __restrict__ ws, uint32_t seed, uint32_t batch, int H, int W,

@@ -51,10 +51,12 @@ class Executor(object):
         keras flow per array with a shared seed, zipped).  A single array yields bare batches instead of 1-tuples.
         RotationFlow when the dict sets nothing but rotation_range (the reference's default), AugmentFlow otherwise."""
         from ..utils.augment import AugmentFlow, RotationFlow, rotation_only
-        arrays = []
+        arrays, n_images = [], 0
         for group in (train_images, train_labels):
             if group is not None:
                 arrays += list(group) if isinstance(group, (list, tuple)) else [group]
+            if group is train_images:
+                n_images = len(arrays)          # the leading arrays are images: intensity augmentation (INTENSITY_KEYS) changes only them
         if not arrays:
             raise Exception('No data to iterate.')
         p = self.datagen_params()
@@ -66,7 +68,7 @@ class Executor(object):
         if rotation_only(p):
             return RotationFlow(arrays, self.conf.batch_size, seed, self.device, rotation_range=p.get('rotation_range', 0.),
                                 order=order)
-        return AugmentFlow(arrays, self.conf.batch_size, seed, self.device, p, order=order)
+        return AugmentFlow(arrays, self.conf.batch_size, seed, self.device, p, order=order, n_images=n_images)
 
     def validate(self, epoch_loss):
         pass

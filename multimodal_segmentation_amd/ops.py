@@ -1670,6 +1670,72 @@ def elastic_gather(data, rows, mat, disp, shift=None, order=1, fill_mode='neares
     return _gather(data, rows, mat, disp, shift, order, fill_mode, cval)
 
 
+INTENSITY_BLUR_MAX_RADIUS = 32          # IN_MAXR of csrc/intensity.hip
+INTENSITY_FLAGS = dict(bias=1, contrast=2, gamma=4, noise=8)          # column 0 of intensity_apply's table
+INTENSITY_PARAMS = 5                                                  # its columns: flags, c, g, invert, std
+
+
+def intensity_weight_rows(sigmas):
+    """(radius [B] int32, weights [B, INTENSITY_BLUR_MAX_RADIUS + 1] fp64) of per-sample blur sigmas, on the host; sigma 0, or one so
+    small that gaussian_filter's kernel is the single weight 1, gives radius 0: the sample is copied"""
+    radius = np.zeros(len(sigmas), np.int32)
+    rows = np.zeros((len(sigmas), INTENSITY_BLUR_MAX_RADIUS + 1), np.float64)
+    for b, s in enumerate(sigmas):
+        R = elastic_radius(s) if s else 0
+        if R > INTENSITY_BLUR_MAX_RADIUS:
+            raise ValueError('intensity blur: int(4*sigma + 0.5) must not exceed %d, got sigma=%r' % (INTENSITY_BLUR_MAX_RADIUS, s))
+        if R:
+            radius[b] = R
+            rows[b, :R + 1] = elastic_weights(s)
+    return radius, rows
+
+
+def _intensity_ws(x):
+    B, H, W, C = x.shape
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('intensity: x must be a contiguous fp32 [B,H,W,C] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+    n = N.call('mmseg_intensity_workspace_doubles', B, H, W, C)
+    if B and not n:
+        raise ValueError('intensity: shape %r is outside the kernels\' limits (H*W*C < 2^31 - 65536, B <= 65535)' % (tuple(x.shape),))
+    return _ws('intensity', n, x.device, torch.float64)
+
+
+def intensity_stats(x):
+    """[B,3] fp64 (min, max, sum) of every sample of x [B,H,W,C], on the device (csrc/intensity.hip; fixed summation order)"""
+    B, H, W, C = x.shape
+    stats = _new((B, 3), x, torch.float64)
+    N.call('mmseg_intensity_stats', x, stats, _intensity_ws(x), B, H, W, C)
+    return stats
+
+
+def intensity_blur(x, radius, weights):
+    """scipy.ndimage.gaussian_filter(x[b], sigma_b, mode='reflect', truncate=4.0) over H and W with a radius and a weight row per sample
+    (intensity_weight_rows, uploaded by the caller); radius[b] == 0 copies the sample bit for bit.  A new tensor.  No gradient."""
+    B, H, W, C = x.shape
+    if tuple(radius.shape) != (B,) or tuple(weights.shape) != (B, INTENSITY_BLUR_MAX_RADIUS + 1):
+        raise ValueError('intensity_blur: radius must be [B] and weights [B, %d], got %r and %r'
+                         % (INTENSITY_BLUR_MAX_RADIUS + 1, tuple(radius.shape), tuple(weights.shape)))
+    out = _new(x.shape, x)
+    N.call('mmseg_intensity_blur', x, radius, weights, out, _intensity_ws(x), B, H, W, C)
+    return out
+
+
+def intensity_apply(x, params, stats, field, seed, batch, array):
+    """bias field, contrast, clip, gamma and noise IN PLACE on x [B,H,W,C] (the definition is in include/mmseg_hip.h): params [B,5] fp64
+    (INTENSITY_FLAGS, c, g, invert, std), stats from intensity_stats, field [B,H,W,2] (elastic_field) or None.  Returns x.  No gradient."""
+    B, H, W, C = x.shape
+    if tuple(params.shape) != (B, INTENSITY_PARAMS) or tuple(stats.shape) != (B, 3):
+        raise ValueError('intensity_apply: params must be [B,%d] and stats [B,3], got %r and %r'
+                         % (INTENSITY_PARAMS, tuple(params.shape), tuple(stats.shape)))
+    if field is not None and tuple(field.shape) != (B, H, W, 2):
+        raise ValueError('intensity_apply: field must be [B,H,W,2] = %r, got %r' % ((B, H, W, 2), tuple(field.shape)))
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('intensity_apply: x must be a contiguous fp32 tensor, got %s' % (x.dtype,))
+    N.call('mmseg_intensity_apply', x, params, stats, None if field is None else _c(field), _i32(seed), _i32(batch), _i32(array),
+           B, H, W, C)
+    return x
+
+
 def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod):
     """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
     (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,

@@ -21,6 +21,9 @@ modes; `KerasTransformStream` is keras' full random_transform draw sequence) wit
 
 Elastic deformation (ELASTIC_KEYS; build-defined, not keras) adds a random smooth displacement field to the coordinates of that
 same resampling: one field per batch, computed on the device from (seed, batch number, sample, pixel) and shared by every array.
+
+MR intensity augmentation (INTENSITY_KEYS; build-defined, not keras) then changes the grey values of the IMAGE arrays of the gathered batch
+on the device: blur, bias field, contrast, gamma and noise, every image array with its own Philox draws (csrc/intensity.hip).
 """
 import numpy as np
 import torch
@@ -105,6 +108,24 @@ DATAGEN_KEYS = ('rotation_range', 'width_shift_range', 'height_shift_range', 'sh
 ELASTIC_KEYS = ('elastic_alpha', 'elastic_sigma', 'elastic_prob', 'elastic_seed')
 
 
+# build-defined keys (not keras'): MR intensity augmentation of the image arrays after the gather, in the spirit of nnU-Net's gamma /
+# contrast / noise / blur transforms and TorchIO's RandomBiasField.  Every operation is drawn per sample and per image array and is on
+# where its Philox uniform falls below its probability (intensity_draws); the order is blur, bias field, contrast, clip, gamma, noise and
+# the sample's minimum, maximum and mean are measured ONCE, before all of them (the definition: include/mmseg_hip.h).  Unlike nnU-Net,
+# contrast keeps the mean and gamma the range of the UNAUGMENTED sample, and the noise is drawn by standard deviation, not variance.
+#   gamma_range (lo, hi)  None (off): exponent g uniform in [lo, hi], 0 < lo <= hi      gamma_prob  1.0
+#   gamma_invert_prob  0: the probability that the curve is applied to the inverted sample (nnU-Net's invert_image)
+#   contrast_range (lo, hi)  None (off): factor c about the sample's mean                 contrast_prob  1.0
+#   noise_std_max  0 (off): the sample's standard deviation is u * noise_std_max, in units of the [-1, 1] images      noise_prob  1.0
+#   blur_sigma_range (lo, hi)  None (off): Gaussian sigma in pixels, int(4 hi + 0.5) in [1, 32]      blur_prob  1.0
+#   bias_field_strength  0 (off): about the RMS of the log of the smooth multiplicative field (it is an elastic_field of scale
+#                        strength * sigma * sqrt(12 pi), by the RMS relation above)       bias_field_sigma  required with a strength;
+#                        elastic_sigma's bounds       bias_field_prob  1.0
+#   intensity_seed  the flow's seed: seed of the intensity stream
+INTENSITY_KEYS = ('gamma_range', 'gamma_prob', 'gamma_invert_prob', 'contrast_range', 'contrast_prob', 'noise_std_max', 'noise_prob',
+                  'blur_sigma_range', 'blur_prob', 'bias_field_strength', 'bias_field_sigma', 'bias_field_prob', 'intensity_seed')
+
+
 # keras arguments outside the device path: accepted only at a value that switches them off
 _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center', 'featurewise_std_normalization',
                   'samplewise_std_normalization', 'zca_whitening', 'zca_epsilon', 'rescale', 'preprocessing_function', 'data_format')
@@ -113,7 +134,7 @@ _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center',
 def check_datagen_params(params):
     """ValueError with a clear message for a dict the device pipeline cannot honour exactly; returns the dict."""
     for k, v in params.items():
-        if k in DATAGEN_KEYS or k in ELASTIC_KEYS:
+        if k in DATAGEN_KEYS or k in ELASTIC_KEYS or k in INTENSITY_KEYS:
             continue
         if k in _OFF_PATH_KEYS:
             if k == 'zca_epsilon' or v is None or v is False or (k == 'data_format' and v == 'channels_last') or \
@@ -137,6 +158,7 @@ def check_datagen_params(params):
     if fm not in ops.FILL_MODES:
         raise ValueError('fill_mode must be one of %s, got %r' % (', '.join(ops.FILL_MODES), fm))
     elastic_params(params)
+    intensity_params(params)
     return params
 
 
@@ -189,9 +211,111 @@ def elastic_scales(alpha, prob, seed, batch, B):
                     np.float64)
 
 
+def _range(params, key):
+    """a (lo, hi) key: None, or a pair of finite numbers with 0 < lo <= hi"""
+    v = params.get(key, None)
+    if v is None:
+        return None
+    if not isinstance(v, (list, tuple, np.ndarray)) or len(v) != 2 or not all(_number(t) and np.isfinite(t) for t in v) or \
+            not 0 < v[0] <= v[1]:
+        raise ValueError('%s must be None or a pair (lo, hi) of numbers with 0 < lo <= hi, got %r' % (key, v))
+    return float(v[0]), float(v[1])
+
+
+def _prob(params, key, default):
+    v = params.get(key, default)
+    if not _number(v) or not 0 <= v <= 1:
+        raise ValueError('%s must be a number in [0, 1], got %r' % (key, v))
+    return float(v)
+
+
+def intensity_params(params, seed=None):
+    """the INTENSITY_KEYS of a datagen dict as a dict with every default filled in, validated: ValueError naming the key"""
+    p = dict(gamma=_range(params, 'gamma_range'), gamma_prob=_prob(params, 'gamma_prob', 1.0),
+             invert_prob=_prob(params, 'gamma_invert_prob', 0.), contrast=_range(params, 'contrast_range'),
+             contrast_prob=_prob(params, 'contrast_prob', 1.0), noise_prob=_prob(params, 'noise_prob', 1.0),
+             blur=_range(params, 'blur_sigma_range'), blur_prob=_prob(params, 'blur_prob', 1.0),
+             bias_prob=_prob(params, 'bias_field_prob', 1.0))
+    std = params.get('noise_std_max', 0)
+    if not _number(std) or not np.isfinite(std) or std < 0:
+        raise ValueError('noise_std_max must be a number >= 0 (in units of the [-1, 1] images), got %r' % (std,))
+    if p['blur'] is not None and not 1 <= ops.elastic_radius(p['blur'][1]) <= ops.INTENSITY_BLUR_MAX_RADIUS:
+        raise ValueError('blur_sigma_range=%r gives a blur radius int(4*hi + 0.5) = %d outside [1, %d]'
+                         % (params['blur_sigma_range'], ops.elastic_radius(p['blur'][1]), ops.INTENSITY_BLUR_MAX_RADIUS))
+    s, sigma = params.get('bias_field_strength', 0), params.get('bias_field_sigma', None)
+    if not _number(s) or not np.isfinite(s) or s < 0:
+        raise ValueError('bias_field_strength must be a number >= 0 (RMS of the log of the field), got %r' % (s,))
+    if sigma is not None:
+        if not _number(sigma) or not np.isfinite(sigma) or sigma <= 0:
+            raise ValueError('bias_field_sigma must be a number > 0, got %r' % (sigma,))
+        if not 1 <= ops.elastic_radius(sigma) <= ops.ELASTIC_MAX_RADIUS:
+            raise ValueError('bias_field_sigma=%r gives a blur radius int(4*sigma + 0.5) = %d outside [1, %d]'
+                             % (sigma, ops.elastic_radius(sigma), ops.ELASTIC_MAX_RADIUS))
+    elif s != 0:
+        raise ValueError('bias_field_sigma is required when bias_field_strength != 0')
+    iseed = params.get('intensity_seed', None)
+    if iseed is not None and (isinstance(iseed, bool) or not isinstance(iseed, (int, np.integer))):
+        raise ValueError('intensity_seed must be an integer, got %r' % (iseed,))
+    p.update(noise_std_max=float(std), bias_strength=float(s), bias_sigma=None if sigma is None else float(sigma),
+             seed=int((0 if seed is None else seed) if iseed is None else iseed))
+    return p
+
+
+def intensity_on(params):
+    """some intensity operation has a switched-on value and a non-zero probability"""
+    ranges = any(params.get(k) is not None and bool(params.get(pk, 1.0)) for k, pk in (
+        ('gamma_range', 'gamma_prob'), ('contrast_range', 'contrast_prob'), ('blur_sigma_range', 'blur_prob')))
+    return ranges or any(bool(params.get(k, 0)) and bool(params.get(pk, 1.0)) for k, pk in (
+        ('noise_std_max', 'noise_prob'), ('bias_field_strength', 'bias_field_prob')))
+
+
+def intensity_draws(params, seed, batch, B, n_images):
+    """The intensity draws of batch number `batch` (counted from 0) for B samples of n_images image arrays, as numpy tables [n_images, B]:
+    blur / bias / contrast / noise / gamma / invert (bool: the operation is on) and sigma / c / std / g (fp64, 0 where off).
+    Q_j = Philox(counter (b, a, j, 2), key (intensity_seed, batch)), u(w) = (w >> 8) * 2^-24:
+        Q_0 = (p_blur, u_blur, p_bias, -)   Q_1 = (p_contrast, u_contrast, p_noise, u_noise)   Q_2 = (p_gamma, u_gamma, p_invert, -)
+    on iff p < prob; a value is lo + u * (hi - lo), the noise's std u * noise_std_max.  Counter word 3 = 2 keeps these apart from the
+    elastic field (0) and the elastic scales (1); numpy's global RNG is not touched."""
+    p = intensity_params(params, seed)
+    u = np.array([[[[(w >> 8) * 2.0 ** -24 for w in philox4x32((b, a, j, 2), (p['seed'], batch))] for j in range(3)]
+                   for b in range(B)] for a in range(n_images)], np.float64).reshape(n_images, B, 3, 4)
+    d = {}
+
+    def draw(name, value, rng, prob, pw, uw):
+        on = (u[:, :, pw[0], pw[1]] < prob) & (rng is not None)
+        lo, hi = rng if rng is not None else (0., 0.)
+        d[name], d[value] = on, np.where(on, lo + u[:, :, uw[0], uw[1]] * (hi - lo), 0.)
+
+    draw('blur', 'sigma', p['blur'], p['blur_prob'], (0, 0), (0, 1))
+    draw('contrast', 'c', p['contrast'], p['contrast_prob'], (1, 0), (1, 1))
+    draw('noise', 'std', (0., p['noise_std_max']) if p['noise_std_max'] else None, p['noise_prob'], (1, 2), (1, 3))
+    draw('gamma', 'g', p['gamma'], p['gamma_prob'], (2, 0), (2, 1))
+    d['bias'] = (u[:, :, 0, 2] < p['bias_prob']) & (p['bias_strength'] != 0)
+    d['invert'] = d['gamma'] & (u[:, :, 2, 2] < p['invert_prob'])
+    return d
+
+
+def intensity_tables(params, seed, draws, a):
+    """the host tables of image array a for one batch, from intensity_draws' `draws`: (radius [B] int32, weight rows [B,33] fp64) or None
+    when no sample is blurred; the [B,5] fp64 table of ops.intensity_apply or None when nothing else is on; (scale [B] fp64, sigma,
+    seed) of the bias field's ops.elastic_field or None when no sample is biased"""
+    p = intensity_params(params, seed)
+    F = ops.INTENSITY_FLAGS
+    blur = ops.intensity_weight_rows(draws['sigma'][a]) if draws['blur'][a].any() else None
+    flags = sum(F[k] * draws[k][a].astype(np.int64) for k in ('bias', 'contrast', 'gamma', 'noise'))
+    table = np.stack([flags.astype(np.float64), draws['c'][a], draws['g'][a], draws['invert'][a].astype(np.float64), draws['std'][a]],
+                     axis=1) if flags.any() else None
+    field = None
+    if draws['bias'][a].any():
+        scale = np.where(draws['bias'][a], p['bias_strength'] * p['bias_sigma'] * np.sqrt(12.0 * np.pi), 0.0)
+        field = (scale, p['bias_sigma'], (p['seed'] + 0x9E3779B9 * (a + 1)) % 2 ** 32)
+    return blur, table, field
+
+
 def rotation_only(params):
-    """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges, no elastic deformation"""
-    return not elastic_on(params) and params.get('fill_mode', 'nearest') == 'nearest' and not any(
+    """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges, no elastic deformation and no
+    intensity augmentation"""
+    return not elastic_on(params) and not intensity_on(params) and params.get('fill_mode', 'nearest') == 'nearest' and not any(
         params.get(k) for k in ('width_shift_range', 'height_shift_range', 'shear_range', 'channel_shift_range',
                                 'horizontal_flip', 'vertical_flip')) and zoom_bounds(params.get('zoom_range', 0.) or 0.) == (1., 1.)
 
@@ -310,9 +434,13 @@ class AugmentFlow(object):
     With elastic deformation on (ELASTIC_KEYS) batch k, counted from 0, gets one displacement field from ops.elastic_field(scale, sigma,
     elastic_seed, k, H, W), scale = elastic_scales(...): every array of the batch is gathered through that same field (images and masks
     are deformed alike even where the channel-shift quirk gives them different matrices), and its draws are Philox words on the host
-    and the device -- the global numpy RNG sees exactly the draws it sees with elastic off."""
+    and the device -- the global numpy RNG sees exactly the draws it sees with elastic off.
 
-    def __init__(self, arrays, batch_size, seed, device, params, order=1):
+    With intensity augmentation on (INTENSITY_KEYS) the first n_images arrays are images: after the gather each of them is changed on the
+    device with its own draws of batch k (intensity_draws: Philox, the global numpy RNG is untouched); the other arrays (masks) are not.
+    n_images = 0 (the default) leaves every array as gathered."""
+
+    def __init__(self, arrays, batch_size, seed, device, params, order=1, n_images=0):
         self.device = torch.device(device)
         self.arrays = [a if isinstance(a, torch.Tensor) else
                        torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device) for a in arrays]
@@ -335,9 +463,36 @@ class AugmentFlow(object):
         self.order = order
         self.elastic = elastic_params(params, seed) if elastic_on(params) else None
         self.elastic_batch = 0
+        if not 0 <= int(n_images) <= len(self.arrays):
+            raise ValueError('n_images must lie in [0, %d], got %r' % (len(self.arrays), n_images))
+        self.n_images = int(n_images)
+        self.intensity = (dict(params), seed) if intensity_on(params) and self.n_images else None
+        self.intensity_batch = 0
+        if self.intensity is not None:
+            intensity_params(*self.intensity)
 
     def __iter__(self):
         return self
+
+    def _intensity(self, out):
+        """blur, bias field, contrast, gamma and noise on the leading image arrays of one gathered batch"""
+        (params, seed), k = self.intensity, self.intensity_batch
+        self.intensity_batch += 1
+        up = lambda a, dtype: nn.host_to_device(a, self.device, dtype)
+        draws = intensity_draws(params, seed, k, int(out[0].shape[0]), self.n_images)
+        iseed = intensity_params(params, seed)['seed']
+        for a in range(self.n_images):
+            blur, table, field = intensity_tables(params, seed, draws, a)
+            x = out[a]
+            stats = ops.intensity_stats(x) if table is not None else None          # of the sample as gathered: before the blur
+            if blur is not None:
+                x = ops.intensity_blur(x, up(blur[0], np.int32), up(blur[1], np.float64))
+            if table is not None:
+                if field is not None:
+                    field = ops.elastic_field(up(field[0], np.float64), field[1], field[2], k, self.H, self.W)
+                ops.intensity_apply(x, up(table, np.float64), stats, field, iseed, k, a)
+            out[a] = x
+        return out
 
     def __next__(self):
         rows_d, mats, shifts = None, {}, {}
@@ -356,6 +511,8 @@ class AugmentFlow(object):
             self.elastic_batch += 1
             gather = lambda a, r, m, *rest: ops.elastic_gather(a, r, m, disp, *rest)      # one field for every array of the batch
         out = tuple(gather(a, rows_d, mats[k], shifts[k], self.order, self.fill_mode, self.cval) for a, k in zip(self.arrays, self.keys))
+        if self.intensity is not None:
+            out = tuple(self._intensity(list(out)))
         return out if len(out) > 1 else out[0]
 
     next = __next__
