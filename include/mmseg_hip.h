@@ -73,7 +73,8 @@ int mmseg_conv2d_fwd_scaled_t(const void* x1, const void* x2, const float* w, co
 /* which kernel template the last convolution entry point launched: family * 1000000 + 500000 * flag + (M | K tile) * 1000 + N tile (flag:
  * 16-byte gather of the generic kernels / two inputs of conv_wgrad_tr_kernel); families
  * 1 conv_fast_kernel, 2 conv_fwd_kernel, 3 conv_direct_kernel, 4 conv_fast_batched_kernel, 5 conv_dgrad_s2k4_smallc_kernel,
- * 6 conv_wgrad_tr_kernel, 7 conv_wgrad_fast_kernel, 8 conv_wgrad_kernel, 9 conv_wgrad_c8_kernel (profiling aid, no launch) */
+ * 6 conv_wgrad_tr_kernel, 7 conv_wgrad_fast_kernel, 8 conv_wgrad_kernel, 9 conv_wgrad_c8_kernel, 25 conv_fast_planes_kernel (the
+ * products of mmseg_conv2d_fwd_wino) (profiling aid, no launch) */
 int mmseg_conv2d_last_kernel(void);
 /* fast path (Cin % 32 == 0, not transposed, at most 32 taps -- the reference's largest kernel is 5 x 5; more taps fall back to the
  * generic kernel, which reads `w`): K tiles lie inside one tap, gather by buffer loads, weights read from
@@ -130,6 +131,26 @@ int mmseg_conv2d_fwd_ups_parity(const float* x, const float* wt_classes, const f
 /* weight gradient of such a layer (models/unet.py:67-82), second half: dW [3,3,C1,Cout] += sum_{u in KU[kh], v in KU[kw]} dWe[u][v][co][ci]
  * with KU = [{2,3},{1,2},{0,1}] and dWe [4,4,Cout,C1] the weight gradient of the 4x4 stride-2 pad-1 convolution that maps dy to dx. */
 int mmseg_conv2d_ups_wgrad_fold(const float* dWe, float* dW, int C1, int Cout, void* stream);
+/* ---- Winograd F(2x2, 3x3) for the inference forward of the deep 3x3 'same' layers (`predict` of the conv blocks of models/unet.py:94-101):
+ * weight image, input transform, sixteen products in one launch of the fast-path body, output transform with the folded BatchNorm.
+ * Process-wide switch like mmseg_conv2d_ups_fold_mode: 0 = never, 1 (default) = the shapes measured faster than the direct launch,
+ * 2 = wherever the structural conditions hold.  Returns the previous mode; other values only query. */
+int mmseg_conv2d_wino_mode(int mode);
+/* 1 when the inference forward of a 3x3, stride 1, 'same' layer without up-sampling x1 [B,H,W,C1] (+ x2 [B,H,W,C2]) -> y [B,H,W,Cout]
+ * takes the route: fp32 precision mode, H and W even, C1 / C2 / Cout multiples of 32 (C1, Cout >= 32), every tensor and every plane of
+ * the workspace below 2^31 - 64 bytes; in mode 1 also H, W <= 64, B * H/2 * W/2 >= 512, C1 + C2 >= 256 and Cout >= 256
+ * (the region measured faster, profiles/wino_ab.txt).  No launch. */
+int mmseg_conv2d_wino_ok(int B, int H, int W, int C1, int C2, int Cout);
+/* floats of workspace of mmseg_conv2d_fwd_wino: 16 * B * H/2 * W/2 * (C1 + C2 + Cout) */
+long mmseg_conv2d_wino_workspace(int B, int H, int W, int C1, int C2, int Cout);
+/* weight image out [16][Cout][Cin] = G w G^T per (ci, co) of w [3,3,Cin,Cout], plane p = i * 4 + j, G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]];
+ * fixed summation order.  fp32 mode only. */
+int mmseg_conv2d_wprep_wino(const float* w, float* out, int Cin, int Cout, void* stream);
+/* y = act(conv3x3_same(concat(x1, x2)) * oscale[c] + bias[c]) (oscale / bias may be NULL; scale before bias, the expression of
+ * mmseg_conv2d_fwd_scaled) in four launches; U from mmseg_conv2d_wprep_wino; ws = caller's scratch of at least
+ * mmseg_conv2d_wino_workspace floats (checked, with the structural conditions and 16-byte alignment, before anything is queued). */
+int mmseg_conv2d_fwd_wino(const float* x1, const float* x2, const float* U, const float* bias, const float* oscale, float* y, int B, int H,
+                          int W, int C1, int C2, int Cout, int act, float alpha, float* ws, long ws_floats, void* stream);
 /* Data gradient of a stride-1 convolution with few input channels (segmentor c0 8 -> 64, the SPADE shared convolutions 8 -> 128:
  * model_components/segmentor.py:16, layers/spade.py:29), second half: dx = sum over the taps of the shifted planes of
  * T [B,Ho,Wo,KH*KW*Cin], which the caller computes with ONE 1x1 mmseg_conv2d_fwd over dy (wt = the Keras kernel itself read as

@@ -781,7 +781,7 @@ static int g_conv_bf16 = 0;     // 0 fp32, 1 bf16, 2 fp16
 // M tile * 1000 + N tile (flag: 16-byte gather of the generic kernels / 16-bit input of the fast kernels / two inputs of conv_wgrad_tr_kernel); families: 1 conv_fast_kernel, 2 conv_fwd_kernel (generic), 3 conv_direct_kernel, 4 conv_fast_batched_kernel,
 // 5 conv_dgrad_s2k4_smallc_kernel, 6 conv_wgrad_tr_kernel, 7 conv_wgrad_fast_kernel, 8 conv_wgrad_kernel, 9 conv_wgrad_c8_kernel,
 // 10 pw_reduce_kernel<LANES, COUT, VPL>, 12 pw_reduce_wgrad_kernel<...> (M tile field = LANES, N tile field = COUT);
-// 11 smallk_conv_kernel<KS, CIN, L>, 13 smallk_wgrad_kernel<...> (M tile field = KS * 20 + L, N tile field = CIN); 14 conv_wgrad_tr_anyw_kernel; 16 conv16_kernel, 17 conv16h_kernel (M tile field = pixels per block), 18 wgrad32h_kernel<NCI, NCO>, 19 wgrad16h_kernel, 20 conv8h_kernel (M tile field = 16-bit x | 2 * 16-bit y | 4 * ReLU); 21 s2k3c9_fwd_kernel (N field 16) / s2k3c9_dgrad_kernel (N field 9), 22 s2k3c9_wgrad_kernel, 23 locnet5_fwd_kernel / locnet5_f32_kernel, 24 locnet5_wgrad_kernel
+// 11 smallk_conv_kernel<KS, CIN, L>, 13 smallk_wgrad_kernel<...> (M tile field = KS * 20 + L, N tile field = CIN); 14 conv_wgrad_tr_anyw_kernel; 16 conv16_kernel, 17 conv16h_kernel (M tile field = pixels per block), 18 wgrad32h_kernel<NCI, NCO>, 19 wgrad16h_kernel, 20 conv8h_kernel (M tile field = 16-bit x | 2 * 16-bit y | 4 * ReLU); 21 s2k3c9_fwd_kernel (N field 16) / s2k3c9_dgrad_kernel (N field 9), 22 s2k3c9_wgrad_kernel, 23 locnet5_fwd_kernel / locnet5_f32_kernel, 24 locnet5_wgrad_kernel, 25 conv_fast_planes_kernel (the sixteen Winograd products of mmseg_conv2d_fwd_wino, wino.hpp)
 static int g_last_kernel = 0;
 #define MMSEG_SET_LAST(fam, bm, bn) (g_last_kernel = (fam) * 1000000 + (bm) * 1000 + (bn))
 template <int BM, int BN, int WM, int WN, int PREC = 0, bool IN16 = false>
@@ -2967,3 +2967,5 @@ int mmseg_conv2d_wflip(const float* w, float* wt, int KH, int KW, int Cin, int C
 }
 
 }  // extern "C"
+
+#include "wino.hpp"

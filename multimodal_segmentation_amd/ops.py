@@ -357,6 +357,38 @@ def _ups_fold_ok(x1, Cout, direction):
     return bool(N.call('mmseg_conv2d_ups_fold_ok', B, H1, W1, C1, Cout, direction))
 
 
+def _wprep_wino(w, Cin, Cout, wkey=None):
+    """Winograd F(2x2,3x3) weight image U [16][Cout][Cin] of a 3x3 layer (mmseg_conv2d_wprep_wino, 16/9 of the layer's weights); cached
+    per weight version like _wprep_ups."""
+    n = 16 * Cin * Cout
+    key = (wkey, w.data_ptr(), 'wino', _sid(w.device))
+    ent = _wprep_cache.get(key) if wkey is not None else None
+    if ent is not None and ent[0] == _wver(wkey) and ent[1].numel() == n:
+        return ent[1]
+    if wkey is None:
+        out = _ws('wprep_wino', n, w.device)[:n]
+    else:
+        out = ent[1] if (ent is not None and ent[1].numel() == n) else torch.empty(n, dtype=torch.float32, device=w.device)
+    N.call('mmseg_conv2d_wprep_wino', w, out, Cin, Cout)
+    if wkey is not None:
+        _wprep_cache[key] = (_wver(wkey), out)
+    return out
+
+
+def _wino_ok(x1, x2, w, ups, out_dtype):
+    """the inference forward of this layer takes the Winograd route: a 3x3 'same' fp32 layer without up-sampling that
+    mmseg_conv2d_wino_ok admits (mode, precision, shape)"""
+    if ups or tuple(w.shape[:2]) != (3, 3):
+        return False
+    if not (x1.dtype == w.dtype == out_dtype == torch.float32) or (x2 is not None and x2.dtype != torch.float32):
+        return False
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    if not N.call('mmseg_conv2d_fast_path', C1, C2, w.shape[3], 0):      # the products run on the fast path's body
+        return False
+    return bool(N.call('mmseg_conv2d_wino_ok', B, H, W, C1, C2, w.shape[3]))
+
+
 def _conv_fwd_raw(x1, x2, w, wt, bias, y, y2, B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, ups, transposed,
                   act, alpha, nsplit1):
     # host-side shape checks: the kernel trusts these numbers
@@ -585,6 +617,12 @@ def conv2d_bn_infer(x, w, cbias, gamma, beta, mov_mean, mov_var, relu=False, x2=
     if _ups_fold(x1, x2, w, 1, 'same', upsample, out_dtype) and _ups_fold_ok(x1, Cout, 3):
         N.call('mmseg_conv2d_fwd_ups_parity', x1, _wprep_ups(w, C1, Cout, 0, wkey), ss[1], ss[0], y, B, H1, W1, C1, Cout,
                ACT['relu' if relu else None], 0.0)
+        return y
+    if _wino_ok(x1, x2, w, upsample, out_dtype):
+        need = N.call('mmseg_conv2d_wino_workspace', B, H, W, C1, C2, Cout)
+        ws = _ws('wino', need, x1.device)
+        N.call('mmseg_conv2d_fwd_wino', x1, x2, _wprep_wino(w, Cin, Cout, wkey), ss[1], ss[0], y, B, H, W, C1, C2, Cout,
+               ACT['relu' if relu else None], 0.0, ws, ws.numel())
         return y
     wt = _wprep(w, KH, KW, Cin, Cout, 0, wkey) if N.call('mmseg_conv2d_fast_path', C1, C2, Cout, 0) else None
     io = (1 if _h(x1) else 0) | (2 if _h(x2) else 0) | (4 if _h(y) else 0)
