@@ -444,7 +444,34 @@ int mmseg_diffloss_grad(const float* p, const float* t, float tconst, long n, in
 int mmseg_diffloss_grad_s(const float* p, const float* t, float tconst, long n, int mode, float scale, const float* scale_dev, float* dp,
                           void* stream);
 
-/* ---- optimiser / regulariser (csrc/optim.hip) ---------------------------------------------------------- */
+/* ---- boundary loss of the segmentor (csrc/boundary.hip; BUILD-DEFINED, conf.w_boundary: the reference's losses hold no distance.
+ *      Kervadec et al., "Boundary loss for highly unbalanced segmentation", MIDL 2019) ----
+ * mmseg_boundary_map: target [B,H,W,C] fp32 NHWC (the tensor mmseg_segloss_* reads), foreground of channel k < nm is target > 0.5;
+ * phi [B,H,W,nm] fp32, every element written.  Per sample and channel, with d_fg(q) / d_bg(q) the Euclidean distance in pixels from
+ * q to the nearest foreground / background pixel (the image edge is not background):
+ *     phi(q) = d_fg(q) where q is background,  phi(q) = -(d_bg(q) - 1) where q is foreground,
+ *     phi = 0 everywhere for a mask that is empty or full
+ * (one_hot2dist of the paper's code over scipy.ndimage.distance_transform_edt; the full mask is defined here).  Exact: int32 squared
+ * distances from a two-pass separable minimum, one correctly rounded sqrtf, then the "- 1" in fp32.  1 <= nm <= C <= 8,
+ * 1 <= H, W <= 2048 (H^2 + W^2 < 2^24), 1 <= B <= 65535; anything else, or a null pointer, returns hipErrorInvalidValue and launches
+ * nothing.  ws: mmseg_boundary_workspace_bytes(B, H, W, nm) bytes (0 for arguments that would be refused).  No host synchronisation,
+ * no allocation, no atomics: two runs are bitwise equal, and the launches may be recorded into a hipGraph.
+ * mmseg_boundary_loss: loss_b[0] = sum over b, px, k < nm of pred[b,px,k] * phi[b,px,k], divided by B * HW * nm; pred [B,HW,C], phi
+ * [B,HW,nm].  Two stages in a fixed order; ws: mmseg_boundary_loss_workspace_floats(B) floats.
+ * mmseg_boundary_grad_add: for k < nm, dpred[b,px,k] += s * phi[b,px,k] with s = ((scale_host * scale_dev[0]) * weight_dev[0]) /
+ * (float)(B * HW * nm), every step rounded to fp32 (scale_dev == NULL: the factor is left out); channels >= nm are not touched.  It adds
+ * to what mmseg_segloss_grad[_s] wrote.  weight_dev [1] lives on the device so that a recorded step follows a weight the host changes
+ * between replays.
+ * mmseg_boundary_combine: loss[0] += weight_dev[0] * loss_b[0] (one thread; loss_b stays as it was). */
+long mmseg_boundary_workspace_bytes(int B, int H, int W, int nm);
+int mmseg_boundary_map(const float* target, float* phi, int* ws, int B, int H, int W, int C, int nm, void* stream);
+int mmseg_boundary_loss_workspace_floats(int B);
+int mmseg_boundary_loss(const float* pred, const float* phi, float* loss_b, float* ws, int B, long HW, int C, int nm, void* stream);
+int mmseg_boundary_grad_add(const float* phi, float* dpred, int B, long HW, int C, int nm, float scale_host, const float* scale_dev,
+                            const float* weight_dev, void* stream);
+int mmseg_boundary_combine(float* loss, const float* loss_b, const float* weight_dev, void* stream);
+
+/* ---- optimiser / regulariser (csrc/optim.hip)---------------------------------------------------------- */
 /* Keras 2.1.6 Adam step over a flat arena (models/dafnet.py:93,114,155,161) */
 int mmseg_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2, float eps, void* stream);
 /* the same update with lr_t read from device memory (one float) -- the form recorded when a training step is captured into a hipGraph */

@@ -122,6 +122,15 @@ def signature(inputs, targets):
     return (_sig(inputs), _sig(targets))
 
 
+def aliases(targets):
+    """per target the position of the first target that is the same object (part of a trainer's signature while its boundary loss is
+    on: targets that are one object share one static buffer, so the distance map of that buffer is recorded once)"""
+    first, out = {}, []
+    for i, x in enumerate(targets):
+        out.append(first.setdefault(id(x), i) if isinstance(x, (torch.Tensor, np.ndarray)) else i)
+    return tuple(out)
+
+
 class FitGraph(object):
     """the recorded step of one trainer for one call signature"""
 
@@ -170,10 +179,13 @@ class FitGraph(object):
         if self.graph is None:
             self.s_in = [self._static_like(x, dev) for x in inputs]
             self.s_tg = [self._static_like(x, dev) if self._is_tensorlike(x) else x for x in targets]
+            # boundary loss: targets that are one object (part of the signature then, Trainer.fit) share one buffer
+            self.tg_first = aliases(targets) if getattr(t, 'boundary', None) is not None else tuple(range(len(targets)))
+            self.s_tg = [self.s_tg[j] for j in self.tg_first]
         for b, x in zip(self.s_in, inputs):
             self._fill(b, x)
-        for b, x in zip(self.s_tg, targets):
-            if self._is_tensorlike(x):
+        for i, (b, x) in enumerate(zip(self.s_tg, targets)):
+            if self._is_tensorlike(x) and self.tg_first[i] == i:
                 self._fill(b, x)
         for d in self.draws:                          # this step's host draws, in the order the step asks for them
             FitGraph._fill(d.buf, d.fn())

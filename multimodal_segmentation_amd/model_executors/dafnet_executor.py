@@ -196,6 +196,8 @@ class DAFNetExecutor(Executor):
         os.makedirs(self.conf.folder, exist_ok=True)
         es = EarlyStopping('val_loss_mod2_fused', min_delta=0.01, patience=60)
         loss_names = self.get_loss_names()
+        if getattr(self.model, 'boundary', None) is not None:      # conf.w_boundary > 0: the raw boundary term gets a column of its own
+            loss_names = loss_names + ['boundary']
         total_loss = {n: [] for n in loss_names}
         csv_path = self.conf.folder + '/training.csv'
         main = dp.is_main()                    # data parallel: rank 0 writes the csv and the checkpoints
@@ -205,6 +207,7 @@ class DAFNetExecutor(Executor):
         for self.epoch in range(self.conf.epochs):
             log.info('Epoch %d/%d' % (self.epoch, self.conf.epochs))
             epoch_loss = {n: [] for n in loss_names}
+            self.model.set_boundary_epoch(self.epoch)       # the boundary weight of this epoch, before its first batch (nothing when off)
             for self.batch in range(self.batches):
                 self.train_batch(epoch_loss)
             dp.average_state(self._all_models())     # replicas leave the epoch with identical BatchNorm moving statistics
@@ -401,6 +404,8 @@ class DAFNetExecutor(Executor):
         hist = h.history
         g = (lambda k: hist._dev[k]) if self.keep_losses_on_device else (lambda k: hist[k][0])
         epoch_loss['supervised_Mask'].append(g('Segmentor_loss'))
+        if 'boundary' in epoch_loss and 'Segmentor_boundary' in hist:
+            epoch_loss['boundary'].append(g('Segmentor_boundary'))
         epoch_loss['adv_M'].append(g('D_Mask_loss'))
         epoch_loss['rec_X'].append(g('Decoder_loss'))
         epoch_loss['adv_X1'].append(g('D_Image1_loss'))

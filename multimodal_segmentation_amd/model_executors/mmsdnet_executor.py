@@ -148,6 +148,8 @@ class MMSDNetExecutor(DAFNetExecutor):
 
     def _store(self, h, epoch_loss):
         epoch_loss['supervised_Mask'].append(self._loss(h, 'Segmentor_loss'))
+        if 'boundary' in epoch_loss and 'Segmentor_boundary' in h.history:
+            epoch_loss['boundary'].append(self._loss(h, 'Segmentor_boundary'))
         epoch_loss['adv_M'].append(self._loss(h, 'D_Mask_loss'))
         epoch_loss['rec_X'].append(self._loss(h, 'Decoder_loss'))
         epoch_loss['KL'].append(self._loss(h, 'Enc_Modality_loss'))

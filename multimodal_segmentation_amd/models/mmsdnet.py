@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .. import costs, loss_scaler, nn, ops
+from .. import boundary, costs, loss_scaler, nn, ops
 from ..model_components import anatomy_encoder, anatomy_fuser, modality_encoder, segmentor, decoder
 from ..utils.rng import global_rng
 from .basenet import BaseNet
@@ -49,6 +49,7 @@ class MMSDNet(BaseNet):
         """conf.compute_dtype (build-defined key, default 'fp32'): 'bf16' / 'fp16' run the MFMA products of the fast-path
         convolutions on operands rounded to that type with fp32 accumulation (BASELINE configs #3 / #5: reduced-
         precision compute, fp32 master weights, fp32 gradient all-reduce).  Process-wide switch of the kernel library."""
+        boundary.parse_conf(self.conf)                       # conf.w_boundary / boundary_ramp_epochs: refused before anything is built
         ops.set_conv_precision(self.conf.get('compute_dtype', 'fp32'))
         # conf.act_storage (build-defined, default 'fp32'): 'half' keeps the trunk's activations / gradients in HBM in the 16-bit type
         ops.set_activation_storage(self.conf.get('act_storage', 'fp32') == 'half')
@@ -77,6 +78,17 @@ class MMSDNet(BaseNet):
                 t.scaler = loss_scaler.LossScaler(t.optimizer, t.device, *dynamic) if fp16 and dynamic is not None else None
                 # conf.hip_graphs (build-defined, default False): record each trainer step into a hipGraph and replay it (graphs.py)
                 t.use_graph = bool(self.conf.get('hip_graphs', False))
+        # conf.w_boundary > 0 (build-defined, default 0 = off; conf.boundary_ramp_epochs, default 0): every Dice output of the generator
+        # trainers also pays w * L_B, the boundary loss over the distance maps of its target (boundary.py, csrc/boundary.hip); one
+        # device-resident weight for the whole model, set per epoch by set_boundary_epoch
+        bconf = boundary.parse_conf(self.conf)               # (validated whether or not a trainer uses it)
+        self.boundary = None
+        for name in ('supervised_trainer', 'unsupervised_trainer'):
+            t = getattr(self, name, None)
+            if t is not None and bconf is not None and any(s.kind in ('dice_bce', 'dice') for s in t.specs):
+                if self.boundary is None:
+                    self.boundary = boundary.BoundaryWeight(t.device, *bconf)
+                t.boundary = self.boundary
         for m in self._generator_models() + [d for d in (getattr(self, 'D_Mask', None), getattr(self, 'D_Image1', None),
                                                          getattr(self, 'D_Image2', None), getattr(self, 'Balancer', None)) if d is not None]:
             m.precision = getattr(self, '_precision', None)          # `predict` of a component re-enters this wrapper's precision
@@ -87,6 +99,12 @@ class MMSDNet(BaseNet):
         self.build_generators()
         self.apply_loss_scale()
         self.load_models()
+
+    def set_boundary_epoch(self, epoch):
+        """the boundary weight of this epoch (w_boundary * min(1, (epoch + 1) / boundary_ramp_epochs)) into the device scalar the
+        recorded and the eager steps read; called by the executors before the first batch of every epoch.  Nothing when off."""
+        if getattr(self, 'boundary', None) is not None:
+            self.boundary.set_epoch(epoch)
 
     def loss_scalers(self):
         """[(trainer name, LossScaler)] of the dynamic loss scale; empty in every other mode"""

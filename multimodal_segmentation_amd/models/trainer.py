@@ -48,6 +48,10 @@ class Trainer(object):
         # (compute_dtype, 16-bit activation storage) of the model wrapper this trainer belongs to: every fit / predict runs inside
         # ops.precision_scope(self.precision); None = whatever the library is set to
         self.precision = None
+        # conf.w_boundary > 0 (build-defined): the boundary.BoundaryWeight whose device weight the boundary term of every Dice output is
+        # multiplied with (csrc/boundary.hip); None = off, none of those kernels is launched
+        self.boundary = None
+        self._prepared, self._phi = None, None            # per fit: targets by identity -> device tensor -> distance map
 
     # keras API used by the executors ---------------------------------------------------------------------------
     @property
@@ -58,14 +62,16 @@ class Trainer(object):
         print_fn('Trainer %s: %d outputs, trainable models: %s' % (self.name, len(self.specs),
                                                                    ', '.join(m.name for m in self.train_models)))
 
-    def _loss_and_grad(self, spec, pred, target):
+    def _loss_and_grad(self, spec, pred, target, hist=None):
         gs = spec.weight * self.loss_scale            # scale of the returned gradient only; the loss value is unscaled
         sd = self.scaler.scale_dev if self.scaler is not None else None     # dynamic: times the device scale
         if spec.kind == 'dice_bce':
-            return ops.seg_loss(pred, target, self.num_masks, 0.01, gs, class_sum_hook=dp.class_sum_hook(),
-                                n_pix_global=pred.numel() // pred.shape[-1] * dp.world_size(), scale_dev=sd)
+            out = ops.seg_loss(pred, target, self.num_masks, 0.01, gs, class_sum_hook=dp.class_sum_hook(),
+                               n_pix_global=pred.numel() // pred.shape[-1] * dp.world_size(), scale_dev=sd)
+            return out if self.boundary is None else self._add_boundary(spec, pred, target, out, gs, sd, hist)
         if spec.kind == 'dice':
-            return ops.seg_loss(pred, target, self.num_masks, 0.0, gs, scale_dev=sd)
+            out = ops.seg_loss(pred, target, self.num_masks, 0.0, gs, scale_dev=sd)
+            return out if self.boundary is None else self._add_boundary(spec, pred, target, out, gs, sd, hist)
         if spec.kind == 'mse':
             return ops.diff_loss(pred, target, 'mse', gs, scale_dev=sd)
         if spec.kind == 'mae':
@@ -74,9 +80,38 @@ class Trainer(object):
             return ops.diff_loss(pred, 0.0, 'mean', gs, scale_dev=sd)
         raise ValueError(spec.kind)
 
+    def _add_boundary(self, spec, pred, target, out, gs, sd, hist):
+        """the segmentation loss of one output + weight * L_B: the map of the target (built once per distinct target of a fit), the term,
+        its gradient added into what seg_loss wrote, the weighted term added into the loss value; the raw term goes into the History
+        as '<name>_boundary'.  The gradient is normalised by the local element count (the data-parallel all-reduce averages over ranks)
+        and the recorded term is rank-local, as for 'mae' / 'mse'."""
+        loss, dpred = out
+        cache = self._phi if self._phi is not None else {}
+        ent = cache.get(id(target))
+        if ent is None:
+            ent = cache[id(target)] = (target, ops.boundary_map(target, self.num_masks))      # (the target is held: its id stays its own)
+        phi = ent[1]
+        w = self.boundary.weight_dev
+        loss_b = ops.boundary_term(pred, phi, self.num_masks)
+        if dpred is not None:
+            ops.boundary_grad_add(phi, dpred, self.num_masks, gs, w, scale_dev=sd)
+        ops.boundary_combine(loss, loss_b, w)
+        if hist is not None:
+            hist.record(spec.name + '_boundary', loss_b)
+        return loss, dpred
+
     def _prep_target(self, t, pred):
         if isinstance(t, (int, float)):
             return float(t)
+        if self._prepared is not None:                # boundary loss: outputs that share a target object share its device tensor
+            key = (id(t), tuple(pred.shape))
+            ent = self._prepared.get(key)
+            if ent is None:
+                ent = self._prepared[key] = (t, self._prep_tensor(t, pred))
+            return ent[1]
+        return self._prep_tensor(t, pred)
+
+    def _prep_tensor(self, t, pred):
         t = nn.to_device(t, self.device)
         if t.numel() != pred.numel():
             # keras broadcasts e.g. zeros(batch) targets against [batch, 1] outputs
@@ -91,6 +126,8 @@ class Trainer(object):
         with ops.precision_scope(self.precision):
             if self.use_graph and not graph_kw and not dp.enabled() and self.device.type == 'cuda':
                 key = graphs.signature(inputs, targets)
+                if self.boundary is not None:         # which targets are one object: the recording shares their buffer (and their map)
+                    key = key + (graphs.aliases(targets),)
                 st = self._graphs.get(key)
                 if st is None:
                     st = self._graphs[key] = graphs.FitGraph(self)
@@ -109,17 +146,20 @@ class Trainer(object):
         # data parallel: arenas are all-reduced as soon as their last gradient kernel is queued (overlap with backward);
         # models that also receive regulariser gradients after the backward pass are reduced at the end
         tracker = dp.begin(self.train_models, defer=[d for d in self.regularised if d in self.train_models])
+        if self.boundary is not None:
+            self._prepared, self._phi = {}, {}
         with torch.enable_grad():
             outs = self.graph_fn(ins, **graph_kw)
             assert len(outs) == len(self.specs)
             hist = nn.History()
             grads, terms = [], []
             for spec, pred, tgt in zip(self.specs, outs, targets):
-                loss, dpred = self._loss_and_grad(spec, pred, self._prep_target(tgt, pred))
+                loss, dpred = self._loss_and_grad(spec, pred, self._prep_target(tgt, pred), hist)
                 grads.append(dpred)
                 terms.append((spec.weight, loss))
                 hist.record(spec.name + '_loss', loss)
             torch.autograd.backward(outs, grads)
+        self._prepared, self._phi = None, None
         for d in self.regularised:
             kw = {} if self.scaler is None else {'grad_scale_dev': self.scaler.scale_dev}
             for loss in d.regulariser_losses(accumulate_grad=d in self.train_models, grad_scale=self.loss_scale, **kw):

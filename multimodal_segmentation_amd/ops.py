@@ -1375,6 +1375,44 @@ def seg_loss(pred, target, num_masks, lambda_bce, scale, class_sum_hook=None, n_
 
 
 # ------------------------------------------------------------------------------------------------------
+# boundary loss of the segmentor (csrc/boundary.hip; build-defined, conf.w_boundary): no autograd node either
+# ------------------------------------------------------------------------------------------------------
+def boundary_map(target, num_masks):
+    """Signed distance map of the first `num_masks` channels of target [B,H,W,C] (foreground: > 0.5) -> phi [B,H,W,num_masks]:
+    the distance to the nearest foreground pixel outside an organ, -(distance to the nearest background pixel - 1) inside, 0 for an
+    empty or a full mask.  Exact (include/mmseg_hip.h)."""
+    target = _c(target)
+    B, H, W, C = target.shape
+    phi = _new((B, H, W, num_masks), target)
+    ws = _ws('boundary_map', (N.call('mmseg_boundary_workspace_bytes', B, H, W, num_masks) + 3) // 4, target.device, torch.int32)
+    N.call('mmseg_boundary_map', target, phi, ws, B, H, W, C, num_masks)
+    return phi
+
+
+def boundary_term(pred, phi, num_masks):
+    """L_B = mean over (b, pixel, k < num_masks) of pred * phi -> loss_b[1] (a fixed-order two-stage reduction)"""
+    pred, phi = _c(pred), _c(phi)
+    B, H, W, C = pred.shape
+    loss_b = _new((1,), pred)
+    ws = _ws('boundary_loss', N.call('mmseg_boundary_loss_workspace_floats', B), pred.device)
+    N.call('mmseg_boundary_loss', pred, phi, loss_b, ws, B, H * W, C, num_masks)
+    return loss_b
+
+
+def boundary_grad_add(phi, dpred, num_masks, scale, weight_dev, scale_dev=None):
+    """dpred[..., :num_masks] += scale [* scale_dev[0]] * weight_dev[0] * phi / phi.numel(), in place on what seg_loss wrote"""
+    B, H, W, C = dpred.shape
+    N.call('mmseg_boundary_grad_add', _c(phi), dpred, B, H * W, C, num_masks, float(scale), scale_dev, weight_dev)
+    return dpred
+
+
+def boundary_combine(loss, loss_b, weight_dev):
+    """loss[0] += weight_dev[0] * loss_b[0] on the device (loss_b keeps the raw term)"""
+    N.call('mmseg_boundary_combine', loss, loss_b, weight_dev)
+    return loss
+
+
+# ------------------------------------------------------------------------------------------------------
 # in-graph per-sample loss terms of the automated-pairing trainers (csrc/pairloss.hip)
 # ------------------------------------------------------------------------------------------------------
 class _OverlapDice(torch.autograd.Function):
