@@ -529,6 +529,32 @@ int mmseg_preprocess_image(const float* img, const float* ws, float* out, int S,
 int mmseg_preprocess_label(const unsigned char* lab, const int* values, float* out, int S, int H, int W, int RH, int RW, int OH, int OW,
                            int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch0, int K, void* stream);
 
+/* ---- percentile-window and landmark intensity normalisation (csrc/preprocess.hip; build-defined, the reference rescales by min / max) --
+ * Population of a (volume, modality): the values the bilinear resampling above produces over the WHOLE RH x RW frame of every
+ * slice, the zeros of the strict border rule included -- what mmseg_preprocess_minmax visits.  A segment is one slice (per_volume
+ * = 0: G = S segments of N = RH * RW values) or the volume (per_volume = 1: G = 1, N = S * RH * RW); N >= 2^31 is refused.
+ * Knots: for percentiles q_0 < ... < q_{K-1} in [0, 100], 2 <= K <= 16, knot x_k of a segment is its order statistic of rank
+ * r_k = floor((N - 1) * (q_k / 100)), computed by the CALLER in fp64 in that order (numpy's method='lower'); the device is given
+ * ranks, 0 <= r_k <= N - 1, never percentiles.  The selected value is an element of the population bit for bit (the order is IEEE
+ * totalOrder: -0 below +0); nothing is interpolated between ranks.
+ * Map of a resampled value v through its segment's knots x and the targets y [K] (non-decreasing, y_0 < y_{K-1}), in fp32 without
+ * contraction: v <= x_0 -> y_0 exactly; v >= x_{K-1} -> y_{K-1} exactly; otherwise, with k the largest index that has x_k < v (so
+ * x_k < v <= x_{k+1} and the denominator is positive), fminf(y_k + (v - x_k) * ((y_{k+1} - y_k) / (x_{k+1} - x_k)), y_{k+1}).
+ * Equal knots need no special case; a constant segment gives y_0 everywhere.
+ * Bytes of the workspace of one mmseg_preprocess_quantiles call (per segment K prefixes and K ranks, and four histograms
+ * [G][K][256] of uint32); 0 for S < 1 or K outside 2..16 */
+long mmseg_preprocess_quantiles_workspace_bytes(int S, int K, int per_volume);
+/* x [G,K] fp32 = the knots of every segment of img [S,H,W]; ranks [K] int32 on the device, the same for every segment.  Radix select
+ * on the order-preserving key of an fp32 value, four passes of 8-bit digits, each recomputing the resampling; integer atomics only,
+ * so two runs are bitwise equal.  ws is zeroed here, on the stream. */
+int mmseg_preprocess_quantiles(const float* img, const int* ranks, int* ws, float* x, int S, int H, int W, int RH, int RW, int K,
+                               int per_volume, void* stream);
+/* mmseg_preprocess_image with the map above in place of the min / max rescale: out [S,OH,OW,C], channel ch; slice s uses row
+ * (per_volume ? 0 : s) of x [G,K]; y [K] fp32 on the device */
+int mmseg_preprocess_image_map(const float* img, const float* x, const float* y, float* out, int S, int H, int W, int RH, int RW, int OH,
+                               int OW, int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch, int K,
+                               int per_volume, void* stream);
+
 /* ---- predicted label volumes on a volume's own grid (csrc/postprocess.hip; build-defined, the reference writes no segmentation) ----
  * mmseg_restore_label inverts the geometry of mmseg_preprocess_label and binarises in the same pass: prob [S,OH,OW,C] (the
  * segmentor's output, the K <= 16 organ channels first, K <= C) -> out [S,H,W] uint8 grey values, every byte written.  Per axis the

@@ -211,3 +211,183 @@ int mmseg_preprocess_label(const unsigned char* lab, const int* values, float* o
 }
 
 }  // extern "C"
+
+// ---- percentile-window and landmark normalisation (build-defined; the definition is in include/mmseg_hip.h) -------------------------
+// Instead of the (min, max) of a slice, K order statistics ("knots") of a segment -- one resampled slice, or all resampled slices of
+// the volume -- and a clamped piecewise-linear map through them.  Selection is a radix select on the order-preserving 32-bit key of
+// an fp32 value, most significant 8-bit digit first: pq_hist_kernel recomputes pp_bilinear over the resampled frame (the frame still
+// never exists in memory: one read of the raw slices per pass, four passes, a fifth read by the map), counts per rank the digit of
+// every value whose higher digits equal that rank's prefix in LDS histograms [K][256] and adds its non-empty bins to the segment's
+// global histogram with integer atomics (order independent: bitwise reproducible); pq_pick_kernel, one block per segment, scans the
+// K histograms, extends the K prefixes and reduces the K ranks.  After the fourth pass a prefix is the key of the selected value,
+// an element of the population bit for bit, which pp_image_map_kernel meets again because it calls the same pp_bilinear.
+// The grid stays (blocks, S) in both scopes: with one segment per volume the blocks of every slice add to segment 0, which fills the
+// device better than 64 blocks for a whole volume would.  No block waits for another; every loop is bounded by the frame or by K.
+#define PQ_MAXKNOTS 16
+#define PQ_BINS 256
+#define PQ_PASSES 4
+
+// workspace of one call, in 32-bit words: per segment prefix [K] and remaining rank [K], then per pass and segment hist [K][256]
+static long pq_state_words(int G, int K) { return 2L * G * K; }
+static long pq_hist_words(int G, int K) { return (long)G * K * PQ_BINS; }
+
+// monotone in the value: negative values have all bits flipped, the others get the sign bit (-0 sorts directly below +0)
+__device__ __forceinline__ unsigned pq_key(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float pq_value(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+// grid (nblk, S), block PP_BLOCK: hist[g][j][digit `pass` of key] += 1 for every resampled pixel of slice s whose higher digits equal
+// prefix[g][j]; g = per_volume ? 0 : s.  state / hist: this call's, hist of this pass
+__global__ void __launch_bounds__(PP_BLOCK) pq_hist_kernel(const float* __restrict__ img, const unsigned* __restrict__ state,
+                                                           unsigned* __restrict__ hist, int K, int per_volume, int pass, int H, int W,
+                                                           int RH, int RW, double ry, double rx) {
+    __shared__ unsigned lh[PQ_MAXKNOTS][PQ_BINS];
+    __shared__ unsigned pfx[PQ_MAXKNOTS];
+    const int s = blockIdx.y, g = per_volume ? 0 : s;
+    const int shift = 32 - 8 * (pass + 1);
+    for (int j = 0; j < K; ++j) lh[j][threadIdx.x] = 0u;
+    if (threadIdx.x < K) pfx[threadIdx.x] = pass ? state[(size_t)g * 2 * K + threadIdx.x] >> (shift + 8) : 0u;   // pass 0: all match
+    __syncthreads();
+    const float* src = img + (size_t)s * H * W;
+    const int n = RH * RW;
+    for (int e = blockIdx.x * PP_BLOCK + threadIdx.x; e < n; e += gridDim.x * PP_BLOCK) {
+        const int dr = e / RW, dc = e - dr * RW;
+        const unsigned key = pq_key(pp_bilinear(src, H, W, dr, dc, ry, rx));
+        const unsigned d = (key >> shift) & (PQ_BINS - 1), hb = pass ? key >> (shift + 8) : 0u;
+        for (int j = 0; j < K; ++j)
+            if (hb == pfx[j]) atomicAdd(&lh[j][d], 1u);
+    }
+    __syncthreads();
+    unsigned* gh = hist + (size_t)g * K * PQ_BINS;
+    for (int j = 0; j < K; ++j) {
+        const unsigned c = lh[j][threadIdx.x];
+        if (c) atomicAdd(gh + j * PQ_BINS + threadIdx.x, c);
+    }
+}
+
+// grid G, block PP_BLOCK: per rank j the bin of this pass's histogram that holds the (remaining) rank extends prefix[g][j] and the
+// rank is reduced by the count below that bin.  Pass 0 starts from `ranks`; the last pass writes the knots x[g][j].
+__global__ void __launch_bounds__(PP_BLOCK) pq_pick_kernel(unsigned* __restrict__ state, const unsigned* __restrict__ hist,
+                                                           const int* __restrict__ ranks, float* __restrict__ x, int K, int pass) {
+    __shared__ unsigned lh[PQ_MAXKNOTS][PQ_BINS];
+    const int g = blockIdx.x;
+    const unsigned* gh = hist + (size_t)g * K * PQ_BINS;
+    for (int j = 0; j < K; ++j) lh[j][threadIdx.x] = gh[j * PQ_BINS + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x >= K) return;
+    const int j = threadIdx.x;
+    unsigned* prefix = state + (size_t)g * 2 * K;
+    unsigned* rank = prefix + K;
+    unsigned r = pass ? rank[j] : (unsigned)ranks[j];
+    unsigned p = pass ? prefix[j] : 0u;
+    unsigned below = 0u;
+    for (int b = 0; b < PQ_BINS; ++b) {
+        const unsigned c = lh[j][b];
+        if (r < below + c) {          // true for exactly one b when 0 <= rank < N
+            p |= (unsigned)b << (32 - 8 * (pass + 1));
+            r -= below;
+            break;
+        }
+        below += c;
+    }
+    prefix[j] = p;
+    rank[j] = r;
+    if (pass == PQ_PASSES - 1) x[(size_t)g * K + j] = pq_value(p);
+}
+
+// pp_image_kernel with the map through the knots in place of the rescale: xs [G][K] from pq_pick_kernel (row per_volume ? 0 : s),
+// ys [K] the targets.  v <= x_0 -> y_0, v >= x_{K-1} -> y_{K-1}, else with the largest k that has x_k < v:
+// min(y_k + (v - x_k) * ((y_{k+1} - y_k) / (x_{k+1} - x_k)), y_{k+1}); x_{k+1} >= v > x_k, so the denominator is positive
+__global__ void __launch_bounds__(PP_BLOCK) pp_image_map_kernel(const float* __restrict__ img, const float* __restrict__ xs,
+                                                                const float* __restrict__ ys, int K, int per_volume,
+                                                                float* __restrict__ out, int H, int W, double ry, double rx, int OH,
+                                                                int OW, pp_axis ar, pp_axis ac, int C, int ch) {
+#pragma clang fp contract(off)
+    __shared__ float kx[PQ_MAXKNOTS], ky[PQ_MAXKNOTS], slope[PQ_MAXKNOTS];
+    const int s = blockIdx.y;
+    if (threadIdx.x < K) {
+        const float* row = xs + (size_t)(per_volume ? 0 : s) * K;
+        kx[threadIdx.x] = row[threadIdx.x];
+        ky[threadIdx.x] = ys[threadIdx.x];
+        if (threadIdx.x < K - 1) {
+            const float dx = row[threadIdx.x + 1] - row[threadIdx.x];
+            slope[threadIdx.x] = dx > 0.f ? (ys[threadIdx.x + 1] - ys[threadIdx.x]) / dx : 0.f;          // equal knots: never selected
+        }
+    }
+    __syncthreads();
+    const float x0 = kx[0], xl = kx[K - 1], y0 = ky[0], yl = ky[K - 1];
+    const float* src = img + (size_t)s * H * W;
+    float* dst = out + (size_t)s * OH * OW * C + ch;
+    const int n = OH * OW;
+    for (int e = blockIdx.x * PP_BLOCK + threadIdx.x; e < n; e += gridDim.x * PP_BLOCK) {
+        const int r = e / OW, c = e - r * OW;
+        const int dr = ar.lo + min(max(r - ar.before, 0), ar.kept - 1);
+        const int dc = ac.lo + min(max(c - ac.before, 0), ac.kept - 1);
+        const float v = pp_bilinear(src, H, W, dr, dc, ry, rx);
+        float o;
+        if (v <= x0) o = y0;
+        else if (v >= xl) o = yl;
+        else {
+            int k = K - 2;
+            while (k > 0 && !(kx[k] < v)) --k;
+            o = fminf(ky[k] + (v - kx[k]) * slope[k], ky[k + 1]);
+        }
+        dst[(size_t)e * C] = o;
+    }
+}
+
+static bool pq_ok(int S, int RH, int RW, int K, int per_volume) {
+    return K >= 2 && K <= PQ_MAXKNOTS && (per_volume ? (long)S : 1L) * RH * RW < 0x80000000L;
+}
+
+extern "C" {
+
+// bytes of the state and the four histograms of one mmseg_preprocess_quantiles call
+long mmseg_preprocess_quantiles_workspace_bytes(int S, int K, int per_volume) {
+    if (S < 1 || K < 2 || K > PQ_MAXKNOTS) return 0;
+    const int G = per_volume ? 1 : S;
+    return 4L * (pq_state_words(G, K) + PQ_PASSES * pq_hist_words(G, K));
+}
+
+// img [S,H,W] raw slices, ranks [K] int32 (device), ws: mmseg_preprocess_quantiles_workspace_bytes(S, K, per_volume) bytes, zeroed
+// here on the stream -> x [G,K]
+int mmseg_preprocess_quantiles(const float* img, const int* ranks, int* ws, float* x, int S, int H, int W, int RH, int RW, int K,
+                               int per_volume, void* stream) {
+    if (S <= 0) return 0;
+    if (!img || !ranks || !ws || !x || !pp_geometry_ok(S, H, W, RH, RW) || !pq_ok(S, RH, RW, K, per_volume)) return (int)hipErrorInvalidValue;
+    const int G = per_volume ? 1 : S;
+    const hipError_t zeroed = hipMemsetAsync(ws, 0, (size_t)mmseg_preprocess_quantiles_workspace_bytes(S, K, per_volume), (hipStream_t)stream);
+    if (zeroed != hipSuccess) return (int)zeroed;
+    unsigned* state = reinterpret_cast<unsigned*>(ws);
+    unsigned* hist = state + pq_state_words(G, K);
+    const dim3 grid((unsigned)pp_blocks((long)RH * RW), S);
+    for (int pass = 0; pass < PQ_PASSES; ++pass, hist += pq_hist_words(G, K)) {
+        hipLaunchKernelGGL(pq_hist_kernel, grid, dim3(PP_BLOCK), 0, (hipStream_t)stream, img, state, hist, K, per_volume ? 1 : 0, pass, H, W,
+                           RH, RW, (double)H / (double)RH, (double)W / (double)RW);
+        hipLaunchKernelGGL(pq_pick_kernel, dim3(G), dim3(PP_BLOCK), 0, (hipStream_t)stream, state, hist, ranks, x, K, pass);
+    }
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// out [S,OH,OW,C]: channel ch is written, as by mmseg_preprocess_image; x [G,K] from mmseg_preprocess_quantiles, y [K] (device)
+int mmseg_preprocess_image_map(const float* img, const float* x, const float* y, float* out, int S, int H, int W, int RH, int RW, int OH,
+                               int OW, int lo_r, int kept_r, int before_r, int lo_c, int kept_c, int before_c, int C, int ch, int K,
+                               int per_volume, void* stream) {
+    if (S <= 0) return 0;
+    if (!img || !x || !y || !out || !pp_geometry_ok(S, H, W, RH, RW) || !pq_ok(S, RH, RW, K, per_volume) || OH < 1 || OW < 1 ||
+        (long)OH * OW >= 0x7fffffffL - PP_MAXBLK * PP_BLOCK || C < 1 || ch < 0 || ch >= C || !pp_axis_ok(lo_r, kept_r, before_r, RH, OH) ||
+        !pp_axis_ok(lo_c, kept_c, before_c, RW, OW))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)pp_blocks((long)OH * OW), S);
+    const pp_axis ar = {lo_r, kept_r, before_r}, ac = {lo_c, kept_c, before_c};
+    hipLaunchKernelGGL(pp_image_map_kernel, grid, dim3(PP_BLOCK), 0, (hipStream_t)stream, img, x, y, K, per_volume ? 1 : 0, out, H, W,
+                       (double)H / (double)RH, (double)W / (double)RW, OH, OW, ar, ac, C, ch);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+}  // extern "C"

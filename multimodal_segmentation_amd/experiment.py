@@ -3,6 +3,7 @@
     python experiment.py --config <module in configuration/> --split <int> [--l_mix f] [--test b]
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
                          [--data_folder PATH] [--test_data_folder PATH]
+                         [--intensity_norm minmax|window] [--intensity_scope slice|volume] [--intensity_percentiles LO,HI]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
@@ -11,8 +12,9 @@
                          [--predict_tiles true|false] [--predict_tile_overlap PIXELS] [--predict_tta LIST]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
-every configuration trains and tests on the synthetic volumes.  `--predict_folder` (build-defined) names a folder of exported volumes,
-labelled or not, for which the checkpoint of the run folder writes label volumes on each volume's own grid (volume_predictor.py): after
+every configuration trains and tests on the synthetic volumes.  `--intensity_norm` and its two companions (build-defined, like
+`conf.intensity`) override the `intensity` block of every folder of the run (loaders.intensity_conf).  `--predict_folder`
+(build-defined) names a folder of exported volumes, labelled or not, for which the checkpoint of the run folder writes label volumes on each volume's own grid (volume_predictor.py): after
 the test pass, or instead of training with `--test`.
 
 The run folder name and the config mutations follow Experiment.get_config (experiment.py:31-72):
@@ -58,6 +60,12 @@ def parse_arguments(argv=None):
     ap.add_argument('--randomise', type=bool, help='randomise the multimodal pairs')
     ap.add_argument('--data_folder', help='folder of exported volumes (dataset.json + .npz) to train, validate and test on')
     ap.add_argument('--test_data_folder', help='another folder of exported volumes for the test pass')
+    ap.add_argument('--intensity_norm', choices=['minmax', 'window'],
+                    help='intensity normalisation of every volume folder of the run, instead of what their dataset.json say: every '
+                         'slice by its extremes / clipped to a percentile window')
+    ap.add_argument('--intensity_scope', choices=['slice', 'volume'], help='the window of --intensity_norm window is taken per slice / '
+                                                                           'per volume (default: volume)')
+    ap.add_argument('--intensity_percentiles', metavar='LO,HI', help='the window of --intensity_norm window (default: 0.5,99.5)')
     ap.add_argument('--predict_folder', help='folder of exported volumes (labels optional) to write predicted label volumes for')
     ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
     ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
@@ -94,6 +102,13 @@ def parse_arguments(argv=None):
                          'id,fliplr,flipud,rot180 (= flips), d4 (the eight flips and right-angle turns) or id,rot10,rot-10 (degrees); '
                          'the first view is id')
     args = ap.parse_args(argv)
+    if (args.intensity_scope or args.intensity_percentiles) and args.intensity_norm != 'window':
+        ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
+    if args.intensity_percentiles is not None:
+        try:
+            args.intensity_percentiles = [float(v) for v in args.intensity_percentiles.split(',')]
+        except ValueError:
+            ap.error('--intensity_percentiles must be two numbers LO,HI, got %r' % args.intensity_percentiles)
     if args.predict_tile_overlap is not None and args.predict_tile_overlap < 0:
         ap.error('--predict_tile_overlap must be a number of pixels >= 0, got %r' % args.predict_tile_overlap)
     if not 0.0 <= args.predict_percentile <= 100.0:          # here, so that a bad value stops the run before the model is built
@@ -178,6 +193,49 @@ def register_data_folders(module, args):
     return own_name
 
 
+def intensity_override(named, args):
+    """the `intensity` block of `--intensity_norm` / `--intensity_scope` / `--intensity_percentiles`, else the configuration's
+    `intensity`, else None: no override, every folder follows its own dataset.json.  Landmarks are configured in dataset.json only."""
+    from .loaders.volume_folder import check_intensity
+    block, where = named.get('intensity'), 'conf.intensity'
+    if getattr(args, 'intensity_norm', None):
+        block, where = {'mode': args.intensity_norm}, '--intensity_norm'
+        if getattr(args, 'intensity_scope', None):
+            block['scope'] = args.intensity_scope
+        if getattr(args, 'intensity_percentiles', None):
+            block['percentiles'] = list(args.intensity_percentiles)
+    if block is None:
+        return None
+    if isinstance(block, dict) and block.get('mode') == 'landmarks':
+        raise ValueError('%s: landmarks are configured in the dataset.json of a folder (tools/fit_intensity_landmarks.py), not as an '
+                         'override' % where)
+    return check_intensity(dict(block), (), where)
+
+
+def register_intensity(named, args, names):
+    """Fill loaders.intensity_conf for the data set names of this run; without an override their entries are removed"""
+    from .loaders import intensity_conf
+    block = intensity_override(named, args)
+    for name in names:
+        if block is None:
+            intensity_conf.pop(name, None)
+        else:
+            intensity_conf[name] = dict(block)
+    return block
+
+
+def warn_predict_intensity(conf, folder, log):
+    """a warning when the intensity setting in force for the predict folder differs from the one the run folder records (conf.intensity;
+    a run on the synthetic volumes records none: min / max).  True when it warned."""
+    from .loaders.volume_folder import effective_intensity
+    trained, here = conf.get('intensity') or {'mode': 'minmax'}, effective_intensity(folder)
+    if here == trained:
+        return False
+    log.warning('--predict_folder: %s is normalised by %s, the run folder %s records %s: the model sees other grey levels than it was '
+                'trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
+    return True
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
@@ -190,8 +248,15 @@ class Experiment(object):
         if test_dataset is not None:
             conf.test_dataset = test_dataset
         from .loaders import data_conf
+        names = set(data_conf)
+        if getattr(args, 'predict_folder', None):
+            from .loaders.volume_folder import read_manifest
+            names.add(read_manifest(args.predict_folder)['name'])
+        register_intensity(conf, args, sorted(names))      # before a loader that loads volumes is built: it reads its setting then
         if data_conf.get(conf.dataset_name):
             conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
+            from .loaders.volume_folder import effective_intensity
+            conf.intensity = effective_intensity(conf.data_folder)  # the setting in force, override or dataset.json: recorded too
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')
@@ -257,6 +322,7 @@ class Experiment(object):
             raise FileNotFoundError('--predict_folder: the run folder %s holds no checkpoint to predict with (train first, without '
                                     '--test)' % conf.folder)
         if dp.is_main():
+            warn_predict_intensity(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()

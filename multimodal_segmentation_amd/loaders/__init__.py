@@ -3,6 +3,12 @@
 `data_conf` mirrors the dict of the same name in the reference's loaders/base_loader.py:5-7: data set name -> folder that holds
 it.  It starts empty, so every configuration trains on the synthetic volumes; `experiment.py --data_folder PATH` (or
 `conf.data_folder`) registers a folder in the format of loaders/volume_folder.py under the configured data set name, and
-`loader_factory.init_loader(name)` then returns a loader that reads it."""
+`loader_factory.init_loader(name)` then returns a loader that reads it.
+
+`intensity_conf` (build-defined) sits beside it and is keyed like it: data set name -> an `intensity` block in the form of
+dataset.json's that overrides the block of the folder registered under that name (or of the folder whose dataset.json carries that
+name).  `experiment.py --intensity_norm ...` (or `conf.intensity`) fills it for every folder of a run; it starts empty, so each
+folder is normalised as its own dataset.json says."""
 
 data_conf = {}
+intensity_conf = {}

@@ -19,6 +19,15 @@ slices.  S, H, W and the resolution may differ between volumes and between modal
 Per (volume, modality) the raw slices are uploaded once through pinned memory and three launches write the volume's share of the
 NHWC containers [N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map).
 
+`intensity` (optional key of dataset.json; build-defined) chooses how grey values reach [-1, 1].  Absent or {"mode": "minmax"}: every
+slice by the extremes of its resampled frame, the reference's rule and the three launches above.  {"mode": "window", "scope":
+"volume" | "slice", "percentiles": [lo, hi]} (defaults "volume", [0.5, 99.5]): clip to the two percentiles of the volume's (or the
+slice's) resampled values and rescale.  {"mode": "landmarks", "percentiles": [...], "standard": {"<modality>": [y_0 .. y_K-1]}}
+(default percentiles 1, 10, 20 .. 90, 99; per volume): Nyul and Udupa's standardisation, the volume's own landmarks mapped piecewise
+linearly onto the scale that tools/fit_intensity_landmarks.py learned from the training volumes.  The percentiles are exact order
+statistics selected on the device (ops.preprocess_quantiles, once per uploaded volume and modality: `intensity_knots`); the
+definition is in include/mmseg_hip.h.  loaders.intensity_conf overrides the key for a run (experiment.py --intensity_norm).
+
 For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
 frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
 import json
@@ -123,6 +132,87 @@ def has_data(name):
     return bool(name) and bool(data_conf.get(name))
 
 
+INTENSITY_MODES = ('minmax', 'window', 'landmarks')
+INTENSITY_SCOPES = ('volume', 'slice')
+WINDOW_PERCENTILES = (0.5, 99.5)                                        # nnU-Net's clip
+LANDMARK_PERCENTILES = (1, 10, 20, 30, 40, 50, 60, 70, 80, 90, 99)      # Nyul and Udupa's deciles between the 1st and 99th
+MAX_KNOTS = ops.PREPROCESS_MAX_KNOTS
+
+
+def quantile_ranks(n, percentiles):
+    """rank floor((n - 1) * (q / 100)) of every percentile q among n values, in fp64 in that order: numpy's method='lower'"""
+    return [int(np.floor((int(n) - 1) * (float(q) / 100.0))) for q in percentiles]
+
+
+def check_intensity(block, modalities, where):
+    """The normalised form of an `intensity` block (dataset.json, conf.intensity): {'mode': 'minmax'}, or mode, scope and percentiles
+    for 'window', and additionally `standard` {modality: [y_0 .. y_{K-1}]} for 'landmarks'.  None and {} mean 'minmax'."""
+    if block is None:
+        return {'mode': 'minmax'}
+    if not isinstance(block, dict):
+        raise ValueError('%s: "intensity" must be an object, got %r' % (where, block))
+    mode = block.get('mode', 'minmax')
+    if mode not in INTENSITY_MODES:
+        raise ValueError('%s: "intensity" mode must be one of %s, got %r' % (where, ', '.join(INTENSITY_MODES), mode))
+    unknown = sorted(set(block) - {'mode', 'scope', 'percentiles', 'standard'})
+    if unknown:
+        raise ValueError('%s: "intensity" has unknown key(s) %s' % (where, ', '.join(unknown)))
+    if mode == 'minmax':
+        if set(block) - {'mode'}:
+            raise ValueError('%s: "intensity" mode minmax takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
+        return {'mode': 'minmax'}
+    scope = block.get('scope', 'volume')
+    if scope not in INTENSITY_SCOPES:
+        raise ValueError('%s: "intensity" scope must be one of %s, got %r' % (where, ', '.join(INTENSITY_SCOPES), scope))
+    q = block.get('percentiles', WINDOW_PERCENTILES if mode == 'window' else LANDMARK_PERCENTILES)
+    if (not isinstance(q, (list, tuple)) or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in q)
+            or any(not np.isfinite(v) or not 0 <= v <= 100 for v in q)):
+        raise ValueError('%s: "intensity" percentiles must be a list of numbers in [0, 100], got %r' % (where, q))
+    if mode == 'window' and len(q) != 2:
+        raise ValueError('%s: "intensity" mode window takes two percentiles [lo, hi], got %r' % (where, q))
+    if not 2 <= len(q) <= MAX_KNOTS:
+        raise ValueError('%s: "intensity" takes 2..%d percentiles, got %d' % (where, MAX_KNOTS, len(q)))
+    if any(b <= a for a, b in zip(q[:-1], q[1:])):
+        raise ValueError('%s: "intensity" percentiles must increase strictly, got %r' % (where, q))
+    out = {'mode': mode, 'scope': scope, 'percentiles': [float(v) for v in q]}
+    if mode == 'window':
+        if 'standard' in block:
+            raise ValueError('%s: "intensity" mode window takes no "standard" scale (its targets are -1 and 1)' % where)
+        return out
+    if scope != 'volume':
+        raise ValueError('%s: "intensity" mode landmarks works per volume; scope %r is not available' % (where, scope))
+    std = block.get('standard')
+    if not isinstance(std, dict):
+        raise ValueError('%s: "intensity" mode landmarks needs "standard": {modality: scale} (tools/fit_intensity_landmarks.py '
+                         'writes it)' % where)
+    out['standard'] = {}
+    for mod in modalities:
+        y = std.get(mod)
+        if not isinstance(y, (list, tuple)) or len(y) != len(q):
+            raise ValueError('%s: "intensity" standard scale of modality %r must hold %d values, one per percentile, got %r'
+                             % (where, mod, len(q), y))
+        y = [float(v) for v in y]
+        if y[0] != -1.0 or y[-1] != 1.0:
+            raise ValueError('%s: "intensity" standard scale of modality %r must begin with -1 and end with 1, got %r' % (where, mod, y))
+        if any(b < a for a, b in zip(y[:-1], y[1:])):
+            raise ValueError('%s: "intensity" standard scale of modality %r must not decrease, got %r' % (where, mod, y))
+        out['standard'][mod] = y
+    return out
+
+
+def effective_intensity(root, manifest=None):
+    """the normalised intensity setting of the folder `root`: the override registered in loaders.intensity_conf under a data set name
+    that loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
+    from . import data_conf, intensity_conf
+    m = read_manifest(root) if manifest is None else manifest
+    here = os.path.abspath(root)
+    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
+    for n in names:
+        if intensity_conf.get(n) is not None:
+            return check_intensity(intensity_conf[n], m['modalities'], 'loaders.intensity_conf[%r]' % n)
+    return check_intensity(m.get('intensity'), m['modalities'], os.path.join(root, MANIFEST))
+
+
 def read_manifest(root):
     path = os.path.join(root, MANIFEST)
     if not os.path.isfile(path):
@@ -153,6 +243,7 @@ def read_manifest(root):
         for mod in m['modalities']:
             if mod not in entry or 'file' not in entry[mod]:
                 raise ValueError('%s: volume %s has no file for modality %r' % (path, v, mod))
+    check_intensity(m.get('intensity'), m['modalities'], path)
     return m
 
 
@@ -170,6 +261,7 @@ class VolumeFolderLoader(object):
         self.num_volumes = len(self.volumes)
         self.processed_folder = None
         self.log = log
+        self.intensity = effective_intensity(root, m)          # build-defined: {'mode': 'minmax'} is the reference's rescale
 
     # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
     def splits(self):
@@ -236,6 +328,21 @@ class VolumeFolderLoader(object):
             raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
         return (RH, RW), crop_pad_map(RH, self.input_shape[0]), crop_pad_map(RW, self.input_shape[1])
 
+    def intensity_knots(self, x, resampled, modality):
+        """The normalisation of one (volume, modality) whose raw slices x [S,H,W] are on the device: None for 'minmax' (the kernels
+        rescale every slice by its extremes), else (knots [G,K], targets [K]) for ops.preprocess_images / preprocess_volume -- the
+        ranks of the configured percentiles among the resampled values of a slice or of the volume, and their order statistics,
+        selected on the device (ops.preprocess_quantiles).  The one place where this is decided: training, validation, testing,
+        prediction and tiles call it once per uploaded (volume, modality)."""
+        setting = self.intensity
+        if setting['mode'] == 'minmax':
+            return None
+        per_volume = setting['scope'] == 'volume'
+        n = (x.shape[0] if per_volume else 1) * int(resampled[0]) * int(resampled[1])
+        knots = ops.preprocess_quantiles(x, resampled, quantile_ranks(n, setting['percentiles']), per_volume)
+        y = setting['standard'][modality] if setting['mode'] == 'landmarks' else (-1.0, 1.0)
+        return knots, nn.host_to_device(np.asarray(y), x.device, np.float32)
+
     def load_volume_for_prediction(self, volume):
         """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
         [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
@@ -252,7 +359,8 @@ class VolumeFolderLoader(object):
                 selected = np.arange(S_file)
             resampled, rows, cols = self.geometry(H, W, res)
             container = torch.zeros((len(selected), OH, OW, 1), dtype=torch.float32, device=device)
-            ops.preprocess_images(nn.host_to_device(image[selected], device, np.float32), container, resampled, rows, cols, 0)
+            x = nn.host_to_device(image[selected], device, np.float32)
+            ops.preprocess_images(x, container, resampled, rows, cols, 0, knots=self.intensity_knots(x, resampled, mod))
             images.append(container)
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
@@ -268,7 +376,8 @@ class VolumeFolderLoader(object):
 
     def upload_volume(self, volume):
         """(raw, geometry) of one volume: per modality the selected raw slices [S,H,W] fp32 on the device, uploaded once, and the
-        record of load_volume_for_prediction.  What load_volume_tiles builds its containers from, for every predicted modality."""
+        record of load_volume_for_prediction plus `knots`: intensity_knots' result, selected once here and shared by every tile.
+        What load_volume_tiles builds its containers from, for every predicted modality."""
         device = nn.default_device()
         raw, geometry = [], []
         for mod in self.modalities:
@@ -280,7 +389,8 @@ class VolumeFolderLoader(object):
             raw.append(nn.host_to_device(image[selected], device, np.float32))
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
-                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
+                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing,
+                                 knots=self.intensity_knots(raw[-1], resampled, mod)))
         self._same_counts(volume, [x.shape[0] for x in raw])
         return raw, geometry
 
@@ -309,7 +419,7 @@ class VolumeFolderLoader(object):
             for tr, r in enumerate(rows):
                 for tc, c in enumerate(cols):
                     t = tr * len(cols) + tc
-                    ops.preprocess_images(x, container[t * S:(t + 1) * S], geo['resampled'], r, c, 0)
+                    ops.preprocess_images(x, container[t * S:(t + 1) * S], geo['resampled'], r, c, 0, knots=geo.get('knots'))
             images.append(container)
         return images, geometry, plan
 
@@ -347,9 +457,10 @@ class VolumeFolderLoader(object):
                 RW = resampled_size(W, res[1], self.target_resolution[1])
                 if RH < 1 or RW < 1:
                     raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
-                ops.preprocess_volume(nn.host_to_device(image, device, np.float32), nn.host_to_device(label, device, np.uint8),
-                                      values, images[n0:n0 + S], masks[n0:n0 + S], (RH, RW), crop_pad_map(RH, OH),
-                                      crop_pad_map(RW, OW), mod)
+                x = nn.host_to_device(image, device, np.float32)
+                ops.preprocess_volume(x, nn.host_to_device(label, device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
+                                      (RH, RW), crop_pad_map(RH, OH), crop_pad_map(RW, OW), mod,
+                                      knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))
             n0 += S
         assert n0 == n
         return nn.to_numpy(images), nn.to_numpy(masks)

@@ -1812,12 +1812,13 @@ def intensity_apply(x, params, stats, field, seed, batch, array):
     return x
 
 
-def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod):
+def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod, knots=None):
     """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
     (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,
     rescale every slice to [-1, 1] by the extremes of its whole resampled frame, crop / pad with the per-axis index maps
-    rows / cols = (lo, kept, before).  img [S,H,W] fp32, lab [S,H,W] uint8, values int32, all on the device of `images`.  No
-    gradient (input pipeline)."""
+    rows / cols = (lo, kept, before).  img [S,H,W] fp32, lab [S,H,W] uint8, values int32, all on the device of `images`.  With
+    knots = (x [G,K], y [K]) (preprocess_quantiles; build-defined) the rescale is the clamped piecewise-linear map through the
+    knots instead, one launch in place of two; G = S: a row per slice, G = 1: one row for the volume.  No gradient (input pipeline)."""
     S, H, W = img.shape
     RH, RW = int(resampled[0]), int(resampled[1])
     K = int(values.numel())
@@ -1827,13 +1828,16 @@ def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mo
         raise ValueError('preprocess_volume: img %s %s, lab %s %s, images %s, masks %s, K = %d, modality %d'
                          % (tuple(img.shape), img.dtype, tuple(lab.shape), lab.dtype, tuple(images.shape), tuple(masks.shape), K, mod))
     geo = [int(v) for v in tuple(rows) + tuple(cols)]
-    ws = _ws('preprocess', N.call('mmseg_preprocess_workspace_floats', S, RH, RW), images.device)
-    N.call('mmseg_preprocess_minmax', _c(img), ws, S, H, W, RH, RW)
-    N.call('mmseg_preprocess_image', _c(img), ws, images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod]))
+    if knots is None:
+        ws = _ws('preprocess', N.call('mmseg_preprocess_workspace_floats', S, RH, RW), images.device)
+        N.call('mmseg_preprocess_minmax', _c(img), ws, S, H, W, RH, RW)
+        N.call('mmseg_preprocess_image', _c(img), ws, images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod]))
+    else:
+        _image_map(img, images, knots, S, H, W, RH, RW, OH, OW, geo, M, mod)
     N.call('mmseg_preprocess_label', _c(lab), values, masks, S, H, W, RH, RW, OH, OW, *(geo + [M * K, mod * K, K]))
 
 
-def preprocess_images(img, images, resampled, rows, cols, mod):
+def preprocess_images(img, images, resampled, rows, cols, mod, knots=None):
     """The image half of preprocess_volume, for a volume without labels: channel `mod` of images [S,OH,OW,M] is written and no label
     kernel is launched."""
     S, H, W = img.shape
@@ -1842,9 +1846,54 @@ def preprocess_images(img, images, resampled, rows, cols, mod):
     if img.dtype != torch.float32 or images.shape[0] != S or not 0 <= mod < M or not images.is_contiguous():
         raise ValueError('preprocess_images: img %s %s, images %s, modality %d' % (tuple(img.shape), img.dtype, tuple(images.shape), mod))
     geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    if knots is not None:
+        return _image_map(img, images, knots, S, H, W, RH, RW, OH, OW, geo, M, mod)
     ws = _ws('preprocess', N.call('mmseg_preprocess_workspace_floats', S, RH, RW), images.device)
     N.call('mmseg_preprocess_minmax', _c(img), ws, S, H, W, RH, RW)
     N.call('mmseg_preprocess_image', _c(img), ws, images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod]))
+
+
+PREPROCESS_MAX_KNOTS = 16          # csrc/preprocess.hip
+
+
+def _image_map(img, images, knots, S, H, W, RH, RW, OH, OW, geo, M, mod):
+    """mmseg_preprocess_image_map with knots = (x [G,K], y [K]) fp32 on the device; G = 1 (one scale for the volume) or S"""
+    x, y = knots
+    K = int(y.numel())
+    if (x.dim() != 2 or x.dtype != torch.float32 or y.dtype != torch.float32 or x.shape[1] != K or x.shape[0] not in (1, S)
+            or not 2 <= K <= PREPROCESS_MAX_KNOTS):
+        raise ValueError('preprocess: knots must be (x [1 or %d, K], y [K]) fp32 with K in 2..%d, got %s %s and %s %s'
+                         % (S, PREPROCESS_MAX_KNOTS, tuple(x.shape), x.dtype, tuple(y.shape), y.dtype))
+    per_volume = 1 if x.shape[0] == 1 and S > 1 else 0          # one slice: both scopes read row 0
+    if per_volume and S * RH * RW >= 2 ** 31:
+        raise ValueError('preprocess: a volume of %d x %d x %d resampled values (2^31 or more) cannot share one scale' % (S, RH, RW))
+    N.call('mmseg_preprocess_image_map', _c(img), _c(x), _c(y), images, S, H, W, RH, RW, OH, OW, *(geo + [M, mod, K, per_volume]))
+
+
+def preprocess_quantiles(img, resampled, ranks, per_volume):
+    """x [G,K] fp32 on the device: the order statistics of rank ranks[k] (0-based, a host sequence of K = 2..16 integers) of every
+    segment of the raw slices img [S,H,W] fp32 resampled to `resampled` = (RH, RW) -- one segment per slice (G = S, N = RH * RW values)
+    or, with per_volume, the whole volume (G = 1, N = S * RH * RW).  Exact: every x is an element of the resampled population that
+    preprocess_images(knots=...) meets again bit for bit (csrc/preprocess.hip; the definition is in include/mmseg_hip.h).  No gradient."""
+    S, H, W = img.shape
+    RH, RW = int(resampled[0]), int(resampled[1])
+    ranks = [int(r) for r in ranks]
+    K, per_volume = len(ranks), bool(per_volume)
+    n = (S if per_volume else 1) * RH * RW
+    if img.dtype != torch.float32 or S < 1 or RH < 1 or RW < 1 or not 2 <= K <= PREPROCESS_MAX_KNOTS:
+        raise ValueError('preprocess_quantiles: img %s %s, resampled %s, %d ranks (2..%d)'
+                         % (tuple(img.shape), img.dtype, (RH, RW), K, PREPROCESS_MAX_KNOTS))
+    if n >= 2 ** 31:
+        raise ValueError('preprocess_quantiles: a segment of %d values (2^31 or more)' % n)
+    if any(not 0 <= r <= n - 1 for r in ranks):
+        raise ValueError('preprocess_quantiles: ranks must lie in [0, %d], got %r' % (n - 1, ranks))
+    G = 1 if per_volume else S
+    x = _new((G, K), img)
+    nbytes = N.call('mmseg_preprocess_quantiles_workspace_bytes', S, K, int(per_volume))
+    ws = _ws('preprocess_quantiles', (nbytes + 3) // 4, img.device, torch.int32)
+    N.call('mmseg_preprocess_quantiles', _c(img), torch.tensor(ranks, dtype=torch.int32).to(img.device), ws, x, S, H, W, RH, RW, K,
+           int(per_volume))
+    return x
 
 
 def restore_label(prob, values, raw_hw, resampled, rows, cols, order=1):

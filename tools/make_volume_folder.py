@@ -10,7 +10,7 @@ same anatomy; the later modalities carry extra leading / trailing slices, and th
 ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
-                                       [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI]
+                                       [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI] [--hot_voxels N]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -48,6 +48,17 @@ def make_volume(rng, anatomy_seed, mod, S, H, W, values):
     return image, label
 
 
+def add_hot_voxels(rng, image, count):
+    """image [S,H,W] int16 times a gain from [0.5, 2], then `count` voxels per slice at 8 .. 16 times the slice's maximum (within int16)"""
+    out = image.astype(np.float64) * rng.uniform(0.5, 2.0)
+    S, H, W = out.shape
+    for i in range(S):
+        top = out[i].max()
+        for _ in range(count):
+            out[i, rng.randint(0, H), rng.randint(0, W)] = min(top * rng.uniform(8.0, 16.0), 32767.0)
+    return np.round(out).astype(np.int16)
+
+
 def default_splits(ids):
     """70 / 15 / 15 like CHAOS's 14 / 3 / 3 (at least one volume each), rotated for a second split"""
     n = len(ids)
@@ -60,10 +71,12 @@ def default_splits(ids):
 
 
 def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False,
-                 slice_spacing=None):
+                 slice_spacing=None, hot_voxels=0):
     """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
     draws included, is as without it.  slice_spacing = (LO, HI): every file also stores `slice_spacing`, mm between its slices, drawn
-    from [LO, HI] by a generator of its own, so that every other draw is as without it"""
+    from [LO, HI] by a generator of its own, so that every other draw is as without it.  hot_voxels = N > 0: every file is multiplied
+    by a gain of its own from [0.5, 2] (scanners differ) and every slice gets N voxels of 8 to 16 times its maximum (vessels, fold-over
+    artefacts): what the `intensity` modes of the loader are for.  These draws too come from a generator of their own."""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
@@ -71,6 +84,9 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
     spacing_rng = np.random.RandomState(seed + 1000003)
     if slice_spacing is not None and not 0 < slice_spacing[0] <= slice_spacing[1]:
         raise ValueError('slice_spacing must be 0 < LO <= HI, got %r' % (slice_spacing,))
+    if hot_voxels < 0:
+        raise ValueError('hot_voxels must be 0 or more, got %r' % (hot_voxels,))
+    hot_rng = np.random.RandomState(seed + 2000003)
     values = label_values(masks)
     ids = list(range(1, volumes + 1))
     manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
@@ -85,6 +101,8 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
                 H, W = [int(rng.randint(raw_size[0], raw_size[1] + 1)) for _ in range(2)]
             before, after = (0, 0) if mod == 0 else (int(rng.randint(0, 3)), int(rng.randint(0, 3)))
             image, label = make_volume(rng, 1000 * (seed + 1) * v - before, mod, before + slices + after, H, W, values)
+            if hot_voxels:
+                image = add_hot_voxels(hot_rng, image, hot_voxels)
             fname = 'vol%02d_%s.npz' % (v, mod_name)
             arrays = dict(image=image, resolution=res.astype(np.float64)) if unlabelled else dict(image=image, label=label,
                                                                                                    resolution=res.astype(np.float64))
@@ -114,8 +132,11 @@ def main(argv=None):
     ap.add_argument('--unlabelled', action='store_true', help='write files without a label array (a folder to predict on)')
     ap.add_argument('--slice_spacing', type=float, nargs=2, metavar=('LO', 'HI'),
                     help='store a slice spacing in mm per file, drawn from [LO, HI] (what the scores in mm need)')
+    ap.add_argument('--hot_voxels', type=int, default=0, metavar='N',
+                    help='a gain per file and N very bright voxels per slice (what the intensity modes of dataset.json are for)')
     a = ap.parse_args(argv)
-    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing)
+    m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing,
+                     a.hot_voxels)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 
