@@ -471,6 +471,37 @@ int mmseg_boundary_grad_add(const float* phi, float* dpred, int B, long HW, int 
                             const float* weight_dev, void* stream);
 int mmseg_boundary_combine(float* loss, const float* loss_b, const float* weight_dev, void* stream);
 
+/* ---- Lovasz-Softmax loss of the segmentor (csrc/lovasz.hip; BUILD-DEFINED, conf.w_lovasz: the reference's losses hold no sort.
+ *      Berman et al., "The Lovasz-Softmax loss", CVPR 2018; here per image and over the organ channels k < nm only) ----
+ * Per sample b and channel k < nm, over the P = HW pixels:
+ *     y_i = target > 0.5 ? 1 : 0,   e_i = fabsf(y_i - p_i) in fp32 (one subtraction)
+ *     order: e descending, equal e by pixel index ascending (numpy.argsort(-e, kind='stable'))
+ *     G = sum y;  c / n = the positives / negatives strictly before a sorted position
+ *     g = 1 / (G + n)                                   y = 1
+ *     g = (G - c) / ((G + n) (G + n + 1))               y = 0, G > 0
+ *     g = 1 at the first position, 0 elsewhere          G = 0            (lovasz_grad, J_k - J_{k-1}, without cancellation)
+ *     m[b,i,k] = s_i g_i q_b,  s = +1 for y = 0, -1 for y = 1;  m = 0 where e_i == 0;  q_b = 1 / (B |K_b|), K_b the classes with G > 0
+ *     (classes_all = 0, 'present') or all nm classes (classes_all != 0); m = 0 for a class outside K_b (so for a sample with empty K_b)
+ *     L = sum over b, i, k of m (p - y)  in [0, 1];   dL/dp = m (the order is constant almost everywhere).
+ * mmseg_lovasz_map: pred, target [B,HW,C] fp32 NHWC; m [B,HW,nm] fp32, every element written.  A stable least-significant-digit radix
+ * sort (four 8-bit passes over the bit pattern of e) of 64-bit records per (b, k), a scan of the label bit along the sorted order, g in
+ * fp64 from the integers, times q_b, rounded to fp32 once.  1 <= nm <= C <= 8, 1 <= HW <= 2^22, 1 <= B <= 65535; anything else, or a null
+ * pointer, returns hipErrorInvalidValue and launches nothing.  ws: mmseg_lovasz_workspace_bytes(B, HW, nm) bytes, 8-byte aligned (0 for
+ * arguments that would be refused).  No host synchronisation, no allocation, integer atomics only: two runs are bitwise equal; every
+ * grid is a function of (B, HW, nm), so the launches may be recorded into a hipGraph.  Non-finite pred: the kernels terminate, stay in
+ * bounds and write every element; the values are unspecified.
+ * mmseg_lovasz_loss: loss_l[0] = sum m * (p - y), fp64 in two stages of a fixed order, rounded once; ws:
+ * mmseg_lovasz_loss_workspace_floats(B) floats, 8-byte aligned.
+ * mmseg_lovasz_grad_add: for k < nm, dpred[b,px,k] += ((scale_host * scale_dev[0]) * weight_dev[0]) * m[b,px,k], every step rounded to
+ * fp32 (scale_dev == NULL: the factor is left out); channels >= nm are not touched.  It adds to what mmseg_segloss_grad[_s] and
+ * mmseg_boundary_grad_add wrote.  The weighted term enters the loss through mmseg_boundary_combine. */
+long mmseg_lovasz_workspace_bytes(int B, long HW, int nm);
+int mmseg_lovasz_map(const float* pred, const float* target, float* m, int* ws, int B, long HW, int C, int nm, int classes_all, void* stream);
+int mmseg_lovasz_loss_workspace_floats(int B);
+int mmseg_lovasz_loss(const float* pred, const float* target, const float* m, float* loss_l, float* ws, int B, long HW, int C, int nm, void* stream);
+int mmseg_lovasz_grad_add(const float* m, float* dpred, int B, long HW, int C, int nm, float scale_host, const float* scale_dev,
+                          const float* weight_dev, void* stream);
+
 /* ---- optimiser / regulariser (csrc/optim.hip)---------------------------------------------------------- */
 /* Keras 2.1.6 Adam step over a flat arena (models/dafnet.py:93,114,155,161) */
 int mmseg_adam(float* p, const float* g, float* m, float* v, long n, float lr_t, float b1, float b2, float eps, void* stream);

@@ -56,6 +56,12 @@ def parse_arguments(argv=None):
                     help='weight of the boundary loss on the segmentation outputs, 0 or more (overrides the configuration; 0 = off)')
     ap.add_argument('--boundary_ramp_epochs', type=int, metavar='N',
                     help='epochs over which that weight rises linearly to --w_boundary (overrides the configuration; 0 = at once)')
+    ap.add_argument('--w_lovasz', type=float, metavar='W',
+                    help='weight of the Lovasz-Softmax loss on the segmentation outputs, 0 or more (overrides the configuration; 0 = off)')
+    ap.add_argument('--lovasz_ramp_epochs', type=int, metavar='N',
+                    help='epochs over which that weight rises linearly to --w_lovasz (overrides the configuration; 0 = at once)')
+    ap.add_argument('--lovasz_classes', choices=['present', 'all'],
+                    help="classes a sample's Lovasz-Softmax loss averages over: those it holds, or all (overrides the configuration)")
     ap.add_argument('--automatedpairing', type=bool, help='learn the pairing weights (n_pairs = 3)')
     ap.add_argument('--randomise', type=bool, help='randomise the multimodal pairs')
     ap.add_argument('--data_folder', help='folder of exported volumes (dataset.json + .npz) to train, validate and test on')
@@ -264,7 +270,7 @@ class Experiment(object):
         shown = conf.l_mix                       # the folder carries the string as typed on the command line
         if getattr(args, 'l_mix', None) is not None:
             conf.l_mix, shown = float(args.l_mix), args.l_mix
-        for key in ('w_boundary', 'boundary_ramp_epochs'):       # build-defined keys; validated when the model is built
+        for key in ('w_boundary', 'boundary_ramp_epochs', 'w_lovasz', 'lovasz_ramp_epochs', 'lovasz_classes'):   # build-defined keys; validated when the model is built
             if getattr(args, key, None) is not None:
                 conf[key] = getattr(args, key)
         conf.folder = folder_name(conf.folder, conf.randomise, conf.automatedpairing, shown, conf.modality, split)

@@ -198,6 +198,8 @@ class DAFNetExecutor(Executor):
         loss_names = self.get_loss_names()
         if getattr(self.model, 'boundary', None) is not None:      # conf.w_boundary > 0: the raw boundary term gets a column of its own
             loss_names = loss_names + ['boundary']
+        if getattr(self.model, 'lovasz', None) is not None:        # conf.w_lovasz > 0: likewise the raw Lovasz-Softmax term
+            loss_names = loss_names + ['lovasz']
         total_loss = {n: [] for n in loss_names}
         csv_path = self.conf.folder + '/training.csv'
         main = dp.is_main()                    # data parallel: rank 0 writes the csv and the checkpoints
@@ -208,6 +210,7 @@ class DAFNetExecutor(Executor):
             log.info('Epoch %d/%d' % (self.epoch, self.conf.epochs))
             epoch_loss = {n: [] for n in loss_names}
             self.model.set_boundary_epoch(self.epoch)       # the boundary weight of this epoch, before its first batch (nothing when off)
+            self.model.set_lovasz_epoch(self.epoch)         # and the Lovasz weight
             for self.batch in range(self.batches):
                 self.train_batch(epoch_loss)
             dp.average_state(self._all_models())     # replicas leave the epoch with identical BatchNorm moving statistics
@@ -406,6 +409,8 @@ class DAFNetExecutor(Executor):
         epoch_loss['supervised_Mask'].append(g('Segmentor_loss'))
         if 'boundary' in epoch_loss and 'Segmentor_boundary' in hist:
             epoch_loss['boundary'].append(g('Segmentor_boundary'))
+        if 'lovasz' in epoch_loss and 'Segmentor_lovasz' in hist:
+            epoch_loss['lovasz'].append(g('Segmentor_lovasz'))
         epoch_loss['adv_M'].append(g('D_Mask_loss'))
         epoch_loss['rec_X'].append(g('Decoder_loss'))
         epoch_loss['adv_X1'].append(g('D_Image1_loss'))

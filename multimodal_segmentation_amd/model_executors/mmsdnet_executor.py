@@ -150,6 +150,8 @@ class MMSDNetExecutor(DAFNetExecutor):
         epoch_loss['supervised_Mask'].append(self._loss(h, 'Segmentor_loss'))
         if 'boundary' in epoch_loss and 'Segmentor_boundary' in h.history:
             epoch_loss['boundary'].append(self._loss(h, 'Segmentor_boundary'))
+        if 'lovasz' in epoch_loss and 'Segmentor_lovasz' in h.history:
+            epoch_loss['lovasz'].append(self._loss(h, 'Segmentor_lovasz'))
         epoch_loss['adv_M'].append(self._loss(h, 'D_Mask_loss'))
         epoch_loss['rec_X'].append(self._loss(h, 'Decoder_loss'))
         epoch_loss['KL'].append(self._loss(h, 'Enc_Modality_loss'))

@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .. import boundary, costs, loss_scaler, nn, ops
+from .. import boundary, costs, loss_scaler, lovasz, nn, ops
 from ..model_components import anatomy_encoder, anatomy_fuser, modality_encoder, segmentor, decoder
 from ..utils.rng import global_rng
 from .basenet import BaseNet
@@ -50,6 +50,7 @@ class MMSDNet(BaseNet):
         convolutions on operands rounded to that type with fp32 accumulation (BASELINE configs #3 / #5: reduced-
         precision compute, fp32 master weights, fp32 gradient all-reduce).  Process-wide switch of the kernel library."""
         boundary.parse_conf(self.conf)                       # conf.w_boundary / boundary_ramp_epochs: refused before anything is built
+        lovasz.parse_conf(self.conf)                         # conf.w_lovasz / lovasz_ramp_epochs / lovasz_classes: likewise
         ops.set_conv_precision(self.conf.get('compute_dtype', 'fp32'))
         # conf.act_storage (build-defined, default 'fp32'): 'half' keeps the trunk's activations / gradients in HBM in the 16-bit type
         ops.set_activation_storage(self.conf.get('act_storage', 'fp32') == 'half')
@@ -89,6 +90,17 @@ class MMSDNet(BaseNet):
                 if self.boundary is None:
                     self.boundary = boundary.BoundaryWeight(t.device, *bconf)
                 t.boundary = self.boundary
+        # conf.w_lovasz > 0 (build-defined, default 0 = off; conf.lovasz_ramp_epochs, default 0; conf.lovasz_classes, default 'present'):
+        # every Dice output of the generator trainers also pays w * L, the Lovasz-Softmax loss of its prediction (lovasz.py,
+        # csrc/lovasz.hip); one device-resident weight for the whole model, set per epoch by set_lovasz_epoch
+        lconf = lovasz.parse_conf(self.conf)
+        self.lovasz = None
+        for name in ('supervised_trainer', 'unsupervised_trainer'):
+            t = getattr(self, name, None)
+            if t is not None and lconf is not None and any(s.kind in ('dice_bce', 'dice') for s in t.specs):
+                if self.lovasz is None:
+                    self.lovasz = boundary.BoundaryWeight(t.device, lconf[0], lconf[1])
+                t.lovasz, t.lovasz_all = self.lovasz, lconf[2] == 'all'
         for m in self._generator_models() + [d for d in (getattr(self, 'D_Mask', None), getattr(self, 'D_Image1', None),
                                                          getattr(self, 'D_Image2', None), getattr(self, 'Balancer', None)) if d is not None]:
             m.precision = getattr(self, '_precision', None)          # `predict` of a component re-enters this wrapper's precision
@@ -105,6 +117,12 @@ class MMSDNet(BaseNet):
         recorded and the eager steps read; called by the executors before the first batch of every epoch.  Nothing when off."""
         if getattr(self, 'boundary', None) is not None:
             self.boundary.set_epoch(epoch)
+
+    def set_lovasz_epoch(self, epoch):
+        """the Lovasz weight of this epoch (w_lovasz * min(1, (epoch + 1) / lovasz_ramp_epochs)) into its device scalar; called by the
+        executors beside set_boundary_epoch.  Nothing when off."""
+        if getattr(self, 'lovasz', None) is not None:
+            self.lovasz.set_epoch(epoch)
 
     def loss_scalers(self):
         """[(trainer name, LossScaler)] of the dynamic loss scale; empty in every other mode"""

@@ -52,6 +52,10 @@ class Trainer(object):
         # multiplied with (csrc/boundary.hip); None = off, none of those kernels is launched
         self.boundary = None
         self._prepared, self._phi = None, None            # per fit: targets by identity -> device tensor -> distance map
+        # conf.w_lovasz > 0 (build-defined): the device weight (a boundary.BoundaryWeight, the generic ramped device scalar) of the
+        # Lovasz-Softmax term of every Dice output (csrc/lovasz.hip), and conf.lovasz_classes == 'all'; None = off, no launch
+        self.lovasz = None
+        self.lovasz_all = False
 
     # keras API used by the executors ---------------------------------------------------------------------------
     @property
@@ -68,10 +72,10 @@ class Trainer(object):
         if spec.kind == 'dice_bce':
             out = ops.seg_loss(pred, target, self.num_masks, 0.01, gs, class_sum_hook=dp.class_sum_hook(),
                                n_pix_global=pred.numel() // pred.shape[-1] * dp.world_size(), scale_dev=sd)
-            return out if self.boundary is None else self._add_boundary(spec, pred, target, out, gs, sd, hist)
+            return self._add_terms(spec, pred, target, out, gs, sd, hist)
         if spec.kind == 'dice':
             out = ops.seg_loss(pred, target, self.num_masks, 0.0, gs, scale_dev=sd)
-            return out if self.boundary is None else self._add_boundary(spec, pred, target, out, gs, sd, hist)
+            return self._add_terms(spec, pred, target, out, gs, sd, hist)
         if spec.kind == 'mse':
             return ops.diff_loss(pred, target, 'mse', gs, scale_dev=sd)
         if spec.kind == 'mae':
@@ -79,6 +83,31 @@ class Trainer(object):
         if spec.kind == 'ypred':
             return ops.diff_loss(pred, 0.0, 'mean', gs, scale_dev=sd)
         raise ValueError(spec.kind)
+
+    def _add_terms(self, spec, pred, target, out, gs, sd, hist):
+        """the optional terms of a Dice output, in a fixed order: boundary, then Lovasz (each nothing when off)"""
+        if self.boundary is not None:
+            out = self._add_boundary(spec, pred, target, out, gs, sd, hist)
+        if self.lovasz is not None:
+            out = self._add_lovasz(spec, pred, target, out, gs, sd, hist)
+        return out
+
+    def _add_lovasz(self, spec, pred, target, out, gs, sd, hist):
+        """+ weight * L of the Lovasz-Softmax loss (per image, organ channels): the signed map m of this prediction (a device sort per
+        sample and class; it depends on the prediction, so it is built per output), the term sum m (p - y), its gradient m added into
+        what seg_loss (and the boundary term) wrote, the weighted term added into the loss value; the raw term goes into the History
+        as '<name>_lovasz'.  q_b holds the local batch size (the data-parallel all-reduce averages over ranks) and the recorded term is
+        rank-local, as for the boundary term."""
+        loss, dpred = out
+        w = self.lovasz.weight_dev
+        m = ops.lovasz_map(pred, target, self.num_masks, self.lovasz_all)
+        loss_l = ops.lovasz_term(pred, target, m, self.num_masks)
+        if dpred is not None:
+            ops.lovasz_grad_add(m, dpred, self.num_masks, gs, w, scale_dev=sd)
+        ops.boundary_combine(loss, loss_l, w)
+        if hist is not None:
+            hist.record(spec.name + '_lovasz', loss_l)
+        return loss, dpred
 
     def _add_boundary(self, spec, pred, target, out, gs, sd, hist):
         """the segmentation loss of one output + weight * L_B: the map of the target (built once per distinct target of a fit), the term,

@@ -1413,6 +1413,38 @@ def boundary_combine(loss, loss_b, weight_dev):
 
 
 # ------------------------------------------------------------------------------------------------------
+# Lovasz-Softmax loss of the segmentor (csrc/lovasz.hip; build-defined, conf.w_lovasz): no autograd node either
+# ------------------------------------------------------------------------------------------------------
+def lovasz_map(pred, target, num_masks, classes_all=False):
+    """The signed Lovasz map m [B,H,W,num_masks] of pred against target (both [B,H,W,C], foreground: target > 0.5): per sample and
+    class the pixels sorted by |y - p| on the device, m = +-lovasz_grad / (B * classes counted), 0 where the error is 0
+    (include/mmseg_hip.h).  The loss is sum m * (p - y) and m is its gradient with respect to pred."""
+    pred, target = _c(pred), _c(target)
+    B, H, W, C = pred.shape
+    m = _new((B, H, W, num_masks), pred)
+    ws = _ws('lovasz_map', (N.call('mmseg_lovasz_workspace_bytes', B, H * W, num_masks) + 3) // 4, pred.device, torch.int32)
+    N.call('mmseg_lovasz_map', pred, target, m, ws, B, H * W, C, num_masks, 1 if classes_all else 0)
+    return m
+
+
+def lovasz_term(pred, target, m, num_masks):
+    """L = sum over (b, pixel, k < num_masks) of m * (pred - y) -> loss_l[1] (fp64, a fixed-order two-stage reduction, rounded once)"""
+    pred, target, m = _c(pred), _c(target), _c(m)
+    B, H, W, C = pred.shape
+    loss_l = _new((1,), pred)
+    ws = _ws('lovasz_loss', N.call('mmseg_lovasz_loss_workspace_floats', B), pred.device)
+    N.call('mmseg_lovasz_loss', pred, target, m, loss_l, ws, B, H * W, C, num_masks)
+    return loss_l
+
+
+def lovasz_grad_add(m, dpred, num_masks, scale, weight_dev, scale_dev=None):
+    """dpred[..., :num_masks] += scale [* scale_dev[0]] * weight_dev[0] * m, in place on what seg_loss (and the boundary term) wrote"""
+    B, H, W, C = dpred.shape
+    N.call('mmseg_lovasz_grad_add', _c(m), dpred, B, H * W, C, num_masks, float(scale), scale_dev, weight_dev)
+    return dpred
+
+
+# ------------------------------------------------------------------------------------------------------
 # in-graph per-sample loss terms of the automated-pairing trainers (csrc/pairloss.hip)
 # ------------------------------------------------------------------------------------------------------
 class _OverlapDice(torch.autograd.Function):
