@@ -728,6 +728,28 @@ int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const
  * synchronisation, allocation or copy. */
 int mmseg_merge_views(const float* prob, const double* back, float* out, int V, int N, int OH, int OW, int C, int K, void* stream);
 
+/* ---- maps refined against the image: a windowed mean-field CRF (csrc/crf.hip; build-defined, the rule is in INTEGRATION.md section 5) ----
+ * prob [N,H,W,C] fp32: a segmentor's output on the network grid, the K organ channels first.  image [N,H,W,1] fp32: the slices the network
+ * saw, in [-1, 1] (finite).  out [N,H,W,K] fp32, every element written: the organ channels of Q^T.  L = K + 1 labels: the K organs and
+ * "rest" = max(0, 1 - sum of the K organ channels), whatever C is.  u_l(p) = log(max(P_l(p), 1e-6)), Q^0 = softmax_l(u).  Iteration
+ * t = 1 .. iterations, every pixel reading Q^(t-1) only, over the neighbours q = p + (dy, dx), |dy|, |dx| <= radius, q != p, q inside the
+ * slice (pixels beyond it are skipped, not padded; slices never see each other):
+ *   a(p,q) = exp(-|p-q|^2 / (2 theta_alpha^2) - (I_p - I_q)^2 / (2 theta_beta^2)),  s(p,q) = exp(-|p-q|^2 / (2 theta_gamma^2))
+ *   m_l(p) = w_a * sum_q a Q_l(q) / sum_q a + w_s * sum_q s Q_l(q) / sum_q s,        Q^t(p) = softmax_l(u_l(p) + m_l(p))
+ * Each kernel is normalised by its own sum over the neighbours that exist; a pixel without neighbours (a 1 x 1 slice) gets m = 0, and so
+ * does the appearance term of a pixel whose fp32 appearance sum underflows to 0.  fp32 throughout, the window walked in ascending
+ * (dy, dx); the appearance weight through the hardware exp2, the unary and the soft-max through logf / expf; the spatial factors from a
+ * table built once per call.  A gather without atomics: two runs are bitwise equal, and the result of a slice does not depend on the
+ * other slices of the call.  prob and image are only read.
+ * 1 <= radius <= 8, 1 <= iterations <= 20, the three theta finite and > 0, w_a and w_s finite and >= 0 and not both 0, 1 <= K <= min(C, 16),
+ * extents >= 1, prob, image and out below 2^31 bytes each; anything else, a null pointer, or out or ws overlapping another operand is
+ * refused (hipErrorInvalidValue, nothing is launched).  N == 0 does nothing. */
+/* bytes of ws for mmseg_crf_refine: the two tables and two planar Q buffers [N,K+1,H,W]; 0 for sizes that it would refuse */
+long mmseg_crf_refine_workspace_bytes(int N, int H, int W, int K);
+/* ws is the only scratch.  2 + iterations launches on the stream; no host synchronisation, allocation or copy. */
+int mmseg_crf_refine(const float* prob, const float* image, float* out, void* ws, int N, int H, int W, int C, int K, int radius,
+                     int iterations, float w_a, float theta_alpha, float theta_beta, float w_s, float theta_gamma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
                          [--predict_smooth open|close|smooth] [--predict_smooth_radius MM] [--predict_smooth_extent 2d|3d]
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
                          [--predict_tiles true|false] [--predict_tile_overlap PIXELS] [--predict_tta LIST]
+                         [--predict_crf SPEC]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--intensity_norm` and its two companions (build-defined, like
@@ -107,6 +108,11 @@ def parse_arguments(argv=None):
                     help='test-time augmentation: predict every slice under these views and average the maps brought back, e.g. '
                          'id,fliplr,flipud,rot180 (= flips), d4 (the eight flips and right-angle turns) or id,rot10,rot-10 (degrees); '
                          'the first view is id')
+    ap.add_argument('--predict_crf', default='none', metavar='SPEC',
+                    help='refine every probability map against its image by a windowed mean-field CRF before the labels are taken: '
+                         'none, default, or key=value,... over the defaults radius=5,iterations=5,w_a=4,theta_alpha=3,theta_beta=0.1,'
+                         'w_s=1,theta_gamma=1.5, which are untuned starting values (tools/crf_sweep.py scores a grid of settings; '
+                         'results_crf_<modality>.csv)')
     args = ap.parse_args(argv)
     if (args.intensity_scope or args.intensity_percentiles) and args.intensity_norm != 'window':
         ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
@@ -340,6 +346,7 @@ class Experiment(object):
                                               tiles=bool(getattr(args, 'predict_tiles', False)),
                                               tile_overlap=getattr(args, 'predict_tile_overlap', None),
                                               tta=getattr(args, 'predict_tta', None),
+                                              crf=getattr(args, 'predict_crf', None),
                                               smooth=getattr(args, 'predict_smooth', None),
                                               smooth_radius=getattr(args, 'predict_smooth_radius', None),
                                               smooth_extent=getattr(args, 'predict_smooth_extent', '2d'))
@@ -359,6 +366,9 @@ class Experiment(object):
         if getattr(args, 'predict_tta', 'none') not in (None, 'none'):          # before the model is built as well
             from .volume_predictor import check_tta
             check_tta(args.predict_tta, conf.input_shape)
+        if getattr(args, 'predict_crf', 'none') not in (None, 'none'):          # and so is this
+            from .volume_predictor import check_crf
+            check_crf(args.predict_crf)
         if getattr(args, 'predict_folder', None) and args.test:
             from .volume_predictor import checkpoint_of
             if checkpoint_of(conf.folder) is None:          # before the test pass evaluates an untrained model

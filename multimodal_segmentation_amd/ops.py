@@ -5,6 +5,7 @@ arithmetic operation on activations, gradients and weights is a kernel of csrc/*
 _native.call (C ABI, include/mmseg_hip.h).  Layout: NHWC fp32 (the reference's layout), weights in Keras
 layout (conv HWIO, dense [in, out]).
 """
+import collections
 import math
 
 import numpy as np
@@ -2177,6 +2178,75 @@ def merge_views(prob, back, N_, K):
     out = _new((n, OH, OW, K), prob)
     if n:
         N.call('mmseg_merge_views', _c(prob), _c(b.to(prob.device)), out, V, n, OH, OW, C, K)
+    return out
+
+
+# the parameters of crf_refine, in the order of the entry point; the defaults are starting values that nobody has tuned
+CrfParams = collections.namedtuple('CrfParams', ('radius', 'iterations', 'w_a', 'theta_alpha', 'theta_beta', 'w_s', 'theta_gamma'))
+CRF_DEFAULTS = CrfParams(radius=5, iterations=5, w_a=4.0, theta_alpha=3.0, theta_beta=0.1, w_s=1.0, theta_gamma=1.5)
+CRF_MAX_RADIUS, CRF_MAX_ITERATIONS = 8, 20          # csrc/crf.hip
+CRF_WORKSPACE_CAP = 256 << 20
+
+
+def crf_params(params, what='crf_refine'):
+    """params: a CrfParams or a sequence in its order -> a CrfParams of two ints and five floats within the limits of the rule: radius
+    1..8, iterations 1..20, the three theta finite and > 0, w_a and w_s finite and >= 0 and not both 0.  Raises ValueError otherwise."""
+    def refuse(why):
+        raise ValueError('%s: %s, got %r' % (what, why, params))
+    try:
+        p = CrfParams(*params)
+    except TypeError:
+        refuse('expected (%s)' % ', '.join(CrfParams._fields))
+    whole = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in p[:2])
+    if not whole or not 1 <= p.radius <= CRF_MAX_RADIUS or not 1 <= p.iterations <= CRF_MAX_ITERATIONS:
+        refuse('radius must be a whole number in 1..%d and iterations one in 1..%d' % (CRF_MAX_RADIUS, CRF_MAX_ITERATIONS))
+    try:
+        reals = [float(v) for v in p[2:]]
+    except (TypeError, ValueError):
+        refuse('the weights and the theta must be numbers')
+    if any(isinstance(v, bool) for v in p[2:]) or not all(math.isfinite(v) for v in reals):
+        refuse('the weights and the theta must be finite numbers')
+    # what the kernel sees is fp32: a value that rounds to 0 or to inf there is refused here as well
+    with np.errstate(over='ignore', under='ignore'):
+        seen = CrfParams(0, 0, *(float(np.float32(v)) for v in reals))
+    if not all(0 < v < float('inf') for v in (seen.theta_alpha, seen.theta_beta, seen.theta_gamma)):
+        refuse('theta_alpha, theta_beta and theta_gamma must be finite and > 0 in fp32')
+    if not all(0 <= v < float('inf') for v in (seen.w_a, seen.w_s)) or (seen.w_a == 0 and seen.w_s == 0):
+        refuse('w_a and w_s must be finite and >= 0 in fp32, and not both 0')
+    return CrfParams(int(p.radius), int(p.iterations), *reals)
+
+
+def crf_refine(prob, image, K, params=CRF_DEFAULTS, max_workspace_bytes=CRF_WORKSPACE_CAP):
+    """prob [N,H,W,C] fp32 on the device: a segmentor's output, the K organ channels first; image [N,H,W,1] fp32: the slices it saw, in
+    [-1, 1] -> fp32 [N,H,W,K], the organ channels after `params.iterations` mean-field iterations of the windowed CRF of INTEGRATION.md
+    section 5 (csrc/crf.hip): K + 1 labels (the organs and the rest), an appearance and a smoothness kernel over the (2 radius + 1)^2
+    window, each normalised by its own sum.  Slices are independent; they run in chunks whose workspace (two Q buffers of K + 1 planes)
+    stays under max_workspace_bytes (one slice at least), with bitwise the result of one call.  No gradient."""
+    p = crf_params(params)
+    K = int(K)
+    if (prob.dim() != 4 or prob.dtype != torch.float32 or image.dtype != torch.float32 or image.device != prob.device
+            or tuple(image.shape) != tuple(prob.shape[:3]) + (1,) or not 1 <= K <= min(16, prob.shape[3]) or min(prob.shape[1:3]) < 1):
+        raise ValueError('crf_refine: prob %s %s, image %s %s on %s and %s, K = %d: expected fp32 [N,H,W,C] and [N,H,W,1] on one device, '
+                         '1 <= K <= min(C, 16)' % (tuple(prob.shape), prob.dtype, tuple(image.shape), image.dtype, prob.device, image.device, K))
+    n, H, W, C = (int(v) for v in prob.shape)
+    if prob.numel() * 4 >= 2 ** 31:
+        raise ValueError('crf_refine: prob %s holds 2^31 bytes or more' % (tuple(prob.shape),))
+    if isinstance(max_workspace_bytes, bool) or not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
+        raise ValueError('crf_refine: max_workspace_bytes must be a whole number of bytes >= 1, got %r' % (max_workspace_bytes,))
+    out = _new((n, H, W, K), prob)
+    if n == 0:
+        return out
+    prob, image = _c(prob), _c(image)
+    one, two = (N.call('mmseg_crf_refine_workspace_bytes', s, H, W, K) for s in (1, 2))
+    if one <= 0:
+        raise ValueError('crf_refine: a slice of %d x %d with %d channels is more than one call holds' % (H, W, C))
+    per_slice = two - one if two > 0 else one
+    step = int(min(n, max(1, (int(max_workspace_bytes) - (one - per_slice)) // per_slice)))
+    ws = _ws('crf_refine', (N.call('mmseg_crf_refine_workspace_bytes', step, H, W, K) + 3) // 4, prob.device)
+    for i in range(0, n, step):
+        s = min(step, n - i)
+        N.call('mmseg_crf_refine', prob[i:i + s], image[i:i + s], out[i:i + s], ws, s, H, W, C, K, p.radius, p.iterations, p.w_a,
+               p.theta_alpha, p.theta_beta, p.w_s, p.theta_gamma)
     return out
 
 

@@ -23,6 +23,15 @@ input file.  The raw arrays cross the bus once each way: the image up, 1 byte pe
                                            the filling and the voxels added, one row per volume
     <out>/results_smooth_<modality>.csv    with smooth='open', 'close' or 'smooth': per organ its voxels before, the voxels removed
                                            and the voxels added, one row per volume
+    <out>/results_crf_<modality>.csv       with crf='default' or 'key=value,...': per organ its voxels on the file grid before the
+                                           refinement, the voxels removed and the voxels added, one row per volume
+
+crf='default' | 'key=value,...' (build-defined, off by default; the rule is in INTEGRATION.md section 5) refines the probability map of
+modality m against the slices of that modality as the network saw them, before anything else: a mean-field CRF over the (2 radius + 1)^2
+window with an appearance and a smoothness kernel (ops.crf_refine, csrc/crf.hip), the one step of the way back that looks at the image
+again.  With tta it follows the merge, against the unturned slices; with tiles it runs tile by tile before the blend.  The order is
+crf, restore_label, smoothing, filter, filling, then scores and file.  predictions.json then carries `crf`, the seven parameters in
+force.  The defaults are untuned starting values (tools/crf_sweep.py scores a grid of settings on a labelled folder).
 
 components='largest' (build-defined, off by default; the rule is in INTEGRATION.md section 5) keeps, per organ, the largest 3-D connected
 component: the prediction is scattered to the file grid [S_file,H,W] on the device and filtered there (ops.keep_largest_components),
@@ -355,6 +364,45 @@ def views_in(images, views):
     return [ops.augment_gather(ops._c(x), rows, mats, None, 1, 'nearest') for x in images]
 
 
+CrfParams, CRF_DEFAULTS = ops.CrfParams, ops.CRF_DEFAULTS
+
+
+def check_crf(spec):
+    """spec: None or 'none' (off) -> None; 'default' -> CRF_DEFAULTS; 'key=value,...' with the keys of CrfParams (radius, iterations, w_a,
+    theta_alpha, theta_beta, w_s, theta_gamma) -> the defaults with those values; a CrfParams or a sequence in its order -> itself.  The
+    result is within the limits of ops.crf_refine (ops.crf_params).  The defaults are starting values that nobody has tuned:
+    tools/crf_sweep.py scores a grid of settings on a labelled folder."""
+    what = 'crf (--predict_crf)'
+
+    def refuse(why):
+        raise ValueError("%s must be 'none', 'default' or key=value,... over the defaults (%s), got %r: %s"
+                         % (what, ', '.join('%s=%g' % kv for kv in CRF_DEFAULTS._asdict().items()), spec, why))
+    if spec is None:
+        return None
+    if not isinstance(spec, str):
+        if isinstance(spec, (bool, int, float, dict)):
+            refuse('neither a string nor a sequence of the seven parameters')
+        return ops.crf_params(spec, what)
+    text = spec.strip().lower()
+    if text == 'none':
+        return None
+    values = CRF_DEFAULTS._asdict()
+    if text != 'default':
+        seen = set()
+        for item in text.split(','):
+            key, eq, value = (s.strip() for s in item.partition('='))
+            if not eq or key not in values:
+                refuse('%r is no key=value of these' % (item,))
+            if key in seen:
+                refuse('%s is given twice' % key)
+            seen.add(key)
+            try:
+                values[key] = int(value) if key in ('radius', 'iterations') else float(value)
+            except ValueError:
+                refuse('%r is no %s' % (value, 'whole number' if key in ('radius', 'iterations') else 'number'))
+    return ops.crf_params(CrfParams(**values), what)
+
+
 _fill_holes, _smooth = fill_holes, smooth          # for score_folder and VolumePredictor.run, whose keywords carry the functions' names
 
 
@@ -385,6 +433,11 @@ def write_smooth_results(path, rows, num_masks):
     _write_table(path, rows, ('Before', 'Removed', 'Added'), num_masks, '%d', False)
 
 
+def write_crf_results(path, rows, num_masks):
+    """rows: (volume, stats [K,3]) -> Vol, Before0, Removed0, Added0, Before1, ..."""
+    _write_table(path, rows, ('Before', 'Removed', 'Added'), num_masks, '%d', False)
+
+
 def write_surface_results(path, rows, num_masks):
     """rows: (volume, [K+1,3] with the union last) -> Vol, RAVD, ASSD, MSSD, RAVD0, ASSD0, MSSD0, ...: the union first"""
     _write_table(path, rows, ('RAVD', 'ASSD', 'MSSD'), num_masks, '%.3f', True)
@@ -398,7 +451,8 @@ def write_robust_results(path, rows, num_masks):
 class ScoreSheet(object):
     """the rows of one run's results_<kind>_<modality>.csv files: rows[kind][m] holds those of modality m; `scores` is score_volume's"""
     WRITERS = (('native', write_results), ('surface', write_surface_results), ('robust', write_robust_results),
-               ('components', write_component_results), ('holes', write_hole_results), ('smooth', write_smooth_results))
+               ('components', write_component_results), ('holes', write_hole_results), ('smooth', write_smooth_results),
+               ('crf', write_crf_results))
 
     def __init__(self, modalities, num_masks, in_mm):
         self.modalities, self.num_masks, self.in_mm = list(modalities), num_masks, in_mm
@@ -425,6 +479,12 @@ class ScoreSheet(object):
 
     def add_smooth(self, m, volume, stats):
         self.rows['smooth'][m].append((volume, nn.to_numpy(stats)))
+
+    def add_crf(self, m, volume, counts):
+        """counts [S,K,3] of ops.label_overlap(labels of the refined map, labels of the map before): per organ the voxels before the
+        refinement, those it removed and those it added"""
+        after, before, both = nn.to_numpy(counts).astype(np.int64).sum(axis=0).T
+        self.rows['crf'][m].append((volume, np.stack([before, before - both, after - both], axis=1)))
 
     def write(self, out_folder):
         """one file per kind and modality that has rows"""
@@ -515,21 +575,29 @@ class VolumePredictor(object):
                              % (len(views.tokens), N, tuple(prob.shape)))
         return ops.merge_views(prob, views.back, N, int(self.conf.num_masks))
 
-    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded, views=None):
+    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded, views=None, crf=None):
         """the blended probability map [S,RH,RW,K] of modality m on its whole resampled frame: the tiles are loaded
         (loader.load_volume_tiles), predicted as one batch of TR*TC*S slices and blended (ops.blend_tiles).  overlap = (rows, columns);
         uploaded: loader.upload_volume(volume).  With views (check_tta's) every tile is predicted under each view, turned about its own
-        centre, and merged (predict_views) before the blend, which then sees the K organ channels alone."""
+        centre, and merged (predict_views) before the blend, which then sees the K organ channels alone.  With crf (check_crf's) every
+        tile's map is refined against the tile's image of modality m (ops.crf_refine) before the blend, and the result is the pair
+        (blend of the refined tiles, blend of the tiles as predicted)."""
         images, geometry, plan = loader.load_volume_tiles(volume, m, overlap, uploaded)
         rows, cols = plan[m]
         OH, OW = loader.input_shape[:2]
         prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
         S = images[m].shape[0] // (len(rows) * len(cols))
-        return ops.blend_tiles(prob, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'],
-                               loader.num_masks)
+
+        def blend(p):
+            return ops.blend_tiles(p, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'],
+                                   loader.num_masks)
+        if crf is None:
+            return blend(prob)
+        return blend(ops.crf_refine(prob, images[m], loader.num_masks, crf)), blend(prob)
 
     def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
-            fill_holes=None, tiles=False, tile_overlap=None, tta=None, smooth=None, smooth_radius=None, smooth_extent='2d'):
+            fill_holes=None, tiles=False, tile_overlap=None, tta=None, smooth=None, smooth_radius=None, smooth_extent='2d', crf=None):
+        crf = check_crf(crf)
         check_components(components, connectivity)
         check_fill_holes(fill_holes)
         smooth_radius = check_smooth(smooth, smooth_radius, smooth_extent)
@@ -570,13 +638,20 @@ class VolumePredictor(object):
                     origins = dict(rows=[t[0] for t in rows], cols=[t[0] for t in cols])
                 if tiles and len(rows) * len(cols) > 1:
                     RH, RW = geo['resampled']
-                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded, views)
-                    pred = ops.restore_label(prob, values, geo['raw_shape'][1:], (RH, RW), (0, RH, 0), (0, RW, 0), order)
+                    window = ((RH, RW), (0, RH, 0), (0, RW, 0))
+                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded, views, crf)
+                    prob, unrefined = prob if crf is not None else (prob, None)
                 else:          # one tile: the centre window of crop_pad_map, the path without the option
                     if images is None:
                         images, _ = loader.load_volume_for_prediction(v)
+                    window = (geo['resampled'], geo['rows'], geo['cols'])
                     prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
-                    pred = ops.restore_label(prob, values, geo['raw_shape'][1:], geo['resampled'], geo['rows'], geo['cols'], order)
+                    if crf is not None:          # against the slices as the network saw them, unturned
+                        prob, unrefined = ops.crf_refine(prob, images[m], loader.num_masks, crf), prob
+                pred = ops.restore_label(prob, values, geo['raw_shape'][1:], window[0], window[1], window[2], order)
+                if crf is not None:
+                    before = ops.restore_label(unrefined, values, geo['raw_shape'][1:], window[0], window[1], window[2], order)
+                    sheet.add_crf(m, v, ops.label_overlap(pred, before, values))
                 if smooth:
                     pred, stats = _smooth(pred, values, geo, smooth, smooth_radius, smooth_extent)
                     sheet.add_smooth(m, v, stats)
@@ -611,6 +686,8 @@ class VolumePredictor(object):
             settings.update(tiles=True, tile_overlap=list(overlap))
         if views is not None:
             settings.update(tta=list(views.tokens))
+        if crf is not None:
+            settings.update(crf=dict(crf._asdict()))
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
         return sheet.by_name('native')
