@@ -401,6 +401,48 @@ int mmseg_intensity_blur(const float* x, const int* radius, const double* weight
 int mmseg_intensity_apply(float* x, const double* params, const double* stats, const float* field, int seed, int batch, int array,
                           int B, int H, int W, int C, void* stream);
 
+/* ---- MR k-space artefact augmentation of a gathered batch (csrc/kspace.hip; build-defined, after TorchIO's RandomMotion / RandomGhosting /
+ *      RandomSpike and MONAI's GibbsNoise / KSpaceSpikeNoise / RicianNoise) ----
+ * x [B,H,W,C] fp32 as above.  lo_b = column 0 of the [B,3] table of mmseg_intensity_stats taken on x as gathered, y = x - lo_b >= 0,
+ * X = fft2(y) per channel in complex fp64, numpy's convention (unshifted; the inverse scaled by 1 / (H W)).  Signed frequencies
+ * ky = u < ceil(H/2) ? u : u - H, kx likewise (numpy.fft.fftfreq(H) * H); p the phase-encode axis (0 rows, 1 columns), k_p the signed
+ * frequency along it, P its extent.  table [B,48] fp64, one row per sample:
+ *   [0] flags = 1 motion + 2 ghosting + 4 Gibbs + 8 spikes + 16 Rician     [1] p     [2] number of breaks (<= 7)     [3..9] sorted breaks
+ *   [10..25] (dy, dx) in pixels of segments 0 .. 7; the host puts (0, 0) into the segment that holds k_p = 0
+ *   [26] n, [27] 1 - a of the ghosts     [28] T = f f H H W W of the Gibbs cut     [29] K <= 4 spikes
+ *   [30..45] per spike (ky mod H, kx mod W, s cos phi, s sin phi)     [46] std of the Rician draw     [47] unused
+ * In this order, each only where its flag is set:
+ *   motion  X *= exp(-2 pi i (ky dy / H + kx dx / W)) with the shift of segment seg(k_p + floor(P/2)), seg(l) = number of breaks <= l
+ *   ghost   X *= 1 - a where k_p != 0 and k_p mod n == 0
+ *   gibbs   X = 0 where 4 (ky^2 W^2 + kx^2 H^2) > T (the left side is an exact integer in fp64)
+ *   spikes  X[ky mod H][kx mod W] += A (s cos phi + i s sin phi), then X[-ky mod H][-kx mod W] += A (s cos phi - i s sin phi), spike after
+ *           spike, both adds also where the two places coincide; A = (sum - H W C lo) / C from the stats table: for C = 1 the DC term
+ *           sum(y), the spectrum's maximum; every element looks its spikes up, nothing is scattered
+ *   rician  z = ifft2(X) + std sqrt(-2 ln u1) (cos 2 pi u2 + i sin 2 pi u2), u1 = ((P[0] >> 8) + 1) * 2^-24, u2 = (P[1] >> 8) * 2^-24,
+ *           P = Philox4x32-10(counter (e, b, array, 5), key (seed, batch)), e = (r*W + c)*C + ch
+ *   output  x = (float)(lo_b + |z|), no clip: an undershoot of the Gibbs ringing folds up, as in a magnitude image
+ * A sample whose flags are 0 is neither read nor written and its slot of spec is left alone; a flagged sample whose spectrum stays as it
+ * was comes back within one fp32 rounding of lo + (x - lo), not bit for bit.
+ *
+ * The transform: 2 <= H, W <= 1024 with no prime factor but 2, 3, 5; Stockham autosort in LDS with radix 4 / 2 / 3 / 5 passes over the
+ * roots of twiddles [H + W] complex fp64: (cos, sin)(2 pi k / H), k < H, then the same for W, made by the host in fp64.  Also needed:
+ * 1 <= B, B*C <= 65535, H*W*C < 2^31, spec and twiddles 16-byte aligned.  Anything else or a null pointer is refused
+ * (hipErrorInvalidValue, nothing is launched); B == 0 does nothing.  No atomics and a fixed order of operations: two runs are bitwise
+ * equal.  No host synchronisation, allocation or copy.
+ *
+ * mmseg_kspace_workspace_doubles: the doubles of spec [B,C,H,W] complex fp64, 2 B C H W; launches nothing, 0 for a refused shape. */
+long mmseg_kspace_workspace_doubles(int B, int H, int W, int C);
+/* spec = fft2(x - lo_b) of the flagged samples: one launch along W (a block per row), one along H (a block per tile of 16 / 8 / 4 / 2
+ * adjacent columns for H <= 128 / 256 / 512 / 1024) */
+int mmseg_kspace_forward(const float* x, const double* table, const double* stats, const double* twiddles, double* spec, int B, int H,
+                         int W, int C, void* stream);
+/* motion, ghosting, Gibbs and spikes on spec, in place: one launch */
+int mmseg_kspace_apply(double* spec, const double* table, const double* stats, int B, int H, int W, int C, void* stream);
+/* x = (float)(lo_b + |ifft2(spec) + the Rician draw|) of the flagged samples: one launch along H, in place on spec (which is left holding
+ * that half-transformed image), one along W.  seed, batch and array are read as 32-bit patterns. */
+int mmseg_kspace_inverse(double* spec, const double* table, const double* stats, const double* twiddles, float* x, int seed, int batch,
+                         int array, int B, int H, int W, int C, void* stream);
+
 /* ---- losses (csrc/loss.hip): costs.py:43-85,129-136, keras mae/mse, costs.ypred ---------------------------- */
 int mmseg_segloss_workspace_floats(int B);
 int mmseg_segloss_stats_floats(int B);

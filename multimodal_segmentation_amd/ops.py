@@ -1845,6 +1845,97 @@ def intensity_apply(x, params, stats, field, seed, batch, array):
     return x
 
 
+KSPACE_FLAGS = dict(motion=1, ghost=2, gibbs=4, spike=8, rician=16)          # column 0 of the k-space table
+KSPACE_PARAMS = 48                                                          # KS_P of csrc/kspace.hip; the columns: include/mmseg_hip.h
+KSPACE_MAX_EXTENT = 1024                                                    # KS_MAXN
+KSPACE_MAX_SEGMENTS, KSPACE_MAX_SPIKES = 8, 4
+_kspace_twiddles = {}
+
+
+def kspace_extent_ok(n):
+    """the transform of csrc/kspace.hip takes a length 2 <= n <= 1024 with no prime factor but 2, 3 and 5"""
+    n = int(n)
+    if not 2 <= n <= KSPACE_MAX_EXTENT:
+        return False
+    for f in (2, 3, 5):
+        while n % f == 0:
+            n //= f
+    return n == 1
+
+
+def kspace_roots(n):
+    """[n, 2] fp64 on the host: (cos, sin)(2 pi k / n), k < n -- the roots the device multiplies by"""
+    t = 2.0 * np.pi * np.arange(int(n), dtype=np.float64) / float(n)
+    return np.stack([np.cos(t), np.sin(t)], axis=1)
+
+
+def kspace_twiddles(H, W, device):
+    """the [H + W, 2] fp64 root table of an (H, W) transform on `device`: made by the host once per (H, W, device) and kept"""
+    device = torch.device(device)
+    key = (int(H), int(W), device)
+    tw = _kspace_twiddles.get(key)
+    if tw is None:
+        if not (kspace_extent_ok(H) and kspace_extent_ok(W)):
+            raise ValueError('kspace: the extents (%d, %d) must lie in [2, %d] and have no prime factor but 2, 3 and 5' % (H, W, KSPACE_MAX_EXTENT))
+        tw = _kspace_twiddles[key] = torch.from_numpy(np.concatenate([kspace_roots(H), kspace_roots(W)])).to(device)
+    return tw
+
+
+def _kspace_check(name, x, table, stats):
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('%s: x must be a contiguous fp32 [B,H,W,C] tensor, got %s %s' % (name, x.dtype, tuple(x.shape)))
+    B, H, W, C = x.shape
+    if tuple(table.shape) != (B, KSPACE_PARAMS) or tuple(stats.shape) != (B, 3):
+        raise ValueError('%s: table must be [B,%d] and stats [B,3], got %r and %r' % (name, KSPACE_PARAMS, tuple(table.shape), tuple(stats.shape)))
+    if B and not N.call('mmseg_kspace_workspace_doubles', B, H, W, C):
+        raise ValueError('%s: shape %r is outside the transform\'s limits (H, W in [2, %d] with no prime factor but 2, 3, 5; B*C <= 65535)'
+                         % (name, tuple(x.shape), KSPACE_MAX_EXTENT))
+    return B, H, W, C
+
+
+def kspace_forward(x, table, stats, spec=None):
+    """spec [B,C,H,W,2] fp64 (re, im) = numpy.fft.fft2(x[b, :, :, ch] - lo_b) of the samples whose table[b, 0] (KSPACE_FLAGS) is not 0;
+    the slots of the others are left as they are (csrc/kspace.hip; the definition is in include/mmseg_hip.h).  x [B,H,W,C] fp32, table
+    [B,48] fp64, stats from intensity_stats(x), all on the device.  spec: a tensor to fill, else a new one.  No gradient."""
+    B, H, W, C = _kspace_check('kspace_forward', x, table, stats)
+    if spec is None:
+        spec = _new((B, C, H, W, 2), x, torch.float64)
+    elif tuple(spec.shape) != (B, C, H, W, 2):
+        raise ValueError('kspace_forward: spec must be [B,C,H,W,2] = %r, got %r' % ((B, C, H, W, 2), tuple(spec.shape)))
+    N.call('mmseg_kspace_forward', x, table, stats, kspace_twiddles(H, W, x.device), spec, B, H, W, C)
+    return spec
+
+
+def kspace_apply(spec, table, stats):
+    """motion, ghosting, Gibbs truncation and spikes IN PLACE on spec [B,C,H,W,2] fp64 (the rule: include/mmseg_hip.h).  Returns spec."""
+    if spec.dim() != 5 or spec.shape[4] != 2 or spec.dtype != torch.float64 or not spec.is_contiguous():
+        raise ValueError('kspace_apply: spec must be a contiguous fp64 [B,C,H,W,2] tensor, got %s %s' % (spec.dtype, tuple(spec.shape)))
+    B, C, H, W = spec.shape[:4]
+    if tuple(table.shape) != (B, KSPACE_PARAMS) or tuple(stats.shape) != (B, 3):
+        raise ValueError('kspace_apply: table must be [B,%d] and stats [B,3], got %r and %r'
+                         % (KSPACE_PARAMS, tuple(table.shape), tuple(stats.shape)))
+    N.call('mmseg_kspace_apply', spec, table, stats, B, H, W, C)
+    return spec
+
+
+def kspace_inverse(spec, table, stats, x, seed, batch, array):
+    """x[b] = fp32(lo_b + |numpy.fft.ifft2(spec[b]) + the Rician draw|) IN PLACE on x [B,H,W,C] for the flagged samples; the others are
+    neither read nor written.  spec [B,C,H,W,2] fp64 is overwritten (it is left half transformed).  Returns x.  No gradient."""
+    B, H, W, C = _kspace_check('kspace_inverse', x, table, stats)
+    if tuple(spec.shape) != (B, C, H, W, 2) or spec.dtype != torch.float64 or not spec.is_contiguous():
+        raise ValueError('kspace_inverse: spec must be a contiguous fp64 [B,C,H,W,2] = %r tensor, got %s %r'
+                         % ((B, C, H, W, 2), spec.dtype, tuple(spec.shape)))
+    N.call('mmseg_kspace_inverse', spec, table, stats, kspace_twiddles(H, W, x.device), x, _i32(seed), _i32(batch), _i32(array), B, H, W, C)
+    return x
+
+
+def kspace_spectrum_buffer(x):
+    """the [B,C,H,W,2] fp64 spectrum of x [B,H,W,C] as a view of the grow-only 'kspace' workspace: AugmentFlow's, one array at a time"""
+    B, H, W, C = x.shape
+    n = 2 * B * C * H * W
+    return _ws('kspace', n, x.device, torch.float64)[:n].view(B, C, H, W, 2)
+
+
 def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod, knots=None):
     """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
     (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,

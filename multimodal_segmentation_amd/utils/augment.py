@@ -24,6 +24,10 @@ same resampling: one field per batch, computed on the device from (seed, batch n
 
 MR intensity augmentation (INTENSITY_KEYS; build-defined, not keras) then changes the grey values of the IMAGE arrays of the gathered batch
 on the device: blur, bias field, contrast, gamma and noise, every image array with its own Philox draws (csrc/intensity.hip).
+
+MR k-space artefacts (KSPACE_KEYS; build-defined, not keras) come between the two: the image arrays of the gathered batch go to their 2-D
+spectrum on the device, get motion, ghosting, Gibbs truncation, spikes and Rician noise there and come back as magnitude images
+(csrc/kspace.hip); the intensity stage then works on that output.
 """
 import numpy as np
 import torch
@@ -126,6 +130,25 @@ INTENSITY_KEYS = ('gamma_range', 'gamma_prob', 'gamma_invert_prob', 'contrast_ra
                   'blur_sigma_range', 'blur_prob', 'bias_field_strength', 'bias_field_sigma', 'bias_field_prob', 'intensity_seed')
 
 
+# build-defined keys (not keras'): MR k-space artefacts of the image arrays, made in the 2-D spectrum of every slice after the gather and
+# BEFORE the intensity stage (csrc/kspace.hip; the rule: include/mmseg_hip.h), after TorchIO's RandomMotion / RandomGhosting / RandomSpike
+# and MONAI's GibbsNoise / KSpaceSpikeNoise / RicianNoise.  Drawn per sample and per image array (kspace_draws); everything is off by
+# default.  Unlike TorchIO, motion is an in-plane translation between segments of the acquisition (no rotated copies), and the output is the
+# magnitude about the sample's own minimum, lo + |ifft2(X)|, not the real part (TorchIO) or abs of the raw image (MONAI).
+#   motion_shift_max  0 (off): a segment is shifted by (2u - 1) * motion_shift_max pixels per axis      motion_segments  4, in [2, 8]
+#   ghost_count_range (lo, hi)  None (off): integers, 2 <= lo <= hi; every n-th phase-encode line is scaled by 1 - a
+#   ghost_intensity_range (lo, hi)  required with a count: a, 0 <= lo <= hi < 1
+#   gibbs_cutoff_range (lo, hi)  None (off): the kept fraction f of the spectrum's radius, 0 < lo <= hi <= 1
+#   spike_count_max  0 (off), in [0, 4]: 1 .. spike_count_max spikes, each with its mirror
+#   spike_intensity_range (lo, hi)  required with a count: the amplitude relative to the DC term, 0 < lo <= hi
+#   rician_std_max  0 (off): the std of the complex Gaussian is u * rician_std_max, in units of the [-1, 1] images
+#   motion_prob, ghost_prob, gibbs_prob, spike_prob, rician_prob  1.0
+#   kspace_phase_axis  0 (rows), 1 (columns) or 'random'          kspace_seed  the flow's seed: seed of the k-space stream
+KSPACE_KEYS = ('motion_shift_max', 'motion_segments', 'motion_prob', 'ghost_count_range', 'ghost_intensity_range', 'ghost_prob',
+               'gibbs_cutoff_range', 'gibbs_prob', 'spike_count_max', 'spike_intensity_range', 'spike_prob', 'rician_std_max', 'rician_prob',
+               'kspace_phase_axis', 'kspace_seed')
+
+
 # keras arguments outside the device path: accepted only at a value that switches them off
 _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center', 'featurewise_std_normalization',
                   'samplewise_std_normalization', 'zca_whitening', 'zca_epsilon', 'rescale', 'preprocessing_function', 'data_format')
@@ -134,7 +157,7 @@ _OFF_PATH_KEYS = ('brightness_range', 'featurewise_center', 'samplewise_center',
 def check_datagen_params(params):
     """ValueError with a clear message for a dict the device pipeline cannot honour exactly; returns the dict."""
     for k, v in params.items():
-        if k in DATAGEN_KEYS or k in ELASTIC_KEYS or k in INTENSITY_KEYS:
+        if k in DATAGEN_KEYS or k in ELASTIC_KEYS or k in INTENSITY_KEYS or k in KSPACE_KEYS:
             continue
         if k in _OFF_PATH_KEYS:
             if k == 'zca_epsilon' or v is None or v is False or (k == 'data_format' and v == 'channels_last') or \
@@ -159,6 +182,7 @@ def check_datagen_params(params):
         raise ValueError('fill_mode must be one of %s, got %r' % (', '.join(ops.FILL_MODES), fm))
     elastic_params(params)
     intensity_params(params)
+    kspace_params(params)
     return params
 
 
@@ -312,10 +336,147 @@ def intensity_tables(params, seed, draws, a):
     return blur, table, field
 
 
+def _pair(params, key, rule, ok):
+    """a (lo, hi) key with its own bounds: None, or a pair of finite numbers that `ok(lo, hi)` accepts"""
+    v = params.get(key, None)
+    if v is None:
+        return None
+    if not isinstance(v, (list, tuple, np.ndarray)) or len(v) != 2 or not all(_number(t) and np.isfinite(t) for t in v) or \
+            not ok(v[0], v[1]):
+        raise ValueError('%s must be None or a pair (lo, hi) of numbers with %s, got %r' % (key, rule, v))
+    return v[0], v[1]
+
+
+def kspace_params(params, seed=None):
+    """the KSPACE_KEYS of a datagen dict as a dict with every default filled in, validated: ValueError naming the key"""
+    p = dict(motion_prob=_prob(params, 'motion_prob', 1.0), ghost_prob=_prob(params, 'ghost_prob', 1.0),
+             gibbs_prob=_prob(params, 'gibbs_prob', 1.0), spike_prob=_prob(params, 'spike_prob', 1.0),
+             rician_prob=_prob(params, 'rician_prob', 1.0))
+    for key, unit in (('motion_shift_max', 'pixels'), ('rician_std_max', 'in units of the [-1, 1] images')):
+        v = params.get(key, 0)
+        if not _number(v) or not np.isfinite(v) or v < 0:
+            raise ValueError('%s must be a number >= 0 (%s), got %r' % (key, unit, v))
+        p[key] = float(v)
+    S = params.get('motion_segments', 4)
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 2 <= S <= ops.KSPACE_MAX_SEGMENTS:
+        raise ValueError('motion_segments must be an integer in [2, %d], got %r' % (ops.KSPACE_MAX_SEGMENTS, S))
+    p['motion_segments'] = int(S)
+    cnt = _pair(params, 'ghost_count_range', 'integers 2 <= lo <= hi', lambda lo, hi: 2 <= lo <= hi and all(
+        isinstance(t, (int, np.integer)) for t in (lo, hi)))
+    p['ghost_count'] = None if cnt is None else (int(cnt[0]), int(cnt[1]))
+    gi = _pair(params, 'ghost_intensity_range', '0 <= lo <= hi < 1', lambda lo, hi: 0 <= lo <= hi < 1)
+    p['ghost_intensity'] = None if gi is None else (float(gi[0]), float(gi[1]))
+    if cnt is not None and gi is None:
+        raise ValueError('ghost_intensity_range is required with a ghost_count_range')
+    gb = _pair(params, 'gibbs_cutoff_range', '0 < lo <= hi <= 1', lambda lo, hi: 0 < lo <= hi <= 1)
+    p['gibbs'] = None if gb is None else (float(gb[0]), float(gb[1]))
+    K = params.get('spike_count_max', 0)
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 0 <= K <= ops.KSPACE_MAX_SPIKES:
+        raise ValueError('spike_count_max must be an integer in [0, %d], got %r' % (ops.KSPACE_MAX_SPIKES, K))
+    p['spike_count_max'] = int(K)
+    si = _pair(params, 'spike_intensity_range', '0 < lo <= hi', lambda lo, hi: 0 < lo <= hi)
+    p['spike_intensity'] = None if si is None else (float(si[0]), float(si[1]))
+    if K and si is None:
+        raise ValueError('spike_intensity_range is required when spike_count_max != 0')
+    axis = params.get('kspace_phase_axis', 0)
+    if isinstance(axis, bool) or not (axis == 'random' if isinstance(axis, str) else (isinstance(axis, (int, np.integer)) and axis in (0, 1))):
+        raise ValueError("kspace_phase_axis must be 0 (rows), 1 (columns) or 'random', got %r" % (axis,))
+    p['axis'] = axis if isinstance(axis, str) else int(axis)
+    kseed = params.get('kspace_seed', None)
+    if kseed is not None and (isinstance(kseed, bool) or not isinstance(kseed, (int, np.integer))):
+        raise ValueError('kspace_seed must be an integer, got %r' % (kseed,))
+    p['seed'] = int((0 if seed is None else seed) if kseed is None else kseed)
+    return p
+
+
+def kspace_on(params):
+    """some k-space operation has a switched-on value and a non-zero probability"""
+    return any(bool(params.get(pk, 1.0)) and (params.get(k) is not None if k.endswith('range') else bool(params.get(k, 0))) for k, pk in (
+        ('motion_shift_max', 'motion_prob'), ('ghost_count_range', 'ghost_prob'), ('gibbs_cutoff_range', 'gibbs_prob'),
+        ('spike_count_max', 'spike_prob'), ('rician_std_max', 'rician_prob')))
+
+
+def kspace_draws(params, seed, batch, B, n_images, H, W):
+    """The k-space draws of batch number `batch` (counted from 0) for B samples of n_images image arrays of H x W, as numpy tables whose
+    first two axes are [n_images, B]: motion / ghost / gibbs / spike / rician (bool: the operation is on), axis (0 rows, 1 columns), breaks
+    [.., S-1] (sorted, int) and shifts [.., S, 2] (dy, dx in pixels; (0, 0) in the segment that holds k_p = 0), n and a of the ghosts,
+    f of the Gibbs cut, K and spikes [.., 4, 4] = (ky, kx, s, phi), std; values are 0 where their operation is off.
+    Q_j = Philox(counter (b, a, j, 4), key (kspace_seed, batch)), u(w) = (w >> 8) * 2^-24, P the extent of the phase-encode axis:
+        Q_0 = (p_motion, p_ghost, p_gibbs, p_spike)      Q_1 = (p_rician, u_std, u_axis, u_n)      Q_2 = (u_a, u_f, u_K, -)
+        Q_3, Q_4: the breaks, u_s = word (s - 1) % 4 of Q_{3 + (s - 1) // 4}, s = 1 .. S - 1; break = floor(u_s P)
+        Q_{5 + s // 2}: words 2 (s % 2), 2 (s % 2) + 1 = (u_dy, u_dx) of segment s = 0 .. S - 1; a shift is (2u - 1) motion_shift_max
+        Q_{9 + i} = (u_ky, u_kx, u_s, u_phi) of spike i < K: ky = floor(u H) - floor(H/2), kx likewise, phi = 2 pi u
+    on iff p < prob; axis = floor(2 u) when 'random'; n = lo + floor(u (hi - lo + 1)); a, f, s = lo + u (hi - lo); K = 1 + floor(u
+    spike_count_max); std = u rician_std_max.  Counter word 3 = 4 keeps these apart from the elastic field (0), the elastic scales (1),
+    the intensity draws (2) and the intensity noise (3); 5 is the Rician noise on the device.  numpy's global RNG is not touched."""
+    p = kspace_params(params, seed)
+    S = p['motion_segments']
+    d = dict({k: np.zeros((n_images, B), bool) for k in ('motion', 'ghost', 'gibbs', 'spike', 'rician')},
+             axis=np.zeros((n_images, B), np.int64), breaks=np.zeros((n_images, B, S - 1), np.int64), shifts=np.zeros((n_images, B, S, 2)),
+             n=np.zeros((n_images, B), np.int64), a=np.zeros((n_images, B)), f=np.zeros((n_images, B)), K=np.zeros((n_images, B), np.int64),
+             spikes=np.zeros((n_images, B, ops.KSPACE_MAX_SPIKES, 4)), std=np.zeros((n_images, B)))
+    for a in range(n_images):
+        for b in range(B):
+            words = {}
+
+            def u(j, w):
+                if j not in words:
+                    words[j] = philox4x32((b, a, j, 4), (p['seed'], batch))
+                return (words[j][w] >> 8) * 2.0 ** -24
+
+            axis = int(2 * u(1, 2)) if p['axis'] == 'random' else p['axis']
+            d['axis'][a, b] = axis
+            P = W if axis else H
+            if p['motion_shift_max'] and u(0, 0) < p['motion_prob']:
+                d['motion'][a, b] = True
+                d['breaks'][a, b] = sorted(int(np.floor(u(3 + (s - 1) // 4, (s - 1) % 4) * P)) for s in range(1, S))
+                zero = int((d['breaks'][a, b] <= P // 2).sum())
+                for s in range(S):
+                    if s != zero:
+                        d['shifts'][a, b, s] = [(2 * u(5 + s // 2, 2 * (s % 2) + i) - 1) * p['motion_shift_max'] for i in (0, 1)]
+            if p['ghost_count'] is not None and u(0, 1) < p['ghost_prob']:
+                (lo, hi), (alo, ahi) = p['ghost_count'], p['ghost_intensity']
+                d['ghost'][a, b], d['n'][a, b], d['a'][a, b] = True, lo + int(np.floor(u(1, 3) * (hi - lo + 1))), alo + u(2, 0) * (ahi - alo)
+            if p['gibbs'] is not None and u(0, 2) < p['gibbs_prob']:
+                d['gibbs'][a, b], d['f'][a, b] = True, p['gibbs'][0] + u(2, 1) * (p['gibbs'][1] - p['gibbs'][0])
+            if p['spike_count_max'] and u(0, 3) < p['spike_prob']:
+                K, (lo, hi) = 1 + int(np.floor(u(2, 2) * p['spike_count_max'])), p['spike_intensity']
+                d['spike'][a, b], d['K'][a, b] = True, K
+                for i in range(K):
+                    d['spikes'][a, b, i] = [int(np.floor(u(9 + i, 0) * H)) - H // 2, int(np.floor(u(9 + i, 1) * W)) - W // 2,
+                                            lo + u(9 + i, 2) * (hi - lo), 2.0 * np.pi * u(9 + i, 3)]
+            if p['rician_std_max'] and u(1, 0) < p['rician_prob']:
+                d['rician'][a, b], d['std'][a, b] = True, u(1, 1) * p['rician_std_max']
+    return d
+
+
+def kspace_tables(draws, a, H, W):
+    """the [B,48] fp64 table of ops.kspace_forward / kspace_apply / kspace_inverse for image array a of one batch, from kspace_draws'
+    `draws` (the columns: include/mmseg_hip.h), or None when no sample has an operation on"""
+    F = ops.KSPACE_FLAGS
+    flags = sum(F[k] * draws[k][a].astype(np.int64) for k in F)
+    if not flags.any():
+        return None
+    B, S = len(flags), draws['shifts'].shape[2]
+    t = np.zeros((B, ops.KSPACE_PARAMS), np.float64)
+    t[:, 0], t[:, 1] = flags, draws['axis'][a]
+    t[:, 2] = np.where(draws['motion'][a], S - 1, 0)
+    t[:, 3:3 + S - 1] = draws['breaks'][a]
+    t[:, 10:10 + 2 * S] = draws['shifts'][a].reshape(B, 2 * S)
+    t[:, 26], t[:, 27] = draws['n'][a], 1.0 - draws['a'][a]
+    t[:, 28] = draws['f'][a] * draws['f'][a] * (float(H) * H * W * W)
+    t[:, 29] = draws['K'][a]
+    sp = draws['spikes'][a]
+    t[:, 30:46] = np.stack([np.mod(sp[..., 0], H), np.mod(sp[..., 1], W), sp[..., 2] * np.cos(sp[..., 3]), sp[..., 2] * np.sin(sp[..., 3])],
+                           axis=-1).reshape(B, 16)
+    t[:, 46] = draws['std'][a]
+    return t
+
+
 def rotation_only(params):
     """True when RotationFlow reproduces the dict exactly: nothing but rotation_range, 'nearest' edges, no elastic deformation and no
-    intensity augmentation"""
-    return not elastic_on(params) and not intensity_on(params) and params.get('fill_mode', 'nearest') == 'nearest' and not any(
+    intensity or k-space augmentation"""
+    return not elastic_on(params) and not intensity_on(params) and not kspace_on(params) and params.get('fill_mode', 'nearest') == 'nearest' and not any(
         params.get(k) for k in ('width_shift_range', 'height_shift_range', 'shear_range', 'channel_shift_range',
                                 'horizontal_flip', 'vertical_flip')) and zoom_bounds(params.get('zoom_range', 0.) or 0.) == (1., 1.)
 
@@ -438,7 +599,11 @@ class AugmentFlow(object):
 
     With intensity augmentation on (INTENSITY_KEYS) the first n_images arrays are images: after the gather each of them is changed on the
     device with its own draws of batch k (intensity_draws: Philox, the global numpy RNG is untouched); the other arrays (masks) are not.
-    n_images = 0 (the default) leaves every array as gathered."""
+    n_images = 0 (the default) leaves every array as gathered.
+
+    With k-space augmentation on (KSPACE_KEYS) the same image arrays first pass through csrc/kspace.hip with their own draws of batch k
+    (kspace_draws; its own batch counter): the intensity stage then measures its statistics on the k-space output.  An (H, W) the
+    transform cannot take is refused here, at construction."""
 
     def __init__(self, arrays, batch_size, seed, device, params, order=1, n_images=0):
         self.device = torch.device(device)
@@ -470,9 +635,34 @@ class AugmentFlow(object):
         self.intensity_batch = 0
         if self.intensity is not None:
             intensity_params(*self.intensity)
+        self.kspace = (dict(params), seed) if kspace_on(params) and self.n_images else None
+        self.kspace_batch = 0
+        if self.kspace is not None:
+            kspace_params(*self.kspace)
+            for name, n in (('H', self.H), ('W', self.W)):
+                if not ops.kspace_extent_ok(n):
+                    raise ValueError('k-space augmentation: the extent %s = %d of the arrays cannot be transformed: an extent must lie in '
+                                     '[2, %d] and have no prime factor but 2, 3 and 5' % (name, n, ops.KSPACE_MAX_EXTENT))
 
     def __iter__(self):
         return self
+
+    def _kspace(self, out):
+        """motion, ghosting, Gibbs ringing, spikes and Rician noise on the leading image arrays of one gathered batch, in place"""
+        (params, seed), k = self.kspace, self.kspace_batch
+        self.kspace_batch += 1
+        draws = kspace_draws(params, seed, k, int(out[0].shape[0]), self.n_images, self.H, self.W)
+        kseed = kspace_params(params, seed)['seed']
+        for a in range(self.n_images):
+            table = kspace_tables(draws, a, self.H, self.W)
+            if table is None:          # no sample of this array is flagged: nothing is launched
+                continue
+            x, table = out[a], nn.host_to_device(table, self.device, np.float64)
+            stats = ops.intensity_stats(x)
+            spec = ops.kspace_forward(x, table, stats, ops.kspace_spectrum_buffer(x))
+            ops.kspace_apply(spec, table, stats)
+            ops.kspace_inverse(spec, table, stats, x, kseed, k, a)
+        return out
 
     def _intensity(self, out):
         """blur, bias field, contrast, gamma and noise on the leading image arrays of one gathered batch"""
@@ -511,6 +701,8 @@ class AugmentFlow(object):
             self.elastic_batch += 1
             gather = lambda a, r, m, *rest: ops.elastic_gather(a, r, m, disp, *rest)      # one field for every array of the batch
         out = tuple(gather(a, rows_d, mats[k], shifts[k], self.order, self.fill_mode, self.cval) for a, k in zip(self.arrays, self.keys))
+        if self.kspace is not None:
+            out = tuple(self._kspace(list(out)))
         if self.intensity is not None:
             out = tuple(self._intensity(list(out)))
         return out if len(out) > 1 else out[0]
