@@ -792,6 +792,56 @@ long mmseg_crf_refine_workspace_bytes(int N, int H, int W, int K);
 int mmseg_crf_refine(const float* prob, const float* image, float* out, void* ws, int N, int H, int W, int C, int K, int radius,
                      int iterations, float w_a, float theta_alpha, float theta_beta, float w_s, float theta_gamma, void* stream);
 
+/* ---- bias-field (coil shading) correction of one MR volume (csrc/biasfield.hip; build-defined: the reference loads CHAOS as exported) ----
+ * An N3 / N4-family rule: Sled's log-domain histogram sharpening in the form of N4's SharpenImage.  One deliberate departure: the
+ * residual is smoothed by a masked, normalised Gaussian convolution in mm, not by a B-spline fit; the levels halve the Gaussian's width
+ * where N4 doubles the spline mesh; nothing is shrunk.  Nearest-bin integer counts replace N4's two-bin split, so that integer atomics
+ * give the same counts every run.  Iteration counts are fixed: no convergence test, nothing comes back to the host, two runs are bitwise
+ * equal.  x [S,H,W] fp32 (finite), n = S * H * W < 2^31 - 1, S, H, W <= 65535.  B = 200 bins, P = 512, offset = (P - B) / 2, fwhm 0.15,
+ * noise 0.01.  All arithmetic fp64, one rounding to fp32 at the end.
+ *   mask       lo, hi = min, max of x.  256-bin histogram, bin min(floor((x - lo) * (256 / (hi - lo))), 255), integer counts n_j.  Over the
+ *              cuts after bin t = 0 .. 254: w0 = sum_{j<=t} n_j, w1 = N - w0, s0 = sum_{j<=t} j n_j, s1 = sum_j j n_j - s0 (integers);
+ *              var = (w0 * w1) * (d * d), d = s0 / w0 - s1 / w1, 0 when w0 or w1 is 0; the first maximum wins.  threshold =
+ *              max(lo + ((t + 1) * (hi - lo)) / 256, 0); m = x > threshold; v0 = log(x) on the mask.  f = 0.
+ *   level l    sigma_axis = sigma_mm / 2^l / d_axis voxels, radius R = int(4 sigma + 0.5), weights w_k = exp(-0.5 k^2 / sigma^2) / sum
+ *              (scipy.ndimage's normalised kernel, made by the host).  G * y = the separable convolution along W, then H, then S (not S
+ *              when the extent is 2d: Rs = 0), zero outside the volume, each pass w_0 y_0 + sum_k w_k (y_-k + y_+k), k ascending.
+ *              den = G * m once per level.
+ *   iteration  v = v0 - f on the mask; vmin, vmax over the mask; slope = (vmax - vmin) / (B - 1); c = (v - vmin) / slope;
+ *              Hh[floor(c + 0.5)] += 1.  V = Hh at offset in a zero array of P; F[n] = (2 sqrt(ln 2 / pi) / w) exp(-(n'^2 4 ln 2) / w^2),
+ *              w = fwhm / slope, n' = min(n, P - n); G = conj(F^) / (|F^|^2 + noise); U = max(Re ifft(V^ Re G), 0); b_j = vmin +
+ *              (j - offset) slope; E = Re ifft(fft(U b) F^) / Re ifft(fft(U) F^), 0 where the denominator is 0, entries offset ..
+ *              offset + B - 1 kept.  e = E[i] + (c - i) (E[i+1] - E[i]), i = min(floor(c), B - 2); r = v - e on the mask, 0 elsewhere;
+ *              f += (G * r) / den where den > 0.  vmax == vmin (or an empty mask): this iteration and all later ones change nothing.
+ *   output     x = fp32(fp64(x) * exp(-f)) at every voxel, in place.  A volume that is constant, whose mask is empty or whose masked
+ *              values are all equal keeps its bits: no kernel writes it.
+ * The sharpen runs in one block: five 512-point radix-2 Stockham transforms (U b + i U share one) over roots [512,2] fp64 = (cos, sin)
+ * (2 pi q / 512) made by the host.  weights [3,129] fp64: rows for S, H, W, w_0 .. w_R each.  1 <= R <= 128 per smoothed axis (R may exceed
+ * the extent of the axis; taps outside contribute nothing), Rs = 0 skips the pass along S; anything else, a null pointer or a shape outside
+ * the limits is refused (hipErrorInvalidValue, nothing is launched).  Buffers are the caller's; no host synchronisation, allocation or
+ * copy; integer atomics only. */
+/* doubles of ws for the entry points below (the state, six fp64 volumes, the mask); 0 for a shape they refuse */
+long mmseg_bias_workspace_doubles(int S, int H, int W);
+/* the stages on their own.  otsu: out [4] fp64 = lo, hi, threshold, 1 when the volume is constant (ws: 512 doubles suffice) */
+int mmseg_bias_otsu(const float* x, double* ws, double* out, int S, int H, int W, void* stream);
+/* v [n] fp64, mask [n] uint8 -> hist [200] int32, range [2] fp64 = vmin, vmax over the mask (NaN when it is empty; ws: 512 doubles) */
+int mmseg_bias_histogram(const double* v, const unsigned char* mask, double* ws, int* hist, double* range, long n, void* stream);
+/* hist [200] int32, range [2] fp64 -> E [200] fp64 (zeros when range[1] <= range[0]; ws: 512 doubles) */
+int mmseg_bias_sharpen(const int* hist, const double* range, const double* roots, double* ws, double* E, void* stream);
+/* out [S,H,W] fp64 = G * in; tmp: 2 n doubles; out may be in, tmp may be neither */
+int mmseg_bias_smooth(const double* in, double* out, double* tmp, const double* weights, int S, int H, int W, int Rs, int Rr, int Rc,
+                      void* stream);
+/* f [n] += num / den where den > 0 */
+int mmseg_bias_update(double* f, const double* num, const double* den, long n, void* stream);
+/* the correction: begin (mask, v0, f = 0), one call of level per level (den, then `iterations` iterations; 1 + 3 + 8 * iterations launches,
+ * one pass fewer each time when Rs = 0), finish (x in place) -- all on one stream with the same ws. */
+int mmseg_bias_begin(const float* x, double* ws, int S, int H, int W, void* stream);
+int mmseg_bias_level(double* ws, const double* roots, const double* weights, int S, int H, int W, int Rs, int Rr, int Rc, int iterations,
+                     void* stream);
+int mmseg_bias_finish(float* x, const double* ws, int S, int H, int W, void* stream);
+/* field [S,H,W] fp64 = f (zeros for a volume that keeps its bits); info [2] int32 = (frozen, iterations that updated f), or null */
+int mmseg_bias_field(const double* ws, double* field, int* info, int S, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
                          [--test_dataset chaos] [--automatedpairing b] [--randomise b]
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--intensity_norm minmax|window] [--intensity_scope slice|volume] [--intensity_percentiles LO,HI]
+                         [--bias_correction off|n3] [--bias_sigma_mm MM] [--bias_levels N] [--bias_iterations N] [--bias_extent 2d|3d]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
@@ -73,6 +74,15 @@ def parse_arguments(argv=None):
     ap.add_argument('--intensity_scope', choices=['slice', 'volume'], help='the window of --intensity_norm window is taken per slice / '
                                                                            'per volume (default: volume)')
     ap.add_argument('--intensity_percentiles', metavar='LO,HI', help='the window of --intensity_norm window (default: 0.5,99.5)')
+    ap.add_argument('--bias_correction', choices=['off', 'n3'],
+                    help='bias-field correction of every volume folder of the run at load time, instead of what their dataset.json say '
+                         '(n3: log-domain histogram sharpening with a masked Gaussian smoother, on the device)')
+    ap.add_argument('--bias_sigma_mm', type=float, help='width of the smoothing Gaussian of --bias_correction n3 at the first level, in mm '
+                                                        '(default 40, an untuned starting value)')
+    ap.add_argument('--bias_levels', type=int, help='levels of --bias_correction n3, each halving the width (default 3, untuned)')
+    ap.add_argument('--bias_iterations', type=int, help='iterations per level of --bias_correction n3 (default 20, untuned)')
+    ap.add_argument('--bias_extent', choices=['2d', '3d'], help='--bias_correction n3 smooths within slices / also across them (default: 3d '
+                                                                'where the files hold slice_spacing)')
     ap.add_argument('--predict_folder', help='folder of exported volumes (labels optional) to write predicted label volumes for')
     ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
     ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
@@ -116,6 +126,8 @@ def parse_arguments(argv=None):
     args = ap.parse_args(argv)
     if (args.intensity_scope or args.intensity_percentiles) and args.intensity_norm != 'window':
         ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
+    if any(getattr(args, a) is not None for a, _ in BIAS_ARGS) and args.bias_correction != 'n3':
+        ap.error('--bias_sigma_mm, --bias_levels, --bias_iterations and --bias_extent go with --bias_correction n3')
     if args.intensity_percentiles is not None:
         try:
             args.intensity_percentiles = [float(v) for v in args.intensity_percentiles.split(',')]
@@ -248,6 +260,48 @@ def warn_predict_intensity(conf, folder, log):
     return True
 
 
+BIAS_ARGS = (('bias_sigma_mm', 'sigma_mm'), ('bias_levels', 'levels'), ('bias_iterations', 'iterations'), ('bias_extent', 'extent'))
+
+
+def bias_override(named, args):
+    """the `bias_field` block of `--bias_correction` and its four companions, else the configuration's `bias_field`, else None: no
+    override, every folder follows its own dataset.json"""
+    from .loaders.volume_folder import check_bias
+    block, where = named.get('bias_field'), 'conf.bias_field'
+    if getattr(args, 'bias_correction', None):
+        block, where = {'mode': args.bias_correction}, '--bias_correction'
+        for arg, key in BIAS_ARGS:
+            if getattr(args, arg, None) is not None:
+                block[key] = getattr(args, arg)
+    if block is None:
+        return None
+    return check_bias(dict(block), where)
+
+
+def register_bias(named, args, names):
+    """Fill loaders.bias_conf for the data set names of this run; without an override their entries are removed"""
+    from .loaders import bias_conf
+    block = bias_override(named, args)
+    for name in names:
+        if block is None:
+            bias_conf.pop(name, None)
+        else:
+            bias_conf[name] = dict(block)
+    return block
+
+
+def warn_predict_bias(conf, folder, log):
+    """a warning when the bias_field setting in force for the predict folder differs from the one the run folder records
+    (conf.bias_field; a run on the synthetic volumes records none: off).  True when it warned."""
+    from .loaders.volume_folder import effective_bias
+    trained, here = conf.get('bias_field') or {'mode': 'off'}, effective_bias(folder)
+    if here == trained:
+        return False
+    log.warning('--predict_folder: the bias field of %s is set to %s, the run folder %s records %s: the model sees other shading than it '
+                'was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
+    return True
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
@@ -265,10 +319,12 @@ class Experiment(object):
             from .loaders.volume_folder import read_manifest
             names.add(read_manifest(args.predict_folder)['name'])
         register_intensity(conf, args, sorted(names))      # before a loader that loads volumes is built: it reads its setting then
+        register_bias(conf, args, sorted(names))
         if data_conf.get(conf.dataset_name):
             conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
-            from .loaders.volume_folder import effective_intensity
+            from .loaders.volume_folder import effective_bias, effective_intensity
             conf.intensity = effective_intensity(conf.data_folder)  # the setting in force, override or dataset.json: recorded too
+            conf.bias_field = effective_bias(conf.data_folder)
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')
@@ -335,6 +391,7 @@ class Experiment(object):
                                     '--test)' % conf.folder)
         if dp.is_main():
             warn_predict_intensity(conf, args.predict_folder, self.log)
+            warn_predict_bias(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()

@@ -8,7 +8,11 @@ it.  It starts empty, so every configuration trains on the synthetic volumes; `e
 `intensity_conf` (build-defined) sits beside it and is keyed like it: data set name -> an `intensity` block in the form of
 dataset.json's that overrides the block of the folder registered under that name (or of the folder whose dataset.json carries that
 name).  `experiment.py --intensity_norm ...` (or `conf.intensity`) fills it for every folder of a run; it starts empty, so each
-folder is normalised as its own dataset.json says."""
+folder is normalised as its own dataset.json says.
+
+`bias_conf` (build-defined) does the same for the `bias_field` block (bias-field correction at load time): `experiment.py
+--bias_correction ...` (or `conf.bias_field`) fills it; empty, each folder follows its own dataset.json."""
 
 data_conf = {}
 intensity_conf = {}
+bias_conf = {}

@@ -9,8 +9,8 @@ device (csrc/preprocess.hip).  Reading DICOM / PNG stays out of scope: a folder 
     <root>/<name>.npz        image [S,H,W] (any integer or float dtype), label [S,H,W] uint8 grey values, resolution [2] mm per
                              pixel along rows and columns.  `label` may be missing in a folder that is only predicted on
                              (load_volume_for_prediction, volume_predictor.py); the training surface then refuses the file.
-                             `slice_spacing` (optional): one positive float, mm between consecutive slices of the file.  Only the
-                             scores in mm of volume_predictor.py use it; training, validation and testing ignore it.
+                             `slice_spacing` (optional): one positive float, mm between consecutive slices of the file.  The
+                             scores in mm of volume_predictor.py and a 3-D `bias_field` use it; nothing else does.
 
 `slices` (optional) lists [start, stop) ranges applied in order: how a user states which slices of the acquisitions show the same
 anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all modalities of a volume must hold the same number of
@@ -27,6 +27,14 @@ slice's) resampled values and rescale.  {"mode": "landmarks", "percentiles": [..
 linearly onto the scale that tools/fit_intensity_landmarks.py learned from the training volumes.  The percentiles are exact order
 statistics selected on the device (ops.preprocess_quantiles, once per uploaded volume and modality: `intensity_knots`); the
 definition is in include/mmseg_hip.h.  loaders.intensity_conf overrides the key for a run (experiment.py --intensity_norm).
+
+`bias_field` (optional key of dataset.json; build-defined) removes coil shading before the grey values are normalised.  Absent or
+{"mode": "off"}: the slices are used as exported.  {"mode": "n3", "sigma_mm": 40, "levels": 3, "iterations": 20, "extent": "3d" | "2d"}
+(the defaults are untuned starting values; `extent` defaults to "3d" where a file holds `slice_spacing`, else "2d"): an N3 / N4-family
+correction (ops.bias_correct; the rule is in include/mmseg_hip.h) of the selected raw slices, once per uploaded (volume, modality), in
+`bias_corrected` -- before `intensity_knots`, so the percentiles are those of the corrected volume, and training, validation, testing,
+prediction, tiles and TTA all see the same volume.  "3d" needs `slice_spacing` and one contiguous run of slices.
+loaders.bias_conf overrides the key for a run (experiment.py --bias_correction).
 
 For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
 frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
@@ -213,6 +221,47 @@ def effective_intensity(root, manifest=None):
     return check_intensity(m.get('intensity'), m['modalities'], os.path.join(root, MANIFEST))
 
 
+BIAS_MODES = ('off', 'n3')
+
+
+def check_bias(block, where):
+    """The normalised form of a `bias_field` block (dataset.json, conf.bias_field): {'mode': 'off'}, or {'mode': 'n3', 'sigma_mm',
+    'levels', 'iterations', 'extent'} with ops.BIAS_DEFAULTS filled in -- except `extent`, which stays None when the block names none:
+    the loader takes '3d' where the files hold a slice_spacing, else '2d'.  None and {} mean 'off'."""
+    if block is None:
+        return {'mode': 'off'}
+    if not isinstance(block, dict):
+        raise ValueError('%s: "bias_field" must be an object, got %r' % (where, block))
+    mode = block.get('mode', 'off')
+    if mode not in BIAS_MODES:
+        raise ValueError('%s: "bias_field" mode must be one of %s, got %r' % (where, ', '.join(BIAS_MODES), mode))
+    unknown = sorted(set(block) - {'mode', 'sigma_mm', 'levels', 'iterations', 'extent'})
+    if unknown:
+        raise ValueError('%s: "bias_field" has unknown key(s) %s' % (where, ', '.join(unknown)))
+    if mode == 'off':
+        if set(block) - {'mode'}:
+            raise ValueError('%s: "bias_field" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
+        return {'mode': 'off'}
+    given = {k: v for k, v in block.items() if k != 'mode' and not (k == 'extent' and v is None)}
+    p = ops.bias_params(given, '%s: "bias_field"' % where)
+    if 'extent' not in given:
+        p['extent'] = None
+    return dict(mode='n3', **p)
+
+
+def effective_bias(root, manifest=None):
+    """the normalised bias_field setting of the folder `root`: the override registered in loaders.bias_conf under a data set name that
+    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
+    from . import bias_conf, data_conf
+    m = read_manifest(root) if manifest is None else manifest
+    here = os.path.abspath(root)
+    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
+    for n in names:
+        if bias_conf.get(n) is not None:
+            return check_bias(bias_conf[n], 'loaders.bias_conf[%r]' % n)
+    return check_bias(m.get('bias_field'), os.path.join(root, MANIFEST))
+
+
 def read_manifest(root):
     path = os.path.join(root, MANIFEST)
     if not os.path.isfile(path):
@@ -244,6 +293,7 @@ def read_manifest(root):
             if mod not in entry or 'file' not in entry[mod]:
                 raise ValueError('%s: volume %s has no file for modality %r' % (path, v, mod))
     check_intensity(m.get('intensity'), m['modalities'], path)
+    check_bias(m.get('bias_field'), path)
     return m
 
 
@@ -262,6 +312,7 @@ class VolumeFolderLoader(object):
         self.processed_folder = None
         self.log = log
         self.intensity = effective_intensity(root, m)          # build-defined: {'mode': 'minmax'} is the reference's rescale
+        self.bias_field = effective_bias(root, m)              # build-defined: {'mode': 'off'} uploads the slices as they are
 
     # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
     def splits(self):
@@ -343,6 +394,30 @@ class VolumeFolderLoader(object):
         y = setting['standard'][modality] if setting['mode'] == 'landmarks' else (-1.0, 1.0)
         return knots, nn.host_to_device(np.asarray(y), x.device, np.float32)
 
+    def bias_extent(self, spacing, selected, what):
+        """'2d' or '3d' for one file under the folder's bias_field setting: the configured extent, else '3d' where the file holds a
+        slice_spacing.  '3d' needs that spacing and one contiguous run of slices, and says so."""
+        extent = self.bias_field['extent'] or ('3d' if spacing is not None else '2d')
+        if extent == '3d':
+            if spacing is None:
+                raise ValueError('%s: "bias_field" extent 3d needs a slice_spacing (mm between slices) in every file; this one holds '
+                                 'none -- add it, or set "extent": "2d"' % what)
+            if selected is not None and len(selected) > 1 and np.any(np.diff(selected) != 1):
+                raise ValueError('%s: "bias_field" extent 3d needs one contiguous run of slices, but "slices" selects %d that are not '
+                                 'consecutive -- set "extent": "2d"' % (what, len(selected)))
+        return extent
+
+    def bias_corrected(self, x, res, spacing=None, selected=None, what='volume'):
+        """The raw slices x [S,H,W] of one (volume, modality) on the device, as the rest of the loader shall see them: x itself when
+        bias_field is off, else a corrected copy (ops.bias_correct; the selected slices only).  The one place where this is decided:
+        preprocess, load_volume_for_prediction and upload_volume call it once per upload, before intensity_knots."""
+        setting = self.bias_field
+        if setting['mode'] == 'off' or x.shape[0] == 0:
+            return x
+        extent = self.bias_extent(spacing, selected, what)
+        params = dict(sigma_mm=setting['sigma_mm'], levels=setting['levels'], iterations=setting['iterations'], extent=extent)
+        return ops.bias_correct(x, (spacing if extent == '3d' else 1.0, float(res[0]), float(res[1])), params)
+
     def load_volume_for_prediction(self, volume):
         """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
         [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
@@ -359,7 +434,8 @@ class VolumeFolderLoader(object):
                 selected = np.arange(S_file)
             resampled, rows, cols = self.geometry(H, W, res)
             container = torch.zeros((len(selected), OH, OW, 1), dtype=torch.float32, device=device)
-            x = nn.host_to_device(image[selected], device, np.float32)
+            x = self.bias_corrected(nn.host_to_device(image[selected], device, np.float32), res, spacing, selected,
+                                    'volume %s, modality %s' % (volume, mod))
             ops.preprocess_images(x, container, resampled, rows, cols, 0, knots=self.intensity_knots(x, resampled, mod))
             images.append(container)
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
@@ -386,7 +462,8 @@ class VolumeFolderLoader(object):
             if selected is None:
                 selected = np.arange(S_file)
             resampled, rows, cols = self.geometry(H, W, res)
-            raw.append(nn.host_to_device(image[selected], device, np.float32))
+            raw.append(self.bias_corrected(nn.host_to_device(image[selected], device, np.float32), res, spacing, selected,
+                                           'volume %s, modality %s' % (volume, mod)))
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
                                  label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing,
@@ -426,9 +503,14 @@ class VolumeFolderLoader(object):
     # ---- the reference's loading surface --------------------------------------------------------------------------------------
     def load_all_modalities_concatenated(self, split, split_type, downsample=1):
         volumes = self.get_volumes_for_split(split, split_type)
-        raw, index = [], []
+        raw, index, extras = [], [], []
         for v in volumes:
-            per_mod = [self.read_volume(v, mod) for mod in self.modalities]
+            per_mod, extra = [], []
+            for mod in self.modalities:
+                image, label, res, selected, spacing = self._read_file(v, mod, True)
+                per_mod.append((image, label, res) if selected is None else (image[selected], label[selected], res))
+                extra.append((spacing, selected, 'volume %s, modality %s' % (v, mod)))
+            extras.append(extra)
             counts = [p[0].shape[0] for p in per_mod]
             if len(set(counts)) != 1:
                 raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the '
@@ -437,11 +519,13 @@ class VolumeFolderLoader(object):
             raw.append(per_mod)
             index.append(np.array([v] * counts[0]))
         index = np.concatenate(index, axis=0) if index else np.zeros((0,), np.int64)
-        images, masks = self.preprocess(raw, len(index))
+        images, masks = self.preprocess(raw, len(index), extras)
         return MultimodalPairedData(images, masks, index, downsample=downsample, num_modalities=len(self.modalities))
 
-    def preprocess(self, raw, n):
-        """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks]"""
+    def preprocess(self, raw, n, extras=None):
+        """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks].
+        extras: per volume, per modality (slice_spacing or None, the selected file indices or None, a name for messages): what
+        bias_corrected needs beyond the resolution; without it the slices count as one run of a file without slice_spacing."""
         device = nn.default_device()
         OH, OW = self.input_shape[:2]
         M, K = len(self.modalities), self.num_masks
@@ -449,7 +533,7 @@ class VolumeFolderLoader(object):
         masks = torch.zeros((n, OH, OW, M * K), dtype=torch.float32, device=device)
         values = nn.host_to_device(np.asarray(self.label_values), device, np.int32)
         n0 = 0
-        for per_mod in raw:
+        for vol, per_mod in enumerate(raw):
             S = per_mod[0][0].shape[0]
             for mod, (image, label, res) in enumerate(per_mod):
                 H, W = image.shape[1:]
@@ -457,7 +541,8 @@ class VolumeFolderLoader(object):
                 RW = resampled_size(W, res[1], self.target_resolution[1])
                 if RH < 1 or RW < 1:
                     raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
-                x = nn.host_to_device(image, device, np.float32)
+                x = self.bias_corrected(nn.host_to_device(image, device, np.float32), res,
+                                        *(extras[vol][mod] if extras is not None else (None, None, 'modality %s' % self.modalities[mod])))
                 ops.preprocess_volume(x, nn.host_to_device(label, device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
                                       (RH, RW), crop_pad_map(RH, OH), crop_pad_map(RW, OW), mod,
                                       knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))

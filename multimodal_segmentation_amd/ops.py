@@ -1936,6 +1936,171 @@ def kspace_spectrum_buffer(x):
     return _ws('kspace', n, x.device, torch.float64)[:n].view(B, C, H, W, 2)
 
 
+BIAS_DEFAULTS = dict(sigma_mm=40.0, levels=3, iterations=20, extent='3d')          # untuned starting values (README)
+BIAS_EXTENTS = ('2d', '3d')
+BIAS_BINS, BIAS_PAD = 200, 512                                                     # BF_BINS, BF_PAD of csrc/biasfield.hip
+BIAS_MAX_RADIUS = 128                                                              # BF_MAXR
+BIAS_TRUNCATE = 4.0
+BIAS_MAX_LEVELS, BIAS_MAX_ITERATIONS = 8, 1000
+BIAS_AXES = ('slice', 'row', 'column')
+_bias_tables = {}
+
+
+def bias_params(params=None, what='bias_correct'):
+    """BIAS_DEFAULTS overlaid with `params`, validated: sigma_mm finite > 0, levels in 1..8, iterations in 1..1000, extent 2d | 3d"""
+    p = dict(BIAS_DEFAULTS)
+    unknown = sorted(set(params or {}) - set(p))
+    if unknown:
+        raise ValueError('%s: unknown key(s) %s (known: %s)' % (what, ', '.join(unknown), ', '.join(sorted(p))))
+    p.update(params or {})
+    s = p['sigma_mm']
+    if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not np.isfinite(s) or s <= 0:
+        raise ValueError('%s: sigma_mm must be a finite number of mm > 0, got %r' % (what, s))
+    for key, top in (('levels', BIAS_MAX_LEVELS), ('iterations', BIAS_MAX_ITERATIONS)):
+        v = p[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
+            raise ValueError('%s: %s must be a whole number in 1..%d, got %r' % (what, key, top, v))
+    if p['extent'] not in BIAS_EXTENTS:
+        raise ValueError('%s: extent must be one of %s, got %r' % (what, ', '.join(BIAS_EXTENTS), p['extent']))
+    return dict(sigma_mm=float(s), levels=int(p['levels']), iterations=int(p['iterations']), extent=p['extent'])
+
+
+def bias_sigmas(spacings, params):
+    """per level the (sigma, radius) in voxels of the slice, row and column axis: sigma_mm / 2^l / d_axis and int(4 sigma + 0.5); the slice
+    axis of extent 2d gets (0.0, 0).  A radius outside 1..128 is refused with the sigma_mm that would fit."""
+    d = [float('nan') if v is None else float(v) for v in spacings]
+    if len(d) != 3 or any(not np.isfinite(v) or v <= 0 for v in d[(1 if params['extent'] == '2d' else 0):]):
+        raise ValueError('bias_correct: spacings must be three finite numbers of mm > 0 (slices, rows, columns), got %r' % (spacings,))
+    out = []
+    for l in range(params['levels']):
+        level = []
+        for a in range(3):
+            if a == 0 and params['extent'] == '2d':
+                level.append((0.0, 0))
+                continue
+            sigma = params['sigma_mm'] / 2.0 ** l / d[a]
+            R = int(BIAS_TRUNCATE * sigma + 0.5)
+            if R > BIAS_MAX_RADIUS:
+                raise ValueError('bias_correct: sigma_mm %g at a %s spacing of %g mm needs a radius of %d voxels at level %d, more than the '
+                                 '%d the kernels take: sigma_mm <= %g fits' % (params['sigma_mm'], BIAS_AXES[a], d[a], R, l, BIAS_MAX_RADIUS,
+                                                                               2.0 ** l * 32.0 * d[a]))
+            if R < 1:
+                raise ValueError('bias_correct: sigma_mm %g at a %s spacing of %g mm leaves a radius of 0 voxels at level %d of %d: '
+                                 'sigma_mm >= %g fits (or fewer levels)' % (params['sigma_mm'], BIAS_AXES[a], d[a], l, params['levels'],
+                                                                           2.0 ** l * 0.125 * d[a]))
+            level.append((sigma, R))
+        out.append(level)
+    return out
+
+
+def bias_weight_rows(level):
+    """[3, 129] fp64 on the host: per axis w_0 .. w_R of scipy.ndimage's normalised Gaussian kernel, zeros beyond R (and for R = 0)"""
+    rows = np.zeros((3, BIAS_MAX_RADIUS + 1), np.float64)
+    for a, (sigma, R) in enumerate(level):
+        if R:
+            k = np.arange(-R, R + 1)
+            w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+            rows[a, :R + 1] = (w / w.sum())[R:]
+    return rows
+
+
+def bias_roots(device):
+    """the [512, 2] fp64 root table of the sharpen's transforms on `device`, made by the host once per device and kept"""
+    device = torch.device(device)
+    key = ('roots', device)
+    if key not in _bias_tables:
+        _bias_tables[key] = torch.from_numpy(kspace_roots(BIAS_PAD)).to(device)
+    return _bias_tables[key]
+
+
+def bias_weights(level, device):
+    """bias_weight_rows(level) on `device`, kept per (level, device)"""
+    device = torch.device(device)
+    key = (tuple(level), device)
+    if key not in _bias_tables:
+        _bias_tables[key] = torch.from_numpy(bias_weight_rows(level)).to(device)
+    return _bias_tables[key]
+
+
+def _bias_ws(S, H, W, device):
+    n = N.call('mmseg_bias_workspace_doubles', S, H, W)
+    if not n:
+        raise ValueError('bias_correct: a volume of %d x %d x %d is outside the kernels\' limits (extents in 1..65535, fewer than 2^31 - 1 '
+                         'voxels)' % (S, H, W))
+    return _ws('bias', n, device, torch.float64)
+
+
+def bias_correct(x, spacings, params=None, out=None, field=False):
+    """Bias-field correction of x [S,H,W] fp32 on the device (csrc/biasfield.hip; the rule is in include/mmseg_hip.h): spacings = mm
+    between slices, rows, columns (the first is not read with extent 2d); params: keys of BIAS_DEFAULTS.  The result is written into
+    `out` (a new tensor by default; out=x corrects in place) and returned; a volume the rule leaves alone keeps its bits.  field=True
+    returns (out, f [S,H,W] fp64, (frozen, updates)) with the estimated log-field.  No host synchronisation, no gradient."""
+    p = bias_params(params)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('bias_correct: x must be a contiguous fp32 [S,H,W] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+    S, H, W = x.shape
+    levels = bias_sigmas(spacings, p)
+    if out is None:
+        out = x.clone()
+    elif out is not x:
+        if out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous():
+            raise ValueError('bias_correct: out must be like x, got %s %s' % (out.dtype, tuple(out.shape)))
+        out.copy_(x)
+    if S * H * W == 0:
+        return (out, _new(x.shape, x, torch.float64), (1, 0)) if field else out
+    ws = _bias_ws(S, H, W, x.device)
+    roots = bias_roots(x.device)
+    N.call('mmseg_bias_begin', out, ws, S, H, W)
+    for level in levels:
+        N.call('mmseg_bias_level', ws, roots, bias_weights(level, x.device), S, H, W, level[0][1], level[1][1], level[2][1], p['iterations'])
+    N.call('mmseg_bias_finish', out, ws, S, H, W)
+    if not field:
+        return out
+    f, info = _new(x.shape, x, torch.float64), _new((2,), x, torch.int32)
+    N.call('mmseg_bias_field', ws, f, info, S, H, W)
+    return out, f, info
+
+
+def bias_otsu(x):
+    """[4] fp64 on the device: lo, hi, the Otsu threshold of x [S,H,W] fp32 after max(., 0), and 1 when x is constant"""
+    S, H, W = x.shape
+    out = _new((4,), x, torch.float64)
+    N.call('mmseg_bias_otsu', _c(x), _bias_ws(S, H, W, x.device), out, S, H, W)
+    return out
+
+
+def bias_histogram(v, mask):
+    """(hist [200] int32, range [2] fp64 = vmin, vmax) of the fp64 values v under the uint8 mask: nearest bin of (v - vmin) / slope"""
+    n = v.numel()
+    hist, rng = _new((BIAS_BINS,), v, torch.int32), _new((2,), v, torch.float64)
+    N.call('mmseg_bias_histogram', _c(v), _c(mask), _ws('bias', 512, v.device, torch.float64), hist, rng, n)
+    return hist, rng
+
+
+def bias_sharpen(hist, rng):
+    """E [200] fp64: the sharpened histogram's expectation per bin (the rule's `E`), from the counts and (vmin, vmax)"""
+    E = _new((BIAS_BINS,), hist, torch.float64)
+    N.call('mmseg_bias_sharpen', hist, rng, bias_roots(hist.device), _ws('bias', 512, hist.device, torch.float64), E)
+    return E
+
+
+def bias_smooth(y, level):
+    """G * y for y [S,H,W] fp64 and one level of bias_sigmas: a new tensor"""
+    S, H, W = y.shape
+    out, tmp = _new(y.shape, y, torch.float64), _new((2,) + tuple(y.shape), y, torch.float64)
+    for a in range(3):
+        if not (0 if a == 0 else 1) <= level[a][1] <= BIAS_MAX_RADIUS:
+            raise ValueError('bias_smooth: the %s radius must lie in %d..%d, got %d' % (BIAS_AXES[a], 0 if a == 0 else 1, BIAS_MAX_RADIUS, level[a][1]))
+    N.call('mmseg_bias_smooth', _c(y), out, tmp, bias_weights(level, y.device), S, H, W, level[0][1], level[1][1], level[2][1])
+    return out
+
+
+def bias_update(f, num, den):
+    """f += num / den where den > 0, in place on f (fp64); returns f"""
+    N.call('mmseg_bias_update', f, _c(num), _c(den), f.numel())
+    return f
+
+
 def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod, knots=None):
     """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
     (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,

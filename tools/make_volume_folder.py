@@ -11,6 +11,7 @@ ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
                                        [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI] [--hot_voxels N]
+                                       [--bias_field STRENGTH]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -59,6 +60,21 @@ def add_hot_voxels(rng, image, count):
     return np.round(out).astype(np.int16)
 
 
+def add_bias_field(rng, image, strength, res, spacing):
+    """image [S,H,W] int16 lifted by 10 % of its maximum (tissue must be brighter than air for the shading to show) and multiplied by
+    exp(f), f a smooth field in mm of amplitude `strength` (a plane plus a bowl, drawn per file): coil shading, what the `bias_field`
+    block of dataset.json removes.  Rounded back to int16."""
+    S, H, W = image.shape
+    z, y, x = np.meshgrid((np.arange(S) - (S - 1) / 2.0) * (spacing or 1.0), (np.arange(H) - (H - 1) / 2.0) * res[0],
+                          (np.arange(W) - (W - 1) / 2.0) * res[1], indexing='ij')
+    a = rng.uniform(-1.0, 1.0, 5)
+    half = max(H * res[0], W * res[1]) / 2.0
+    f = (a[0] * y + a[1] * x + a[2] * z) / half + a[3] * (y * y - x * x) / half ** 2 + a[4] * (y * y + x * x) / half ** 2
+    f = strength * f / max(np.abs(f).max(), 1e-12)
+    out = (image.astype(np.float64) + 0.1 * image.max()) * np.exp(f)
+    return np.round(np.minimum(out, 32767.0)).astype(np.int16)
+
+
 def default_splits(ids):
     """70 / 15 / 15 like CHAOS's 14 / 3 / 3 (at least one volume each), rotated for a second split"""
     n = len(ids)
@@ -71,12 +87,14 @@ def default_splits(ids):
 
 
 def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False,
-                 slice_spacing=None, hot_voxels=0):
+                 slice_spacing=None, hot_voxels=0, bias_field=0.0):
     """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
     draws included, is as without it.  slice_spacing = (LO, HI): every file also stores `slice_spacing`, mm between its slices, drawn
     from [LO, HI] by a generator of its own, so that every other draw is as without it.  hot_voxels = N > 0: every file is multiplied
     by a gain of its own from [0.5, 2] (scanners differ) and every slice gets N voxels of 8 to 16 times its maximum (vessels, fold-over
-    artefacts): what the `intensity` modes of the loader are for.  These draws too come from a generator of their own."""
+    artefacts): what the `intensity` modes of the loader are for.  These draws too come from a generator of their own.  bias_field =
+    STRENGTH > 0: every file carries a smooth multiplicative field exp(f), |f| <= STRENGTH (add_bias_field; a generator of its own), and the
+    manifest gets "bias_field": {"mode": "n3"} so that the loader removes it."""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
@@ -87,6 +105,9 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
     if hot_voxels < 0:
         raise ValueError('hot_voxels must be 0 or more, got %r' % (hot_voxels,))
     hot_rng = np.random.RandomState(seed + 2000003)
+    if bias_field < 0:
+        raise ValueError('bias_field must be 0 or more, got %r' % (bias_field,))
+    bias_rng = np.random.RandomState(seed + 3000003)
     values = label_values(masks)
     ids = list(range(1, volumes + 1))
     manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
@@ -106,13 +127,18 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
             fname = 'vol%02d_%s.npz' % (v, mod_name)
             arrays = dict(image=image, resolution=res.astype(np.float64)) if unlabelled else dict(image=image, label=label,
                                                                                                    resolution=res.astype(np.float64))
-            if slice_spacing is not None:
-                arrays['slice_spacing'] = np.float64(spacing_rng.uniform(slice_spacing[0], slice_spacing[1]))
+            spacing = None if slice_spacing is None else float(spacing_rng.uniform(slice_spacing[0], slice_spacing[1]))
+            if bias_field:
+                arrays['image'] = add_bias_field(bias_rng, image, bias_field, res, spacing)
+            if spacing is not None:
+                arrays['slice_spacing'] = np.float64(spacing)
             np.savez_compressed(os.path.join(out, fname), **arrays)
             entry[mod_name] = {'file': fname}
             if before or after:
                 entry[mod_name]['slices'] = [[before, before + slices]]
         manifest['volumes'][str(v)] = entry
+    if bias_field:
+        manifest['bias_field'] = {'mode': 'n3'}
     with open(os.path.join(out, 'dataset.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -134,9 +160,12 @@ def main(argv=None):
                     help='store a slice spacing in mm per file, drawn from [LO, HI] (what the scores in mm need)')
     ap.add_argument('--hot_voxels', type=int, default=0, metavar='N',
                     help='a gain per file and N very bright voxels per slice (what the intensity modes of dataset.json are for)')
+    ap.add_argument('--bias_field', type=float, default=0.0, metavar='STRENGTH',
+                    help='a smooth multiplicative field exp(f), |f| <= STRENGTH, per file, and "bias_field": {"mode": "n3"} in dataset.json '
+                         '(what the bias-field correction of the loader is for)')
     a = ap.parse_args(argv)
     m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing,
-                     a.hot_voxels)
+                     a.hot_voxels, a.bias_field)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 
