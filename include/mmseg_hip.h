@@ -74,7 +74,7 @@ int mmseg_conv2d_fwd_scaled_t(const void* x1, const void* x2, const float* w, co
  * 16-byte gather of the generic kernels / two inputs of conv_wgrad_tr_kernel); families
  * 1 conv_fast_kernel, 2 conv_fwd_kernel, 3 conv_direct_kernel, 4 conv_fast_batched_kernel, 5 conv_dgrad_s2k4_smallc_kernel,
  * 6 conv_wgrad_tr_kernel, 7 conv_wgrad_fast_kernel, 8 conv_wgrad_kernel, 9 conv_wgrad_c8_kernel, 25 conv_fast_planes_kernel (the
- * products of mmseg_conv2d_fwd_wino) (profiling aid, no launch) */
+ * products of mmseg_conv2d_fwd_wino), 26 winof_kernel (mmseg_conv2d_fwd_winof) (profiling aid, no launch) */
 int mmseg_conv2d_last_kernel(void);
 /* fast path (Cin % 32 == 0, not transposed, at most 32 taps -- the reference's largest kernel is 5 x 5; more taps fall back to the
  * generic kernel, which reads `w`): K tiles lie inside one tap, gather by buffer loads, weights read from
@@ -151,6 +151,17 @@ int mmseg_conv2d_wprep_wino(const float* w, float* out, int Cin, int Cout, void*
  * mmseg_conv2d_wino_workspace floats (checked, with the structural conditions and 16-byte alignment, before anything is queued). */
 int mmseg_conv2d_fwd_wino(const float* x1, const float* x2, const float* U, const float* bias, const float* oscale, float* y, int B, int H,
                           int W, int C1, int C2, int Cout, int act, float alpha, float* ws, long ws_floats, void* stream);
+/* Fused Winograd F(2x2,3x3) of the same operation in ONE launch (family 26 winof_kernel, no workspace): a block builds the transformed
+ * input of 8 image rows x 32 columns in LDS, keeps the sixteen plane accumulators of 64 tiles x 64 output channels in registers and applies
+ * the output transform, scale, bias and activation in its epilogue.  Asked only by callers that opt in (ops.conv2d_bn_infer(rounded=True):
+ * the output is seen through a Rounding layer only), before mmseg_conv2d_wino_ok.  1 when the route is taken: mmseg_conv2d_wino_mode 1 or 2,
+ * fp32 precision mode, H % 8 == 0, W % 32 == 0, C1 % 32 == C2 % 32 == 0 (C1 >= 32), Cout % 64 == 0, every tensor and the weight image below
+ * 2^31 - 64 bytes; in mode 1 also one of the shapes measured faster than the other routes (profiles/winof_ab.txt).  No launch. */
+int mmseg_conv2d_winof_ok(int B, int H, int W, int C1, int C2, int Cout);
+/* y = act(conv3x3_same(concat(x1, x2)) * oscale[c] + bias[c]) (oscale / bias may be NULL); U from mmseg_conv2d_wprep_wino.  The structural
+ * conditions above and 16-byte alignment of every pointer are checked before the launch is queued (hipErrorInvalidValue otherwise). */
+int mmseg_conv2d_fwd_winof(const float* x1, const float* x2, const float* U, const float* bias, const float* oscale, float* y, int B, int H,
+                           int W, int C1, int C2, int Cout, int act, float alpha, void* stream);
 /* Data gradient of a stride-1 convolution with few input channels (segmentor c0 8 -> 64, the SPADE shared convolutions 8 -> 128:
  * model_components/segmentor.py:16, layers/spade.py:29), second half: dx = sum over the taps of the shifted planes of
  * T [B,Ho,Wo,KH*KW*Cin], which the caller computes with ONE 1x1 mmseg_conv2d_fwd over dy (wt = the Keras kernel itself read as

@@ -2969,3 +2969,4 @@ int mmseg_conv2d_wflip(const float* w, float* wt, int KH, int KW, int Cin, int C
 }  // extern "C"
 
 #include "wino.hpp"
+#include "winof.hpp"

@@ -8,6 +8,8 @@ as `.last_soft` (used for teacher-forced parity checks across the rounding disco
 """
 import logging
 
+import torch
+
 from .. import nn, ops
 from ..models import unet
 from ..utils.rng import global_rng
@@ -60,8 +62,11 @@ class AnatomyEncoder(nn.Model):
 
     def forward(self, x, training=False):
         ds = self.conf.downsample
-        l, skips = unet.unet_downsample(self, x, training, ds, self.norm)
-        l = unet.unet_bottleneck_upsample(self.up, l, skips, training, ds, self.norm)
+        # without a tape and with the Rounding layer on, nothing downstream sees the UNet's last bits: its wide 3x3 layers may take the
+        # fused Winograd kernel (ops.conv2d_bn_infer)
+        rounded = bool(self.conf.rounding) and not training and not torch.is_grad_enabled()
+        l, skips = unet.unet_downsample(self, x, training, ds, self.norm, rounded=rounded)
+        l = unet.unet_bottleneck_upsample(self.up, l, skips, training, ds, self.norm, rounded=rounded)
         logits = nn.conv(self.up, 'conv_anatomy', l)
         soft, rounded = ops.softmax_round(logits)        # Conv2D(.., softmax) + Rounding (anatomy_encoder.py:23-25)
         self.last_soft = soft

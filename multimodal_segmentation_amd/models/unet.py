@@ -16,10 +16,11 @@ def declare_conv_block(m, name, cin, f, norm='batch'):
     nn.conv_params(m, name + 'b', 3, f, f, 'he_normal'); nn.norm_params(m, name + 'b_bn', f, norm)
 
 
-def conv_block(m, name, x, training, x2=None, norm='batch'):
-    """reference models/unet.py:94-101; `norm`: 'batch' | 'instance' | None (utils/model_utils.py:6-12)"""
-    l = nn.conv_norm(m, name + 'a', name + 'a_bn', x, training, relu=True, x2=x2, norm=norm)
-    return nn.conv_norm(m, name + 'b', name + 'b_bn', l, training, relu=True, norm=norm)
+def conv_block(m, name, x, training, x2=None, norm='batch', rounded=False):
+    """reference models/unet.py:94-101; `norm`: 'batch' | 'instance' | None (utils/model_utils.py:6-12); `rounded`: the UNet's output is
+    seen only through a Rounding layer (nn.conv_bn)"""
+    l = nn.conv_norm(m, name + 'a', name + 'a_bn', x, training, relu=True, x2=x2, norm=norm, rounded=rounded)
+    return nn.conv_norm(m, name + 'b', name + 'b_bn', l, training, relu=True, norm=norm, rounded=rounded)
 
 
 def declare_unet_down(m, cin, f, downsample=4, norm='batch'):
@@ -29,13 +30,13 @@ def declare_unet_down(m, cin, f, downsample=4, norm='batch'):
         c = f * 2 ** i
 
 
-def unet_downsample(m, x, training, downsample=4, norm='batch'):
+def unet_downsample(m, x, training, downsample=4, norm='batch', rounded=False):
     """reference models/unet.py:37-52 -> (pooled tensor, [d_l0 .. d_l3])"""
     from .. import ops
     skips = []
     l = x
     for i in range(downsample):
-        d = conv_block(m, 'd%d' % i, l, training, norm=norm)
+        d = conv_block(m, 'd%d' % i, l, training, norm=norm, rounded=rounded)
         l, skip = ops.maxpool2_skip(d)        # d feeds the pooling and the skip concatenation: one node, gradients added in one pass
         skips.append(skip)
     return l, skips
@@ -52,12 +53,12 @@ def declare_unet_up(m, f, out_channels, downsample=4, norm='batch'):
     nn.conv_params(m, 'conv_anatomy', 1, f, out_channels)
 
 
-def unet_bottleneck_upsample(m, l, skips, training, downsample=4, norm='batch'):
+def unet_bottleneck_upsample(m, l, skips, training, downsample=4, norm='batch', rounded=False):
     """reference models/unet.py:54-86 (bottleneck + up path); returns the f-channel feature map"""
-    l = conv_block(m, 'bott', l, training, norm=norm)
+    l = conv_block(m, 'bott', l, training, norm=norm, rounded=rounded)
     for i in reversed(range(downsample)):
         n = 'u%d' % i
         # UpSampling2D(2) + Conv2D fused; BatchNorm with activation='linear' (unet.py:67,72,77,82)
         l = nn.conv_norm(m, n, n + '_bn', l, training, relu=False, upsample=True, norm=norm)
-        l = conv_block(m, n + 'c', l, training, x2=skips[i], norm=norm)  # Concatenate([l, skip]) fused into the conv
+        l = conv_block(m, n + 'c', l, training, x2=skips[i], norm=norm, rounded=rounded)  # Concatenate([l, skip]) fused into the conv
     return l

@@ -358,13 +358,14 @@ def bn(m, name, x, training, relu=False, out_dtype=torch.float32):
                          ggrad=g.g(), bgrad=b.g(), anchor=anchor(x.device), out_dtype=out_dtype)
 
 
-def conv_bn(m, cname, bname, x, training, relu=False, x2=None, upsample=False, y16=True):
+def conv_bn(m, cname, bname, x, training, relu=False, x2=None, upsample=False, y16=True, rounded=False):
     """Conv2D(3x3 'same') -> BatchNormalization [-> ReLU].  Training: the two layers as separate launches (batch statistics
     need the whole convolution output first).  Inference without a tape (`predict`): one launch, BatchNorm folded into
     the convolution epilogue.
     With 16-bit activation storage on (conf.act_storage = 'half', ops.set_activation_storage): the convolution output is stored in the
     16-bit type when the convolution runs on the MFMA fast path (input channels a multiple of 32), the BatchNorm output when the
-    caller allows it (`y16`: its consumers read 16-bit tensors) and the channel count is a multiple of 64."""
+    caller allows it (`y16`: its consumers read 16-bit tensors) and the channel count is a multiple of 64.
+    `rounded`: passed to ops.conv2d_bn_infer (the output reaches its consumers only through a Rounding layer)."""
     w, b = m.params[cname + '/kernel'], m.params.get(cname + '/bias')
     half = ops.act16_dtype()
     Cout = w.shape[3]
@@ -378,7 +379,7 @@ def conv_bn(m, cname, bname, x, training, relu=False, x2=None, upsample=False, y
     return ops.conv2d_bn_infer(x, w.data, b.data if b is not None else None, m.params[bname + '/gamma'].data,
                                m.params[bname + '/beta'].data, m.params[bname + '/moving_mean'].data,
                                m.params[bname + '/moving_variance'].data, relu=relu, x2=x2, upsample=upsample, wkey=(w.uid, w.owner.uid),
-                               out_dtype=bn_dt)
+                               out_dtype=bn_dt, rounded=rounded)
 
 
 def norm_params(m, name, c, norm):
@@ -391,10 +392,10 @@ def norm_params(m, name, c, norm):
         m.add_param(name + '/beta', (1,), 'zeros')
 
 
-def conv_norm(m, cname, nname, x, training, relu=False, x2=None, upsample=False, norm='batch'):
+def conv_norm(m, cname, nname, x, training, relu=False, x2=None, upsample=False, norm='batch', rounded=False):
     """Conv2D(3x3 'same') -> normalise(norm) [-> ReLU] (models/unet.py:94-101, utils/model_utils.py:6-22)"""
     if norm == 'batch':
-        return conv_bn(m, cname, nname, x, training, relu=relu, x2=x2, upsample=upsample)
+        return conv_bn(m, cname, nname, x, training, relu=relu, x2=x2, upsample=upsample, rounded=rounded)
     if norm == 'instance':
         # (x - mean) / (std + 1e-3) over (H, W, C) jointly per sample, then the scalar affine and the activation in the FiLM
         # kernel (alpha 0 = ReLU, alpha 1 = linear)

@@ -390,6 +390,20 @@ def _wino_ok(x1, x2, w, ups, out_dtype):
     return bool(N.call('mmseg_conv2d_wino_ok', B, H, W, C1, C2, w.shape[3]))
 
 
+def _winof_ok(x1, x2, w, ups, out_dtype):
+    """the inference forward of this layer, whose caller opted in (`rounded`), takes the fused Winograd route: a 3x3 'same' fp32 layer
+    without up-sampling that mmseg_conv2d_winof_ok admits (mode, precision, shape)"""
+    if ups or tuple(w.shape[:2]) != (3, 3):
+        return False
+    if not (x1.dtype == w.dtype == out_dtype == torch.float32) or (x2 is not None and x2.dtype != torch.float32):
+        return False
+    B, H, W, C1 = x1.shape
+    C2 = x2.shape[3] if x2 is not None else 0
+    if not N.call('mmseg_conv2d_fast_path', C1, C2, w.shape[3], 0):      # (a backend without the MFMA fast path has no fused route either)
+        return False
+    return bool(N.call('mmseg_conv2d_winof_ok', B, H, W, C1, C2, w.shape[3]))
+
+
 def _conv_fwd_raw(x1, x2, w, wt, bias, y, y2, B, H, W, C1, C2, Ho, Wo, Cout, KH, KW, stride, ph, pw, ups, transposed,
                   act, alpha, nsplit1):
     # host-side shape checks: the kernel trusts these numbers
@@ -592,9 +606,12 @@ class _Conv2d(torch.autograd.Function):
 
 
 def conv2d_bn_infer(x, w, cbias, gamma, beta, mov_mean, mov_var, relu=False, x2=None, upsample=False, wkey=None,
-                    out_dtype=torch.float32):
+                    out_dtype=torch.float32, rounded=False):
     """`predict` of Conv2D -> BatchNormalization [-> ReLU] as ONE launch: the moving statistics are folded into a
-    per-channel scale and bias of the convolution epilogue (no tape: inference only)."""
+    per-channel scale and bias of the convolution epilogue (no tape: inference only).
+    `rounded`: the caller's promise that every consumer sees this output only through a Rounding layer (the anatomy encoders'
+    `predict`), so that last-bit differences reach no loss and no weight; only then may the fused Winograd kernel
+    (mmseg_conv2d_fwd_winof) take the layer."""
     x1 = _c(x)
     x2 = _c(x2) if x2 is not None else None
     B, H1, W1, C1 = x1.shape
@@ -617,6 +634,10 @@ def conv2d_bn_infer(x, w, cbias, gamma, beta, mov_mean, mov_var, relu=False, x2=
     y = _new((B, Ho, Wo, Cout), x1, out_dtype)
     if _ups_fold(x1, x2, w, 1, 'same', upsample, out_dtype) and _ups_fold_ok(x1, Cout, 3):
         N.call('mmseg_conv2d_fwd_ups_parity', x1, _wprep_ups(w, C1, Cout, 0, wkey), ss[1], ss[0], y, B, H1, W1, C1, Cout,
+               ACT['relu' if relu else None], 0.0)
+        return y
+    if rounded and _winof_ok(x1, x2, w, upsample, out_dtype):
+        N.call('mmseg_conv2d_fwd_winof', x1, x2, _wprep_wino(w, Cin, Cout, wkey), ss[1], ss[0], y, B, H, W, C1, C2, Cout,
                ACT['relu' if relu else None], 0.0)
         return y
     if _wino_ok(x1, x2, w, upsample, out_dtype):
