@@ -853,6 +853,46 @@ int mmseg_bias_finish(float* x, const double* ws, int S, int H, int W, void* str
 /* field [S,H,W] fp64 = f (zeros for a volume that keeps its bits); info [2] int32 = (frozen, iterations that updated f), or null */
 int mmseg_bias_field(const double* ws, double* field, int* info, int S, int H, int W, void* stream);
 
+/* ---- non-local means denoising of one MR volume (csrc/denoise.hip; build-defined: the reference loads CHAOS as exported) ----
+ * The step that precedes bias correction in an MR chain (ANTs: DenoiseImage, then N4; dipy: nlmeans).  Buades' voxel-wise non-local means
+ * with Manjon's / Wiest-Daessle's Rician correction.  Departures from the literature: patches are always in-plane (CHAOS slices lie 5 to
+ * 9 mm apart against 1.4 to 1.9 mm in plane: a patch across slices compares different anatomy); voxel-wise, not block-wise; sigma = auto is
+ * Immerkaer's estimate; 2 sigma^2 is subtracted from the patch distance inside the weight.
+ * x [S,H,W] fp32 (finite) -> out [S,H,W] fp32, every element written; out must not overlap x; n = S * H * W < 2^31 - 1.
+ * Parameters: search_radius Rs in 1..10, patch_radius Rp in 1..3, search_radius_z Rz in 0..4 (0: every slice on its own, "2d"; > 0: the
+ * search, never the patch, also reaches the same in-plane window of the Rz slices before and after, "3d" / 2.5-D), h finite > 0 (the
+ * smoothing strength in units of sigma), rician 1 | 0 (0: Gaussian noise), sigma in the volume's grey values.
+ *   per voxel p   walk the offsets t = (dz, dy, dx), |dz| <= Rz, |dy| <= Rs, |dx| <= Rs, t != 0, in ascending (dz, dy, dx) order.  A
+ *                 neighbour q = p + t outside the volume is skipped, not padded.  With T = (2 Rp + 1)^2:
+ *                     d2(p, q) = (1 / T) sum_{|a|, |b| <= Rp} (u(p + (0, a, b)) - u(q + (0, a, b)))^2,    a, then b, ascending,
+ *                 the patch coordinates clamped to the slice (edge replicate) on both sides;
+ *                     w(p, q) = exp2(max(d2 - 2 sigma^2, 0) * c),    c = -log2(e) / (h sigma)^2    (the hardware exp2),
+ *                 and 0 where the argument of exp2 is below -126: no weight is a denormal number.
+ *                 sw = sum w, sv = sum w v(q), with v = u (Gaussian) or u^2 (Rician), added in the walk order.  The centre comes last with
+ *                 w(p, p) = the largest of the other weights (Buades' and dipy's convention; 0 without a neighbour).
+ *   output        sw = 0 (no neighbour, or every weight underflowed): out = u(p).  Else m = sv / sw; Gaussian: out = m; Rician
+ *                 (Wiest-Daessle 2008): out = sqrt(max(m - 2 sigma^2, 0)).
+ *   arithmetic    all fp32 (sigma is rounded to fp32 once); a gather without atomics: two runs are bitwise equal, and with Rz = 0 a slice's
+ *                 result does not depend on the other slices of the call.
+ *   sigma         Immerkaer's estimator, always in-plane: sigma = sqrt(pi / 2) / (6 S (H - 2) (W - 2)) sum |L * x| over the interior
+ *                 pixels of every slice, L = [[1, -2, 1], [-2, 4, -2], [1, -2, 1]], each term and the sum in fp64 in an order fixed by the
+ *                 shape (two runs are bitwise equal); H < 3 or W < 3 gives 0.  The estimator reads anatomy edges as noise: it runs high on
+ *                 small or busy slices, and a sigma measured in a background region is better where the user has one.
+ *   keeps its bits  a volume whose sigma, given or estimated, is <= 0 or not finite (a constant volume under `auto` is one), or so small or
+ *                 large that 2 sigma^2, (h sigma)^2 or c leaves the positive finite fp32 numbers: out is a copy of x.
+ * Anything outside the limits, a null pointer, out overlapping x or n >= 2^31 - 1 is refused (hipErrorInvalidValue, nothing is launched);
+ * S = 0 does nothing.  No host synchronisation, allocation or copy; sigma never returns to the host.  Launches: mmseg_nlm_sigma 2 (partial
+ * sums per block, then one block that adds them; no block waits for another), mmseg_nlm_denoise 1.  A block owns a tile of 8 rows x 32
+ * columns of one slice. */
+/* bytes of ws for mmseg_nlm_sigma (the partial sums; 8-byte aligned); 0 for a shape it refuses */
+long mmseg_nlm_workspace_bytes(int S, int H, int W);
+/* sigma_out [1] fp64 on the device */
+int mmseg_nlm_sigma(const float* x, double* ws, double* sigma_out, int S, int H, int W, void* stream);
+/* sigma_dev: one fp64 on the device (what mmseg_nlm_sigma wrote), or null: then `sigma` is used.  Both ways give the same bits for the
+ * same number. */
+int mmseg_nlm_denoise(const float* x, float* out, const double* sigma_dev, double sigma, int S, int H, int W, int search_radius,
+                      int patch_radius, int search_radius_z, float h, int rician, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@
                          [--data_folder PATH] [--test_data_folder PATH]
                          [--intensity_norm minmax|window] [--intensity_scope slice|volume] [--intensity_percentiles LO,HI]
                          [--bias_correction off|n3] [--bias_sigma_mm MM] [--bias_levels N] [--bias_iterations N] [--bias_extent 2d|3d]
+                         [--denoise off|nlm] [--denoise_sigma auto|V] [--denoise_h K] [--denoise_search N] [--denoise_patch N]
+                         [--denoise_search_z N] [--denoise_extent 2d|3d] [--denoise_noise rician|gaussian]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
@@ -83,6 +85,19 @@ def parse_arguments(argv=None):
     ap.add_argument('--bias_iterations', type=int, help='iterations per level of --bias_correction n3 (default 20, untuned)')
     ap.add_argument('--bias_extent', choices=['2d', '3d'], help='--bias_correction n3 smooths within slices / also across them (default: 3d '
                                                                 'where the files hold slice_spacing)')
+    ap.add_argument('--denoise', choices=['off', 'nlm'],
+                    help='denoising of every volume folder of the run at load time, before the bias-field correction, instead of what '
+                         'their dataset.json say (nlm: voxel-wise non-local means with in-plane patches, on the device)')
+    ap.add_argument('--denoise_sigma', metavar='auto|V', help='noise level of --denoise nlm in raw grey values, or auto: estimated per '
+                                                              'volume and modality on the device (default auto)')
+    ap.add_argument('--denoise_h', type=float, help='smoothing strength of --denoise nlm in units of sigma (default 1, an untuned '
+                                                    'starting value)')
+    ap.add_argument('--denoise_search', type=int, help='in-plane search radius of --denoise nlm, 1..10 (default 5, untuned)')
+    ap.add_argument('--denoise_patch', type=int, help='in-plane patch radius of --denoise nlm, 1..3 (default 1, untuned)')
+    ap.add_argument('--denoise_search_z', type=int, help='slices before and after that --denoise_extent 3d also searches, 0..4 (default 1)')
+    ap.add_argument('--denoise_extent', choices=['2d', '3d'], help='--denoise nlm searches within the slice / also in the neighbouring '
+                                                                   'slices (default: 2d)')
+    ap.add_argument('--denoise_noise', choices=['rician', 'gaussian'], help='noise model of --denoise nlm (default: rician)')
     ap.add_argument('--predict_folder', help='folder of exported volumes (labels optional) to write predicted label volumes for')
     ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
     ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
@@ -128,6 +143,13 @@ def parse_arguments(argv=None):
         ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
     if any(getattr(args, a) is not None for a, _ in BIAS_ARGS) and args.bias_correction != 'n3':
         ap.error('--bias_sigma_mm, --bias_levels, --bias_iterations and --bias_extent go with --bias_correction n3')
+    if any(getattr(args, a) is not None for a, _ in DENOISE_ARGS) and args.denoise != 'nlm':
+        ap.error('%s go with --denoise nlm' % ', '.join('--' + a for a, _ in DENOISE_ARGS))
+    if args.denoise_sigma is not None and args.denoise_sigma != 'auto':
+        try:
+            args.denoise_sigma = float(args.denoise_sigma)
+        except ValueError:
+            ap.error('--denoise_sigma takes auto or a number, got %r' % args.denoise_sigma)
     if args.intensity_percentiles is not None:
         try:
             args.intensity_percentiles = [float(v) for v in args.intensity_percentiles.split(',')]
@@ -302,6 +324,49 @@ def warn_predict_bias(conf, folder, log):
     return True
 
 
+DENOISE_ARGS = (('denoise_sigma', 'sigma'), ('denoise_h', 'h'), ('denoise_search', 'search_radius'), ('denoise_patch', 'patch_radius'),
+                ('denoise_search_z', 'search_radius_z'), ('denoise_extent', 'extent'), ('denoise_noise', 'noise'))
+
+
+def denoise_override(named, args):
+    """the `denoise` block of `--denoise` and its companions, else the configuration's `denoise`, else None: no override, every folder
+    follows its own dataset.json"""
+    from .loaders.volume_folder import check_denoise
+    block, where = named.get('denoise'), 'conf.denoise'
+    if getattr(args, 'denoise', None):
+        block, where = {'mode': args.denoise}, '--denoise'
+        for arg, key in DENOISE_ARGS:
+            if getattr(args, arg, None) is not None:
+                block[key] = getattr(args, arg)
+    if block is None:
+        return None
+    return check_denoise(dict(block), None, where)
+
+
+def register_denoise(named, args, names):
+    """Fill loaders.denoise_conf for the data set names of this run; without an override their entries are removed"""
+    from .loaders import denoise_conf
+    block = denoise_override(named, args)
+    for name in names:
+        if block is None:
+            denoise_conf.pop(name, None)
+        else:
+            denoise_conf[name] = dict(block)
+    return block
+
+
+def warn_predict_denoise(conf, folder, log):
+    """a warning when the denoise setting in force for the predict folder differs from the one the run folder records (conf.denoise; a
+    run on the synthetic volumes records none: off).  True when it warned."""
+    from .loaders.volume_folder import effective_denoise
+    trained, here = conf.get('denoise') or {'mode': 'off'}, effective_denoise(folder)
+    if here == trained:
+        return False
+    log.warning('--predict_folder: the denoising of %s is set to %s, the run folder %s records %s: the model sees other noise than it '
+                'was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
+    return True
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
@@ -320,11 +385,13 @@ class Experiment(object):
             names.add(read_manifest(args.predict_folder)['name'])
         register_intensity(conf, args, sorted(names))      # before a loader that loads volumes is built: it reads its setting then
         register_bias(conf, args, sorted(names))
+        register_denoise(conf, args, sorted(names))
         if data_conf.get(conf.dataset_name):
             conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
-            from .loaders.volume_folder import effective_bias, effective_intensity
+            from .loaders.volume_folder import effective_bias, effective_denoise, effective_intensity
             conf.intensity = effective_intensity(conf.data_folder)  # the setting in force, override or dataset.json: recorded too
             conf.bias_field = effective_bias(conf.data_folder)
+            conf.denoise = effective_denoise(conf.data_folder)
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')
@@ -392,6 +459,7 @@ class Experiment(object):
         if dp.is_main():
             warn_predict_intensity(conf, args.predict_folder, self.log)
             warn_predict_bias(conf, args.predict_folder, self.log)
+            warn_predict_denoise(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()

@@ -11,8 +11,12 @@ name).  `experiment.py --intensity_norm ...` (or `conf.intensity`) fills it for 
 folder is normalised as its own dataset.json says.
 
 `bias_conf` (build-defined) does the same for the `bias_field` block (bias-field correction at load time): `experiment.py
---bias_correction ...` (or `conf.bias_field`) fills it; empty, each folder follows its own dataset.json."""
+--bias_correction ...` (or `conf.bias_field`) fills it; empty, each folder follows its own dataset.json.
+
+`denoise_conf` (build-defined) does the same for the `denoise` block (non-local means denoising at load time): `experiment.py
+--denoise ...` (or `conf.denoise`) fills it; empty, each folder follows its own dataset.json."""
 
 data_conf = {}
 intensity_conf = {}
 bias_conf = {}
+denoise_conf = {}

@@ -36,6 +36,15 @@ correction (ops.bias_correct; the rule is in include/mmseg_hip.h) of the selecte
 prediction, tiles and TTA all see the same volume.  "3d" needs `slice_spacing` and one contiguous run of slices.
 loaders.bias_conf overrides the key for a run (experiment.py --bias_correction).
 
+`denoise` (optional key of dataset.json; build-defined) removes acquisition noise before all of the above.  Absent or {"mode": "off"}:
+nothing is launched.  {"mode": "nlm", "sigma": "auto" | number | {modality: number}, "h": 1.0, "search_radius": 5, "patch_radius": 1,
+"extent": "2d" | "3d", "search_radius_z": 0 | 1..4, "noise": "rician" | "gaussian"} (the defaults are untuned starting values; `extent`
+defaults to "2d"): voxel-wise non-local means with in-plane patches (ops.nlm_denoise; the rule is in include/mmseg_hip.h) of the selected
+raw slices, once per uploaded (volume, modality), in `denoised` -- immediately before `bias_corrected`, so the bias field, the percentiles
+and everything after them see the denoised volume.  "3d" lets the search reach the neighbouring slices and needs one contiguous run of
+slices.  `sigma` is in the file's raw grey values; "auto" estimates it per (volume, modality) on the device and runs high on small or busy
+slices.  loaders.denoise_conf overrides the key for a run (experiment.py --denoise).
+
 For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
 frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
 import json
@@ -262,6 +271,64 @@ def effective_bias(root, manifest=None):
     return check_bias(m.get('bias_field'), os.path.join(root, MANIFEST))
 
 
+DENOISE_MODES = ('off', 'nlm')
+
+
+def check_denoise(block, modalities, where):
+    """The normalised form of a `denoise` block (dataset.json, conf.denoise): {'mode': 'off'}, or {'mode': 'nlm', 'sigma', 'h',
+    'search_radius', 'patch_radius', 'search_radius_z', 'extent', 'noise'} with ops.NLM_DEFAULTS filled in.  `sigma` is 'auto', a number
+    or {modality: number}; a mapping must name every modality of `modalities` (None: the folder is not known yet, as for a command-line
+    override).  None and {} mean 'off'."""
+    if block is None:
+        return {'mode': 'off'}
+    if not isinstance(block, dict):
+        raise ValueError('%s: "denoise" must be an object, got %r' % (where, block))
+    mode = block.get('mode', 'off')
+    if mode not in DENOISE_MODES:
+        raise ValueError('%s: "denoise" mode must be one of %s, got %r' % (where, ', '.join(DENOISE_MODES), mode))
+    unknown = sorted(set(block) - {'mode'} - set(ops.NLM_DEFAULTS))
+    if unknown:
+        raise ValueError('%s: "denoise" has unknown key(s) %s' % (where, ', '.join(unknown)))
+    if mode == 'off':
+        if set(block) - {'mode'}:
+            raise ValueError('%s: "denoise" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
+        return {'mode': 'off'}
+    given = {k: v for k, v in block.items() if k != 'mode' and not (k == 'search_radius_z' and v is None)}
+    per_modality = given.get('sigma') if isinstance(given.get('sigma'), dict) else None
+    if per_modality is not None:
+        del given['sigma']
+        for mod, s in sorted(per_modality.items()):
+            ops.nlm_params({'sigma': s}, '%s: "denoise" (modality %r)' % (where, mod))
+            if s == 'auto':
+                raise ValueError('%s: "denoise" sigma of modality %r must be a number; "auto" goes in place of the mapping' % (where, mod))
+        if modalities is not None:
+            missing = [mod for mod in modalities if mod not in per_modality]
+            if missing:
+                raise ValueError('%s: "denoise" sigma names no value for modality %s (a mapping must name every one of %s)'
+                                 % (where, ', '.join(repr(mod) for mod in missing), ', '.join(modalities)))
+            extra = sorted(set(per_modality) - set(modalities))
+            if extra:
+                raise ValueError('%s: "denoise" sigma names %s, which is no modality of the folder (%s)'
+                                 % (where, ', '.join(repr(mod) for mod in extra), ', '.join(modalities)))
+    p = ops.nlm_params(given, '%s: "denoise"' % where)
+    if per_modality is not None:
+        p['sigma'] = {str(mod): float(s) for mod, s in per_modality.items()}
+    return dict(mode='nlm', **p)
+
+
+def effective_denoise(root, manifest=None):
+    """the normalised denoise setting of the folder `root`: the override registered in loaders.denoise_conf under a data set name that
+    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
+    from . import data_conf, denoise_conf
+    m = read_manifest(root) if manifest is None else manifest
+    here = os.path.abspath(root)
+    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
+    for n in names:
+        if denoise_conf.get(n) is not None:
+            return check_denoise(denoise_conf[n], m['modalities'], 'loaders.denoise_conf[%r]' % n)
+    return check_denoise(m.get('denoise'), m['modalities'], os.path.join(root, MANIFEST))
+
+
 def read_manifest(root):
     path = os.path.join(root, MANIFEST)
     if not os.path.isfile(path):
@@ -294,6 +361,7 @@ def read_manifest(root):
                 raise ValueError('%s: volume %s has no file for modality %r' % (path, v, mod))
     check_intensity(m.get('intensity'), m['modalities'], path)
     check_bias(m.get('bias_field'), path)
+    check_denoise(m.get('denoise'), m['modalities'], path)
     return m
 
 
@@ -313,6 +381,7 @@ class VolumeFolderLoader(object):
         self.log = log
         self.intensity = effective_intensity(root, m)          # build-defined: {'mode': 'minmax'} is the reference's rescale
         self.bias_field = effective_bias(root, m)              # build-defined: {'mode': 'off'} uploads the slices as they are
+        self.denoise = effective_denoise(root, m)              # build-defined: {'mode': 'off'} launches nothing
 
     # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
     def splits(self):
@@ -418,6 +487,22 @@ class VolumeFolderLoader(object):
         params = dict(sigma_mm=setting['sigma_mm'], levels=setting['levels'], iterations=setting['iterations'], extent=extent)
         return ops.bias_correct(x, (spacing if extent == '3d' else 1.0, float(res[0]), float(res[1])), params)
 
+    def denoised(self, x, modality, selected=None, what='volume'):
+        """The raw slices x [S,H,W] of one (volume, modality) on the device after the folder's `denoise` setting: x itself when it is off
+        (nothing is launched), else a denoised copy (ops.nlm_denoise).  The one place where this is decided: preprocess,
+        load_volume_for_prediction and upload_volume call it once per upload, immediately before bias_corrected.  Extent 3d searches
+        the neighbouring slices too and therefore needs one contiguous run of slices (no slice_spacing: the rule has no mm in it)."""
+        setting = self.denoise
+        if setting['mode'] == 'off' or x.shape[0] == 0:
+            return x
+        if setting['extent'] == '3d' and selected is not None and len(selected) > 1 and np.any(np.diff(selected) != 1):
+            raise ValueError('%s: "denoise" extent 3d needs one contiguous run of slices, but "slices" selects %d that are not '
+                             'consecutive -- set "extent": "2d"' % (what, len(selected)))
+        params = {k: v for k, v in setting.items() if k != 'mode'}
+        if isinstance(params['sigma'], dict):
+            params['sigma'] = params['sigma'][modality]
+        return ops.nlm_denoise(x, params)
+
     def load_volume_for_prediction(self, volume):
         """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
         [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
@@ -434,8 +519,9 @@ class VolumeFolderLoader(object):
                 selected = np.arange(S_file)
             resampled, rows, cols = self.geometry(H, W, res)
             container = torch.zeros((len(selected), OH, OW, 1), dtype=torch.float32, device=device)
-            x = self.bias_corrected(nn.host_to_device(image[selected], device, np.float32), res, spacing, selected,
-                                    'volume %s, modality %s' % (volume, mod))
+            what = 'volume %s, modality %s' % (volume, mod)
+            x = self.denoised(nn.host_to_device(image[selected], device, np.float32), mod, selected, what)
+            x = self.bias_corrected(x, res, spacing, selected, what)
             ops.preprocess_images(x, container, resampled, rows, cols, 0, knots=self.intensity_knots(x, resampled, mod))
             images.append(container)
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
@@ -462,8 +548,9 @@ class VolumeFolderLoader(object):
             if selected is None:
                 selected = np.arange(S_file)
             resampled, rows, cols = self.geometry(H, W, res)
-            raw.append(self.bias_corrected(nn.host_to_device(image[selected], device, np.float32), res, spacing, selected,
-                                           'volume %s, modality %s' % (volume, mod)))
+            what = 'volume %s, modality %s' % (volume, mod)
+            x = self.denoised(nn.host_to_device(image[selected], device, np.float32), mod, selected, what)
+            raw.append(self.bias_corrected(x, res, spacing, selected, what))
             geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
                                  slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
                                  label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing,
@@ -525,7 +612,7 @@ class VolumeFolderLoader(object):
     def preprocess(self, raw, n, extras=None):
         """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks].
         extras: per volume, per modality (slice_spacing or None, the selected file indices or None, a name for messages): what
-        bias_corrected needs beyond the resolution; without it the slices count as one run of a file without slice_spacing."""
+        denoised and bias_corrected need beyond the resolution; without it the slices count as one run of a file without slice_spacing."""
         device = nn.default_device()
         OH, OW = self.input_shape[:2]
         M, K = len(self.modalities), self.num_masks
@@ -541,8 +628,9 @@ class VolumeFolderLoader(object):
                 RW = resampled_size(W, res[1], self.target_resolution[1])
                 if RH < 1 or RW < 1:
                     raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
-                x = self.bias_corrected(nn.host_to_device(image, device, np.float32), res,
-                                        *(extras[vol][mod] if extras is not None else (None, None, 'modality %s' % self.modalities[mod])))
+                spacing, selected, what = extras[vol][mod] if extras is not None else (None, None, 'modality %s' % self.modalities[mod])
+                x = self.denoised(nn.host_to_device(image, device, np.float32), self.modalities[mod], selected, what)
+                x = self.bias_corrected(x, res, spacing, selected, what)
                 ops.preprocess_volume(x, nn.host_to_device(label, device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
                                       (RH, RW), crop_pad_map(RH, OH), crop_pad_map(RW, OW), mod,
                                       knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))

@@ -2122,6 +2122,94 @@ def bias_update(f, num, den):
     return f
 
 
+NLM_DEFAULTS = dict(search_radius=5, patch_radius=1, search_radius_z=None, h=1.0, noise='rician', sigma='auto',
+                    extent='2d')                                                   # untuned starting values (README)
+NLM_EXTENTS = ('2d', '3d')
+NLM_NOISES = ('rician', 'gaussian')
+NLM_MAX_SEARCH, NLM_MAX_PATCH, NLM_MAX_SEARCH_Z = 10, 3, 4                         # NLM_MAX_RS, _RP, _RZ of csrc/denoise.hip
+NLM_TILE = (8, 32)                                                                 # NLM_TH, NLM_TW: rows x columns one block owns
+
+
+def _is_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def nlm_params(params=None, what='nlm_denoise'):
+    """NLM_DEFAULTS overlaid with `params`, validated: search_radius in 1..10, patch_radius in 1..3, extent 2d | 3d, search_radius_z in
+    0..4 (None: 0 for 2d, 1 for 3d; 2d takes no other), h finite > 0, noise rician | gaussian, sigma 'auto' or a finite number > 0"""
+    p = dict(NLM_DEFAULTS)
+    unknown = sorted(set(params or {}) - set(p))
+    if unknown:
+        raise ValueError('%s: unknown key(s) %s (known: %s)' % (what, ', '.join(unknown), ', '.join(sorted(p))))
+    p.update(params or {})
+    for key, low, top in (('search_radius', 1, NLM_MAX_SEARCH), ('patch_radius', 1, NLM_MAX_PATCH)):
+        v = p[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not low <= v <= top:
+            raise ValueError('%s: %s must be a whole number in %d..%d, got %r' % (what, key, low, top, v))
+    if p['extent'] not in NLM_EXTENTS:
+        raise ValueError('%s: extent must be one of %s, got %r' % (what, ', '.join(NLM_EXTENTS), p['extent']))
+    rz = p['search_radius_z']
+    if rz is None:
+        rz = 0 if p['extent'] == '2d' else 1
+    if isinstance(rz, bool) or not isinstance(rz, (int, np.integer)) or not 0 <= rz <= NLM_MAX_SEARCH_Z:
+        raise ValueError('%s: search_radius_z must be a whole number in 0..%d, got %r' % (what, NLM_MAX_SEARCH_Z, rz))
+    if p['extent'] == '2d' and rz != 0:
+        raise ValueError('%s: search_radius_z %d goes with extent 3d; extent 2d searches within the slice' % (what, rz))
+    if not _is_number(p['h']) or not np.isfinite(p['h']) or p['h'] <= 0:
+        raise ValueError('%s: h must be a finite number > 0 (the smoothing strength in units of sigma), got %r' % (what, p['h']))
+    if p['noise'] not in NLM_NOISES:
+        raise ValueError('%s: noise must be one of %s, got %r' % (what, ', '.join(NLM_NOISES), p['noise']))
+    s = p['sigma']
+    if s != 'auto' and (not _is_number(s) or not np.isfinite(s) or s <= 0):
+        raise ValueError('%s: sigma must be "auto" or a finite number > 0 in the volume\'s grey values, got %r' % (what, s))
+    return dict(search_radius=int(p['search_radius']), patch_radius=int(p['patch_radius']), search_radius_z=int(rz), h=float(p['h']),
+                noise=p['noise'], sigma='auto' if s == 'auto' else float(s), extent=p['extent'])
+
+
+def _nlm_volume(x, what):
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError('%s: x must be a contiguous fp32 [S,H,W] tensor, got %s %s' % (what, x.dtype, tuple(x.shape)))
+    S, H, W = x.shape
+    if S and H and W and not N.call('mmseg_nlm_workspace_bytes', S, H, W):
+        raise ValueError('%s: a volume of %d x %d x %d is outside the kernels\' limits (fewer than 2^31 - 1 voxels)' % (what, S, H, W))
+    return S, H, W
+
+
+def nlm_sigma(x):
+    """Immerkaer's estimate of the noise of x [S,H,W] fp32, in-plane (csrc/denoise.hip; the rule is in include/mmseg_hip.h): one fp64
+    scalar [1] on the device, 0 for slices narrower than 3 pixels.  It reads anatomy edges as noise, so it runs high on small or busy
+    slices.  No host synchronisation."""
+    S, H, W = _nlm_volume(x, 'nlm_sigma')
+    sigma = _new((1,), x, torch.float64)
+    if S * H * W == 0:
+        return sigma.zero_()
+    ws = _ws('nlm', N.call('mmseg_nlm_workspace_bytes', S, H, W) // 8, x.device, torch.float64)
+    N.call('mmseg_nlm_sigma', x, ws, sigma, S, H, W)
+    return sigma
+
+
+def nlm_denoise(x, params=None, out=None, sigma_out=False):
+    """Non-local means denoising of x [S,H,W] fp32 on the device (csrc/denoise.hip; the rule is in include/mmseg_hip.h); params: keys of
+    NLM_DEFAULTS.  The result is written into `out` (a new tensor by default; it may not be x) and returned; sigma_out=True returns
+    (out, sigma) with the fp64 device scalar [1] the kernel read.  A volume whose sigma is not > 0 (a constant one under 'auto') keeps
+    its bits.  No host synchronisation, no gradient."""
+    p = nlm_params(params)
+    S, H, W = _nlm_volume(x, 'nlm_denoise')
+    if out is None:
+        out = torch.empty_like(x)
+    elif out is x or out.shape != x.shape or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('nlm_denoise: out must be another tensor like x, got %s %s' % (out.dtype, tuple(out.shape)))
+    auto = p['sigma'] == 'auto'
+    if S * H * W == 0:
+        return (out, _new((1,), x, torch.float64).zero_()) if sigma_out else out
+    sigma = nlm_sigma(x) if auto else None
+    N.call('mmseg_nlm_denoise', x, out, sigma, 0.0 if auto else p['sigma'], S, H, W, p['search_radius'], p['patch_radius'],
+           p['search_radius_z'], p['h'], int(p['noise'] == 'rician'))
+    if not sigma_out:
+        return out
+    return out, (sigma if auto else torch.full((1,), p['sigma'], dtype=torch.float64, device=x.device))
+
+
 def preprocess_volume(img, lab, values, images, masks, resampled, rows, cols, mod, knots=None):
     """The S raw slices of one (volume, modality) -> channel `mod` of images [S,OH,OW,M] and channels mod*K .. of masks [S,OH,OW,M*K]
     (csrc/preprocess.hip): resample to `resampled` = (RH, RW), split the grey label values `values` [K] into binary channels,

@@ -11,7 +11,7 @@ ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
                                        [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI] [--hot_voxels N]
-                                       [--bias_field STRENGTH]
+                                       [--bias_field STRENGTH] [--rician_noise STD]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -75,6 +75,14 @@ def add_bias_field(rng, image, strength, res, spacing):
     return np.round(np.minimum(out, 32767.0)).astype(np.int16)
 
 
+def add_rician_noise(rng, image, std):
+    """image [S,H,W] int16 through a Rician channel: sqrt((image + n1)^2 + n2^2) with n1, n2 ~ N(0, std^2), the magnitude of a complex
+    signal with Gaussian noise in both parts -- what the `denoise` block of dataset.json removes.  Rounded back to int16."""
+    clean = image.astype(np.float64)
+    n1, n2 = rng.normal(0.0, std, clean.shape), rng.normal(0.0, std, clean.shape)
+    return np.round(np.minimum(np.sqrt((clean + n1) ** 2 + n2 ** 2), 32767.0)).astype(np.int16)
+
+
 def default_splits(ids):
     """70 / 15 / 15 like CHAOS's 14 / 3 / 3 (at least one volume each), rotated for a second split"""
     n = len(ids)
@@ -87,14 +95,16 @@ def default_splits(ids):
 
 
 def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False,
-                 slice_spacing=None, hot_voxels=0, bias_field=0.0):
+                 slice_spacing=None, hot_voxels=0, bias_field=0.0, rician_noise=0.0):
     """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
     draws included, is as without it.  slice_spacing = (LO, HI): every file also stores `slice_spacing`, mm between its slices, drawn
     from [LO, HI] by a generator of its own, so that every other draw is as without it.  hot_voxels = N > 0: every file is multiplied
     by a gain of its own from [0.5, 2] (scanners differ) and every slice gets N voxels of 8 to 16 times its maximum (vessels, fold-over
     artefacts): what the `intensity` modes of the loader are for.  These draws too come from a generator of their own.  bias_field =
     STRENGTH > 0: every file carries a smooth multiplicative field exp(f), |f| <= STRENGTH (add_bias_field; a generator of its own), and the
-    manifest gets "bias_field": {"mode": "n3"} so that the loader removes it."""
+    manifest gets "bias_field": {"mode": "n3"} so that the loader removes it.  rician_noise = STD > 0: every file, after all of the above,
+    passes through a Rician channel of that standard deviation in grey values (add_rician_noise; a generator of its own), and the
+    manifest gets "denoise": {"mode": "nlm", "sigma": STD} so that the loader removes it."""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
@@ -108,6 +118,9 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
     if bias_field < 0:
         raise ValueError('bias_field must be 0 or more, got %r' % (bias_field,))
     bias_rng = np.random.RandomState(seed + 3000003)
+    if not rician_noise >= 0:
+        raise ValueError('rician_noise must be 0 or more, got %r' % (rician_noise,))
+    noise_rng = np.random.RandomState(seed + 4000003)
     values = label_values(masks)
     ids = list(range(1, volumes + 1))
     manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
@@ -130,6 +143,8 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
             spacing = None if slice_spacing is None else float(spacing_rng.uniform(slice_spacing[0], slice_spacing[1]))
             if bias_field:
                 arrays['image'] = add_bias_field(bias_rng, image, bias_field, res, spacing)
+            if rician_noise:
+                arrays['image'] = add_rician_noise(noise_rng, arrays['image'], rician_noise)
             if spacing is not None:
                 arrays['slice_spacing'] = np.float64(spacing)
             np.savez_compressed(os.path.join(out, fname), **arrays)
@@ -139,6 +154,8 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
         manifest['volumes'][str(v)] = entry
     if bias_field:
         manifest['bias_field'] = {'mode': 'n3'}
+    if rician_noise:
+        manifest['denoise'] = {'mode': 'nlm', 'sigma': float(rician_noise)}
     with open(os.path.join(out, 'dataset.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -163,9 +180,12 @@ def main(argv=None):
     ap.add_argument('--bias_field', type=float, default=0.0, metavar='STRENGTH',
                     help='a smooth multiplicative field exp(f), |f| <= STRENGTH, per file, and "bias_field": {"mode": "n3"} in dataset.json '
                          '(what the bias-field correction of the loader is for)')
+    ap.add_argument('--rician_noise', type=float, default=0.0, metavar='STD',
+                    help='pass every file through a Rician channel of this standard deviation in grey values, and "denoise": {"mode": "nlm", '
+                         '"sigma": STD} in dataset.json (what the denoising of the loader is for)')
     a = ap.parse_args(argv)
     m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing,
-                     a.hot_voxels, a.bias_field)
+                     a.hot_voxels, a.bias_field, a.rician_noise)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 
