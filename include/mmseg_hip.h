@@ -893,6 +893,61 @@ int mmseg_nlm_sigma(const float* x, double* ws, double* sigma_out, int S, int H,
 int mmseg_nlm_denoise(const float* x, float* out, const double* sigma_dev, double sigma, int S, int H, int W, int search_radius,
                       int patch_radius, int search_radius_z, float h, int rician, void* stream);
 
+/* ---- alignment of a volume's modalities by mutual information (csrc/align.hip; build-defined: the reference pairs CHAOS slices by hand) ----
+ * Translation only: an integer slice shift dz and an integer in-plane shift (dy, dx) in pixels of the resampled frames, of a moving
+ * volume B against a reference volume A.  Scale is the loader's resampling; rotation and deformation stay with the model.
+ * O = (OH, OW) is the network's input extent, R_x = (RH_x, RW_x) the resampled extent of volume x, c(R) = centre_start(R, O) per axis:
+ * (R - O + 1) / 2 (floor) for R > O, else -((O - R) / 2) (floor).
+ *   1 quantise   q_x [S,RH,RW] uint8 on the resampled grid: v = the bilinear value of mmseg_preprocess_image (same coordinates, same fp32
+ *                expression order, outside -> 0); lo, hi = two order statistics of the volume (mmseg_preprocess_quantiles, per volume;
+ *                knots [2] fp32 on the device).  q = 0 for v <= lo; bins - 1 for v >= hi; else min(bins - 1, (int)floorf((v - lo) *
+ *                ((float)bins / (hi - lo)))) in fp32 without contraction.  hi == lo: all 0.  2 <= bins <= 64.
+ *   2 pairing    candidate (dz, dy, dx): reference slice i pairs with moving slice i + dz; window coordinate (oy, ox) reads A at
+ *                (oy + c_a, ox + c_a) and B at (oy + c_b + dy, ox + c_b + dx) (per axis), so the zero shift is the loader's centre
+ *                pairing.  Only pairs with both indices inside their frames count: nothing is padded, o is not limited to [0, O), the
+ *                whole overlap of the frames is used.  At stride t only o with o mod t == 0 on both axes is sampled (floor-mod: o may be
+ *                negative).  A byte >= bins counts as bins - 1.
+ *   3 score      h [bins,bins] uint32 = the joint histogram of the sampled pairs (row: A's bin), N = sum h.  With p = count / N in fp64 and
+ *                H = sum of -(p * log(p)) over the non-empty bins (natural log) of h, of its row sums and of its column sums: score =
+ *                (H(A) + H(B)) / H(A,B), Studholme's normalised mutual information, in fp64.  Summation order: thread k of 256 adds
+ *                the terms k, k + 256, ... in ascending order, the 256 sums are halved pairwise (k += k + 128, k + 64, ... 1).  Score =
+ *                -1 where N == 0 or H(A,B) == 0, and where the candidate is not admissible: n_full(c) >= min_overlap * n_full(0) in
+ *                fp64, n_full = the stride-1 pair count = the product of the three overlap lengths (closed form), 0 <= min_overlap <= 1.
+ *   4 search     a stage scores C candidates at stride t.  mode 0: cand [C,3] int32 on the device (a test's list; no probe).  mode 1, the
+ *                lattice: dz in [-Z, Z], dy in t * [-floor(Py / t), floor(Py / t)], dx likewise, index ((dz + Z) * ny + iy) * nx + ix.
+ *                mode 2, refinement: centre + (jz - 1, (jy - 1) t, (jx - 1) t), index (jz * 3 + jy) * 3 + jx, centre = state[0..2]; a
+ *                candidate outside [-Z, Z] x [-Py, Py] x [-Px, Px] is skipped (score -1, never selected).  In modes 1 and 2 the last
+ *                candidate, C - 1, is the zero-shift PROBE (0, 0, 0): scored like any other, never selected; its score is reported.
+ *                Best = the highest score; ties go to the smaller dz^2, then the smaller dy^2 + dx^2, then the lexicographically smaller
+ *                (dz, dy, dx).  If the best score is < 0 (nothing admissible) the shift is (0, 0, 0).
+ *   5 state      state [8] fp64 on the device, zeroed by the caller before the first stage: [0..2] (dz, dy, dx) of the stage's best, the
+ *                centre the next refinement stage reads; [3] its score; [4] the probe's score (mode 0: unchanged); [5] its N (the probe's
+ *                where nothing was admissible); [6] 1 where a candidate was admissible; [7] the stages run.  A search of L levels is the
+ *                lattice at t = 2^(L-1), then refinement at t = 2^(L-2) .. 1, each stage three launches (histograms, scores, select); the
+ *                host reads `state` once, after the last.  Integer atomics and fixed-order fp64 only: two runs are bitwise equal.
+ * Limits: S * RH * RW < 2^31 - 1 per volume, 1 <= C <= 65535, 1 <= t <= 65536, |shift| <= 2^20.  Outside them, or with a null pointer, a call
+ * is refused (hipErrorInvalidValue, nothing is launched).  No host synchronisation, allocation or copy.
+ * The candidates of a stage in mode 1 or 2, the probe included; 0 where the kernels refuse the stage */
+long mmseg_align_stage_candidates(int mode, int stride, int Z, int Py, int Px);
+/* bytes of h [C,bins,bins] uint32 followed (8-byte aligned) by scores [C,2] fp64 of one stage; 0 outside the limits */
+long mmseg_align_workspace_bytes(int C, int bins);
+/* img [S,H,W] fp32 raw slices, knots [2] fp32 (lo, hi) on the device -> q [S,RH,RW] uint8 */
+int mmseg_align_quantise(const float* img, const float* knots, unsigned char* q, int S, int H, int W, int RH, int RW, int bins,
+                         void* stream);
+/* h [C,bins,bins] (uint32 counts in int32 storage), zeroed here on the stream.  A block counts in LDS (LDS atomics) and merges its
+ * non-empty bins with integer atomics.  aggregate 1: the lanes of a wave that meet the bin of its first active lane are added by one
+ * atomic (the air of an MR frame); 0: one LDS atomic per pair.  The counts are the same.  cand: mode 0 only; state: mode 2 only. */
+int mmseg_align_histograms(const unsigned char* qa, const unsigned char* qb, const int* cand, const double* state, int* h, int Sa,
+                           int RHa, int RWa, int Sb, int RHb, int RWb, int OH, int OW, int mode, int stride, int Z, int Py, int Px, int C,
+                           int bins, int aggregate, void* stream);
+/* scores [C,2] fp64 = (score, N) of every candidate's table in h */
+int mmseg_align_scores(const int* h, const int* cand, const double* state, double* scores, int Sa, int RHa, int RWa, int Sb, int RHb,
+                       int RWb, int OH, int OW, int mode, int stride, int Z, int Py, int Px, int C, int bins, double min_overlap,
+                       void* stream);
+/* the stage's best under the tie rule -> state (item 5) */
+int mmseg_align_select(const double* scores, const int* cand, double* state, int mode, int stride, int Z, int Py, int Px, int C,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

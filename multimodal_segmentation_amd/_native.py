@@ -16,7 +16,7 @@ CSRC_DIR = os.path.join(_PKG_DIR, 'csrc')
 # MMSEG_HIP_LIB: another build of the same library (A/B measurements of kernel variants); the default is the in-tree build
 LIB_PATH = os.environ.get('MMSEG_HIP_LIB') or os.path.join(CSRC_DIR, 'libmmseg_hip.so')
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_DIR), 'include', 'mmseg_hip.h')
-SOURCES = ('conv.hip', 'pointwise.hip', 'norm.hip', 'act16.hip', 'dense.hip', 'tps.hip', 'augment.hip', 'intensity.hip', 'kspace.hip', 'denoise.hip', 'biasfield.hip', 'preprocess.hip', 'postprocess.hip', 'crf.hip', 'loss.hip', 'boundary.hip', 'lovasz.hip', 'pairloss.hip', 'optim.hip')
+SOURCES = ('conv.hip', 'pointwise.hip', 'norm.hip', 'act16.hip', 'dense.hip', 'tps.hip', 'augment.hip', 'intensity.hip', 'kspace.hip', 'denoise.hip', 'biasfield.hip', 'align.hip', 'preprocess.hip', 'postprocess.hip', 'crf.hip', 'loss.hip', 'boundary.hip', 'lovasz.hip', 'pairloss.hip', 'optim.hip')
 
 _CTYPES = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'void*': ctypes.c_void_p,
            'const float*': ctypes.c_void_p, 'float*': ctypes.c_void_p, 'const int*': ctypes.c_void_p, 'int*': ctypes.c_void_p, 'const void*': ctypes.c_void_p,
@@ -49,7 +49,7 @@ def parse_header(path=HEADER_PATH):
 def build(force=False, verbose=False):
     """Compile every HIP source for gfx950 into one in-tree shared library (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC_DIR, h) for h in ('common.hpp', 'smallconv.hpp', 'conv16.hpp', 'wgrad32h.hpp', 's2conv.hpp', 'wino.hpp', 'winof.hpp', 'philox.hpp')]
+    deps = srcs + [os.path.join(CSRC_DIR, h) for h in ('common.hpp', 'smallconv.hpp', 'conv16.hpp', 'wgrad32h.hpp', 's2conv.hpp', 'wino.hpp', 'winof.hpp', 'philox.hpp', 'resample.hpp')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

@@ -7,6 +7,8 @@
                          [--bias_correction off|n3] [--bias_sigma_mm MM] [--bias_levels N] [--bias_iterations N] [--bias_extent 2d|3d]
                          [--denoise off|nlm] [--denoise_sigma auto|V] [--denoise_h K] [--denoise_search N] [--denoise_patch N]
                          [--denoise_search_z N] [--denoise_extent 2d|3d] [--denoise_noise rician|gaussian]
+                         [--align off|mi] [--align_reference MOD] [--align_max_shift_mm MM] [--align_max_slices N] [--align_bins B]
+                         [--align_levels L] [--align_min_overlap F]
                          [--predict_folder PATH] [--predict_out PATH] [--predict_mode simple|def|max] [--predict_order 0|1]
                          [--predict_surface true|false] [--predict_components none|largest] [--predict_connectivity 6|26]
                          [--predict_fill_holes none|2d|3d]
@@ -98,6 +100,17 @@ def parse_arguments(argv=None):
     ap.add_argument('--denoise_extent', choices=['2d', '3d'], help='--denoise nlm searches within the slice / also in the neighbouring '
                                                                    'slices (default: 2d)')
     ap.add_argument('--denoise_noise', choices=['rician', 'gaussian'], help='noise model of --denoise nlm (default: rician)')
+    ap.add_argument('--align', choices=['off', 'mi'],
+                    help='alignment of the modalities of every volume of the run\'s volume folders at load time, instead of what their '
+                         'dataset.json say (mi: a translation by whole slices and pixels that maximises normalised mutual information '
+                         'against the reference modality, on the device)')
+    ap.add_argument('--align_reference', metavar='MOD', help='the modality the others are aligned to (default: the folder\'s first)')
+    ap.add_argument('--align_max_shift_mm', type=float, metavar='MM', help='largest in-plane shift of --align mi in mm (default 40, untuned)')
+    ap.add_argument('--align_max_slices', type=int, metavar='N', help='largest slice shift of --align mi, 0..64 (default 4, untuned)')
+    ap.add_argument('--align_bins', type=int, metavar='B', help='grey levels per volume of --align mi, 2..64 (default 32, untuned)')
+    ap.add_argument('--align_levels', type=int, metavar='L', help='strides 2^(L-1) .. 1 of the search of --align mi, 1..8 (default 3, untuned)')
+    ap.add_argument('--align_min_overlap', type=float, metavar='F',
+                    help='share of the unshifted overlap a shift of --align mi must keep, in (0, 1] (default 0.5, untuned)')
     ap.add_argument('--predict_folder', help='folder of exported volumes (labels optional) to write predicted label volumes for')
     ap.add_argument('--predict_out', help='where to write them (default: <run folder>/predictions_<name in its dataset.json>)')
     ap.add_argument('--predict_mode', choices=['simple', 'def', 'max'], default='simple', help='predict_mask fusion mode')
@@ -145,6 +158,13 @@ def parse_arguments(argv=None):
         ap.error('--bias_sigma_mm, --bias_levels, --bias_iterations and --bias_extent go with --bias_correction n3')
     if any(getattr(args, a) is not None for a, _ in DENOISE_ARGS) and args.denoise != 'nlm':
         ap.error('%s go with --denoise nlm' % ', '.join('--' + a for a, _ in DENOISE_ARGS))
+    if any(getattr(args, a) is not None for a, _ in ALIGN_ARGS) and args.align != 'mi':
+        ap.error('%s go with --align mi' % ', '.join('--' + a for a, _ in ALIGN_ARGS))
+    if args.align:
+        try:
+            align_override({}, args)
+        except ValueError as e:
+            ap.error(str(e))
     if args.denoise_sigma is not None and args.denoise_sigma != 'auto':
         try:
             args.denoise_sigma = float(args.denoise_sigma)
@@ -367,6 +387,49 @@ def warn_predict_denoise(conf, folder, log):
     return True
 
 
+ALIGN_ARGS = (('align_reference', 'reference'), ('align_max_shift_mm', 'max_shift_mm'), ('align_max_slices', 'max_slices'),
+              ('align_bins', 'bins'), ('align_levels', 'levels'), ('align_min_overlap', 'min_overlap'))
+
+
+def align_override(named, args):
+    """the `align` block of `--align` and its companions, else the configuration's `align`, else None: no override, every folder follows
+    its own dataset.json"""
+    from .loaders.volume_folder import check_align
+    block, where = named.get('align'), 'conf.align'
+    if getattr(args, 'align', None):
+        block, where = {'mode': args.align}, '--align'
+        for arg, key in ALIGN_ARGS:
+            if getattr(args, arg, None) is not None:
+                block[key] = getattr(args, arg)
+    if block is None:
+        return None
+    return check_align(dict(block), None, where)
+
+
+def register_align(named, args, names):
+    """Fill loaders.align_conf for the data set names of this run; without an override their entries are removed"""
+    from .loaders import align_conf
+    block = align_override(named, args)
+    for name in names:
+        if block is None:
+            align_conf.pop(name, None)
+        else:
+            align_conf[name] = {k: v for k, v in block.items() if not (k == 'reference' and v is None)}
+    return block
+
+
+def warn_predict_align(conf, folder, log):
+    """a warning when the align setting in force for the predict folder differs from the one the run folder records (conf.align; a run on
+    the synthetic volumes records none: off).  True when it warned."""
+    from .loaders.volume_folder import effective_align
+    trained, here = conf.get('align') or {'mode': 'off'}, effective_align(folder)
+    if here == trained:
+        return False
+    log.warning('--predict_folder: the alignment of %s is set to %s, the run folder %s records %s: the model sees modalities paired '
+                'otherwise than it was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
+    return True
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
@@ -386,12 +449,14 @@ class Experiment(object):
         register_intensity(conf, args, sorted(names))      # before a loader that loads volumes is built: it reads its setting then
         register_bias(conf, args, sorted(names))
         register_denoise(conf, args, sorted(names))
+        register_align(conf, args, sorted(names))
         if data_conf.get(conf.dataset_name):
             conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
-            from .loaders.volume_folder import effective_bias, effective_denoise, effective_intensity
+            from .loaders.volume_folder import effective_align, effective_bias, effective_denoise, effective_intensity
             conf.intensity = effective_intensity(conf.data_folder)  # the setting in force, override or dataset.json: recorded too
             conf.bias_field = effective_bias(conf.data_folder)
             conf.denoise = effective_denoise(conf.data_folder)
+            conf.align = effective_align(conf.data_folder)
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')
@@ -460,6 +525,7 @@ class Experiment(object):
             warn_predict_intensity(conf, args.predict_folder, self.log)
             warn_predict_bias(conf, args.predict_folder, self.log)
             warn_predict_denoise(conf, args.predict_folder, self.log)
+            warn_predict_align(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()

@@ -14,9 +14,13 @@ folder is normalised as its own dataset.json says.
 --bias_correction ...` (or `conf.bias_field`) fills it; empty, each folder follows its own dataset.json.
 
 `denoise_conf` (build-defined) does the same for the `denoise` block (non-local means denoising at load time): `experiment.py
---denoise ...` (or `conf.denoise`) fills it; empty, each folder follows its own dataset.json."""
+--denoise ...` (or `conf.denoise`) fills it; empty, each folder follows its own dataset.json.
+
+`align_conf` (build-defined) does the same for the `align` block (alignment of a volume's modalities by mutual information at load time):
+`experiment.py --align ...` (or `conf.align`) fills it; empty, each folder follows its own dataset.json."""
 
 data_conf = {}
 intensity_conf = {}
 bias_conf = {}
 denoise_conf = {}
+align_conf = {}

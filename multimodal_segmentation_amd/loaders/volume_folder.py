@@ -45,6 +45,17 @@ and everything after them see the denoised volume.  "3d" lets the search reach t
 slices.  `sigma` is in the file's raw grey values; "auto" estimates it per (volume, modality) on the device and runs high on small or busy
 slices.  loaders.denoise_conf overrides the key for a run (experiment.py --denoise).
 
+`align` (optional key of dataset.json; build-defined) pairs the modalities of a volume by themselves.  Absent or {"mode": "off"}: nothing is
+launched, the pairing is the one `slices` states and the centre windows of the resampled frames.  {"mode": "mi", "reference": modality
+(default the first), "max_shift_mm": 40, "max_slices": 4, "bins": 32, "levels": 3, "min_overlap": 0.5, "percentiles": [0.5, 99.5]} (the
+defaults are untuned starting values): every other modality is translated against the reference -- a whole number of slices and of pixels
+of target_resolution along rows and columns -- so that Studholme's normalised mutual information of the two quantised volumes is largest
+(ops.align_volumes; the rule is in include/mmseg_hip.h), once per uploaded volume, in `alignment` -- after `bias_corrected` and before
+`intensity_knots`.  The slices without a partner in every modality are dropped (so the modalities may hold different numbers of slices
+after `slices`), a shifted modality reads a shifted window of its frame, images and labels alike, and the geometry record of a volume
+carries the kept `slices`, the windows and `shift`, so the way back, the scores, tiles and TTA follow.  loaders.align_conf overrides the
+key for a run (experiment.py --align).
+
 For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
 frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
 import json
@@ -134,12 +145,12 @@ def tile_weights(tiles, target):
     return out
 
 
-def tiles_of_other(tiles, resampled, other_resampled, target):
+def tiles_of_other(tiles, resampled, other_resampled, target, shift=0):
     """The windows of another modality (extent other_resampled) for the tiles planned on the predicted one (extent resampled): tile
-    i, whose window starts at s_i = lo - before on the predicted frame, reads the other frame from s_i - c(R_m) + c(R_j), c =
+    i, whose window starts at s_i = lo - before on the predicted frame, reads the other frame from s_i - c(R_m) + c(R_j) + shift, c =
     centre_start, so that the tile which coincides with the centre crop of one frame coincides with the centre crop of the other: the
-    pairing the model was trained on."""
-    shift = centre_start(other_resampled, target) - centre_start(resampled, target)
+    pairing the model was trained on.  shift: the `align` shift of the other modality minus that of the predicted one, in pixels."""
+    shift = centre_start(other_resampled, target) - centre_start(resampled, target) + int(shift)
     return [tile_window(lo - before + shift, other_resampled, target) for lo, kept, before in tiles]
 
 
@@ -329,6 +340,50 @@ def effective_denoise(root, manifest=None):
     return check_denoise(m.get('denoise'), m['modalities'], os.path.join(root, MANIFEST))
 
 
+ALIGN_MODES = ('off', 'mi')
+
+
+def check_align(block, modalities, where):
+    """The normalised form of an `align` block (dataset.json, conf.align): {'mode': 'off'}, or {'mode': 'mi', 'reference', 'max_shift_mm',
+    'max_slices', 'bins', 'levels', 'min_overlap', 'percentiles'} with ops.ALIGN_DEFAULTS filled in.  `reference` is a modality's name;
+    None stands for the folder's first (a command-line override may not know the folder yet: modalities = None).  None and {} mean 'off'."""
+    if block is None:
+        return {'mode': 'off'}
+    if not isinstance(block, dict):
+        raise ValueError('%s: "align" must be an object, got %r' % (where, block))
+    mode = block.get('mode', 'off')
+    if mode not in ALIGN_MODES:
+        raise ValueError('%s: "align" mode must be one of %s, got %r' % (where, ', '.join(ALIGN_MODES), mode))
+    unknown = sorted(set(block) - {'mode', 'reference'} - set(ops.ALIGN_DEFAULTS))
+    if unknown:
+        raise ValueError('%s: "align" has unknown key(s) %s' % (where, ', '.join(unknown)))
+    if mode == 'off':
+        if set(block) - {'mode'}:
+            raise ValueError('%s: "align" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
+        return {'mode': 'off'}
+    reference = block.get('reference')
+    if reference is not None and (not isinstance(reference, str) or (modalities is not None and reference not in modalities)):
+        raise ValueError('%s: "align" reference must be one of the modalities%s, got %r'
+                         % (where, '' if modalities is None else ' (%s)' % ', '.join(modalities), reference))
+    if reference is None and modalities is not None:
+        reference = modalities[0]
+    p = ops.align_params({k: v for k, v in block.items() if k not in ('mode', 'reference')}, '%s: "align"' % where)
+    return dict(mode='mi', reference=reference, **p)
+
+
+def effective_align(root, manifest=None):
+    """the normalised align setting of the folder `root`: the override registered in loaders.align_conf under a data set name that
+    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
+    from . import align_conf, data_conf
+    m = read_manifest(root) if manifest is None else manifest
+    here = os.path.abspath(root)
+    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
+    for n in names:
+        if align_conf.get(n) is not None:
+            return check_align(align_conf[n], m['modalities'], 'loaders.align_conf[%r]' % n)
+    return check_align(m.get('align'), m['modalities'], os.path.join(root, MANIFEST))
+
+
 def read_manifest(root):
     path = os.path.join(root, MANIFEST)
     if not os.path.isfile(path):
@@ -362,6 +417,7 @@ def read_manifest(root):
     check_intensity(m.get('intensity'), m['modalities'], path)
     check_bias(m.get('bias_field'), path)
     check_denoise(m.get('denoise'), m['modalities'], path)
+    check_align(m.get('align'), m['modalities'], path)
     return m
 
 
@@ -382,6 +438,8 @@ class VolumeFolderLoader(object):
         self.intensity = effective_intensity(root, m)          # build-defined: {'mode': 'minmax'} is the reference's rescale
         self.bias_field = effective_bias(root, m)              # build-defined: {'mode': 'off'} uploads the slices as they are
         self.denoise = effective_denoise(root, m)              # build-defined: {'mode': 'off'} launches nothing
+        self.align = effective_align(root, m)                  # build-defined: {'mode': 'off'} launches nothing
+        self._alignments = {}                                  # volume -> alignment()'s result
 
     # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
     def splits(self):
@@ -503,31 +561,96 @@ class VolumeFolderLoader(object):
             params['sigma'] = params['sigma'][modality]
         return ops.nlm_denoise(x, params)
 
+    def alignment(self, volume, xs, geometries):
+        """The folder's `align` setting applied to one volume whose modalities' raw slices xs (per modality [S,H,W] fp32 on the device,
+        after `denoised` and `bias_corrected`) and geometries (per modality a record with `resolution` and `resampled`) are at hand: None
+        when it is off (nothing is launched), else per modality dict(shift=(dz, dy, dx), keep=(start, stop), rows, cols, record).
+        shift: ops.align_volumes' against the reference modality, (0, 0, 0) for the reference itself.  keep: the run of this modality's
+        selected slices that stays -- the reference keeps the intersection over the moving modalities of [max(0, -dz), min(S_a, S_b - dz)),
+        a moving one the same run moved by its dz.  rows / cols: the (lo, kept, before) windows -- crop_pad_map's, bit for bit, for the
+        reference and on every axis without a shift; tile_window(centre_start(R, O) + d, R, O) on an axis shifted by d (a plain window:
+        where crop_pad_map removes ceil(surplus / 2) pixels from BOTH ends of an odd surplus and repeats the last pixel, the shifted
+        window keeps all O).  The one place where this is decided: preprocess, load_volume_for_prediction and upload_volume call it once
+        per uploaded volume, after bias_corrected and before intensity_knots; the result is cached per volume (None: not cached)."""
+        setting = self.align
+        if setting['mode'] == 'off':
+            return None
+        if volume is not None and volume in self._alignments:
+            return self._alignments[volume]
+        OH, OW = self.input_shape[:2]
+        ref = self.modalities.index(setting['reference'])
+        params = {k: v for k, v in setting.items() if k not in ('mode', 'reference')}
+        out = [None] * len(self.modalities)
+        lo, hi = 0, int(xs[ref].shape[0])
+        for j, mod in enumerate(self.modalities):
+            if j == ref:
+                shift, record = (0, 0, 0), None
+            else:
+                shift, record = ops.align_volumes(xs[ref], geometries[ref]['resolution'], xs[j], geometries[j]['resolution'],
+                                                  self.target_resolution, self.input_shape, params)
+                lo, hi = max(lo, -shift[0]), min(hi, int(xs[j].shape[0]) - shift[0])
+                self.log.info('volume %s: %s against %s: shift (%d slices, %d, %d pixels) = (%.1f, %.1f) mm in plane, score %.6f, %.6f at '
+                              'zero shift, %d voxel pairs' % (volume, mod, setting['reference'], shift[0], shift[1], shift[2],
+                                                              shift[1] * self.target_resolution[0], shift[2] * self.target_resolution[1],
+                                                              record[0], record[1], record[2]))
+            RH, RW = geometries[j]['resampled']
+            rows = tile_window(centre_start(RH, OH) + shift[1], RH, OH) if shift[1] else crop_pad_map(RH, OH)
+            cols = tile_window(centre_start(RW, OW) + shift[2], RW, OW) if shift[2] else crop_pad_map(RW, OW)
+            out[j] = dict(shift=shift, rows=rows, cols=cols, record=record)
+        if hi <= lo:
+            raise ValueError('volume %s: after alignment no slice of %s has a partner in every other modality (slice shifts %s for %s '
+                             'slices); check the files, or lower "max_slices" of "align"'
+                             % (volume, setting['reference'], ', '.join('%s: %d' % (m, a['shift'][0]) for m, a in zip(self.modalities, out)),
+                                ', '.join('%s: %d' % (m, x.shape[0]) for m, x in zip(self.modalities, xs))))
+        for a in out:
+            a['keep'] = (lo + a['shift'][0], hi + a['shift'][0])
+        if volume is not None:
+            self._alignments[volume] = out
+        return out
+
+    def _upload(self, volume, require_label):
+        """per modality of one volume: (x, record) -- the selected raw slices [S,H,W] fp32 on the device after denoised and bias_corrected,
+        and the geometry record of load_volume_for_prediction; then the volume's alignment applied to both (slices, label, rows, cols,
+        shift), or the equal-counts check when `align` is off"""
+        device = nn.default_device()
+        xs, geometry = [], []
+        for mod in self.modalities:
+            image, label, res, selected, spacing = self._read_file(volume, mod, require_label)
+            S_file, H, W = image.shape
+            if selected is None:
+                selected = np.arange(S_file)
+            resampled, rows, cols = self.geometry(H, W, res)
+            what = 'volume %s, modality %s' % (volume, mod)
+            x = self.denoised(nn.host_to_device(image[selected], device, np.float32), mod, selected, what)
+            xs.append(self.bias_corrected(x, res, spacing, selected, what))
+            geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
+                                 slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
+                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
+        aligned = self.alignment(volume, xs, geometry)
+        if aligned is None:
+            self._same_counts(volume, [x.shape[0] for x in xs])
+            return xs, geometry
+        for j, (a, g) in enumerate(zip(aligned, geometry)):
+            k0, k1 = a['keep']
+            xs[j] = xs[j][k0:k1]
+            g.update(slices=g['slices'][k0:k1], rows=a['rows'], cols=a['cols'], shift=a['shift'],
+                     label=None if g['label'] is None else np.ascontiguousarray(g['label'][k0:k1]))
+        return xs, geometry
+
     def load_volume_for_prediction(self, volume):
         """One volume, labelled or not, for volume_predictor.py: (images, geometry).  images: per modality the preprocessed container
         [S,OH,OW,1] on the device (ops.preprocess_images: no label kernel is launched).  geometry: per modality a record with what the
         way back needs -- file, raw_shape (S_file, H, W), slices (the selected file indices, in order), resolution, resampled (RH, RW),
         rows / cols (lo, kept, before), label (the selected raw slices [S,H,W] uint8, or None) and slice_spacing (mm between the file's
-        slices, or None)."""
-        device = nn.default_device()
+        slices, or None).  Under `align`, slices and label hold the kept run only, rows / cols are the shifted windows and `shift` is
+        the modality's (dz, dy, dx)."""
         OH, OW = self.input_shape[:2]
-        images, geometry = [], []
-        for mod in self.modalities:
-            image, label, res, selected, spacing = self._read_file(volume, mod, False)
-            S_file, H, W = image.shape
-            if selected is None:
-                selected = np.arange(S_file)
-            resampled, rows, cols = self.geometry(H, W, res)
-            container = torch.zeros((len(selected), OH, OW, 1), dtype=torch.float32, device=device)
-            what = 'volume %s, modality %s' % (volume, mod)
-            x = self.denoised(nn.host_to_device(image[selected], device, np.float32), mod, selected, what)
-            x = self.bias_corrected(x, res, spacing, selected, what)
-            ops.preprocess_images(x, container, resampled, rows, cols, 0, knots=self.intensity_knots(x, resampled, mod))
+        xs, geometry = self._upload(volume, False)
+        images = []
+        for mod, x, g in zip(self.modalities, xs, geometry):
+            container = torch.zeros((x.shape[0], OH, OW, 1), dtype=torch.float32, device=x.device)
+            ops.preprocess_images(x, container, g['resampled'], g['rows'], g['cols'], 0, knots=self.intensity_knots(x, g['resampled'], mod))
             images.append(container)
-            geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
-                                 slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
-                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing))
-        self._same_counts(volume, [g.shape[0] for g in images])
         return images, geometry
 
     def _same_counts(self, volume, counts):
@@ -540,32 +663,24 @@ class VolumeFolderLoader(object):
         """(raw, geometry) of one volume: per modality the selected raw slices [S,H,W] fp32 on the device, uploaded once, and the
         record of load_volume_for_prediction plus `knots`: intensity_knots' result, selected once here and shared by every tile.
         What load_volume_tiles builds its containers from, for every predicted modality."""
-        device = nn.default_device()
-        raw, geometry = [], []
-        for mod in self.modalities:
-            image, label, res, selected, spacing = self._read_file(volume, mod, False)
-            S_file, H, W = image.shape
-            if selected is None:
-                selected = np.arange(S_file)
-            resampled, rows, cols = self.geometry(H, W, res)
-            what = 'volume %s, modality %s' % (volume, mod)
-            x = self.denoised(nn.host_to_device(image[selected], device, np.float32), mod, selected, what)
-            raw.append(self.bias_corrected(x, res, spacing, selected, what))
-            geometry.append(dict(file=self.manifest['volumes'][str(volume)][mod]['file'], raw_shape=(S_file, H, W),
-                                 slices=[int(i) for i in selected], resolution=res, resampled=resampled, rows=rows, cols=cols,
-                                 label=None if label is None else np.ascontiguousarray(label[selected]), slice_spacing=spacing,
-                                 knots=self.intensity_knots(raw[-1], resampled, mod)))
-        self._same_counts(volume, [x.shape[0] for x in raw])
+        raw, geometry = self._upload(volume, False)
+        for mod, x, g in zip(self.modalities, raw, geometry):
+            g['knots'] = self.intensity_knots(x, g['resampled'], mod)
         return raw, geometry
 
     def tile_plan(self, geometry, m, overlap):
         """per modality (rows, cols): the tiles of the frame of the predicted modality m (tile_axis with overlap = (rows, columns)), and
-        for every other modality the windows that go with them (tiles_of_other)"""
+        for every other modality the windows that go with them (tiles_of_other, moved by the difference of the records' `shift`s)"""
         OH, OW = self.input_shape[:2]
         RH, RW = geometry[m]['resampled']
         rows, cols = tile_axis(RH, OH, overlap[0]), tile_axis(RW, OW, overlap[1])
-        return [(rows, cols) if j == m else (tiles_of_other(rows, RH, g['resampled'][0], OH), tiles_of_other(cols, RW, g['resampled'][1], OW))
-                for j, g in enumerate(geometry)]
+        own = geometry[m].get('shift', (0, 0, 0))
+        plan = []
+        for j, g in enumerate(geometry):
+            d = g.get('shift', (0, 0, 0))
+            plan.append((rows, cols) if j == m else (tiles_of_other(rows, RH, g['resampled'][0], OH, d[1] - own[1]),
+                                                     tiles_of_other(cols, RW, g['resampled'][1], OW, d[2] - own[2])))
+        return plan
 
     def load_volume_tiles(self, volume, m, overlap, uploaded=None):
         """One volume cut into the tiles that cover the whole resampled frame of modality m: (images, geometry, plan).  images: per
@@ -599,20 +714,42 @@ class VolumeFolderLoader(object):
                 extra.append((spacing, selected, 'volume %s, modality %s' % (v, mod)))
             extras.append(extra)
             counts = [p[0].shape[0] for p in per_mod]
-            if len(set(counts)) != 1:
+            if self.align['mode'] != 'off':          # the kept run decides the count; unequal counts are what alignment is for
+                keep = (self._alignments.get(v) or self._aligned(v, per_mod, extra)[1])[0]['keep']
+                counts = [keep[1] - keep[0]]
+            elif len(set(counts)) != 1:
                 raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the '
                                  'matching ranges under "slices" in %s'
                                  % (v, ', '.join('%s: %d' % mc for mc in zip(self.modalities, counts)), MANIFEST))
             raw.append(per_mod)
             index.append(np.array([v] * counts[0]))
         index = np.concatenate(index, axis=0) if index else np.zeros((0,), np.int64)
-        images, masks = self.preprocess(raw, len(index), extras)
+        images, masks = self.preprocess(raw, len(index), extras, volumes)
         return MultimodalPairedData(images, masks, index, downsample=downsample, num_modalities=len(self.modalities))
 
-    def preprocess(self, raw, n, extras=None):
+    def _aligned(self, volume, per_mod, extra):
+        """(xs, alignment, geometries): the modalities of one volume of preprocess's `raw` on the device after denoised and
+        bias_corrected, alignment()'s result for them (None when `align` is off) and their (resolution, resampled) records"""
+        device = nn.default_device()
+        xs, geos = [], []
+        for mod, (image, label, res) in enumerate(per_mod):
+            H, W = image.shape[1:]
+            RH = resampled_size(H, res[0], self.target_resolution[0])
+            RW = resampled_size(W, res[1], self.target_resolution[1])
+            if RH < 1 or RW < 1:
+                raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
+            spacing, selected, what = extra[mod] if extra is not None else (None, None, 'modality %s' % self.modalities[mod])
+            x = self.denoised(nn.host_to_device(image, device, np.float32), self.modalities[mod], selected, what)
+            xs.append(self.bias_corrected(x, res, spacing, selected, what))
+            geos.append(dict(resolution=res, resampled=(RH, RW)))
+        return xs, self.alignment(volume, xs, geos), geos
+
+    def preprocess(self, raw, n, extras=None, volumes=None):
         """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks].
         extras: per volume, per modality (slice_spacing or None, the selected file indices or None, a name for messages): what
-        denoised and bias_corrected need beyond the resolution; without it the slices count as one run of a file without slice_spacing."""
+        denoised and bias_corrected need beyond the resolution; without it the slices count as one run of a file without slice_spacing.
+        volumes: per volume its id, the key under which `alignment` caches (None: nothing is cached).  Under `align` a volume
+        contributes its kept run of slices, and n counts those."""
         device = nn.default_device()
         OH, OW = self.input_shape[:2]
         M, K = len(self.modalities), self.num_masks
@@ -621,19 +758,16 @@ class VolumeFolderLoader(object):
         values = nn.host_to_device(np.asarray(self.label_values), device, np.int32)
         n0 = 0
         for vol, per_mod in enumerate(raw):
-            S = per_mod[0][0].shape[0]
+            xs, aligned, geos = self._aligned(None if volumes is None else volumes[vol], per_mod, None if extras is None else extras[vol])
+            S = per_mod[0][0].shape[0] if aligned is None else aligned[0]['keep'][1] - aligned[0]['keep'][0]
             for mod, (image, label, res) in enumerate(per_mod):
-                H, W = image.shape[1:]
-                RH = resampled_size(H, res[0], self.target_resolution[0])
-                RW = resampled_size(W, res[1], self.target_resolution[1])
-                if RH < 1 or RW < 1:
-                    raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
-                spacing, selected, what = extras[vol][mod] if extras is not None else (None, None, 'modality %s' % self.modalities[mod])
-                x = self.denoised(nn.host_to_device(image, device, np.float32), self.modalities[mod], selected, what)
-                x = self.bias_corrected(x, res, spacing, selected, what)
+                RH, RW = geos[mod]['resampled']
+                x, rows, cols = xs[mod], crop_pad_map(RH, OH), crop_pad_map(RW, OW)
+                if aligned is not None:
+                    k0, k1 = aligned[mod]['keep']
+                    x, label, rows, cols = x[k0:k1], label[k0:k1], aligned[mod]['rows'], aligned[mod]['cols']
                 ops.preprocess_volume(x, nn.host_to_device(label, device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
-                                      (RH, RW), crop_pad_map(RH, OH), crop_pad_map(RW, OW), mod,
-                                      knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))
+                                      (RH, RW), rows, cols, mod, knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))
             n0 += S
         assert n0 == n
         return nn.to_numpy(images), nn.to_numpy(masks)

@@ -2294,6 +2294,209 @@ def preprocess_quantiles(img, resampled, ranks, per_volume):
     return x
 
 
+ALIGN_DEFAULTS = dict(max_shift_mm=40.0, max_slices=4, bins=32, levels=3, min_overlap=0.5,
+                      percentiles=(0.5, 99.5))                                     # untuned starting values (README)
+ALIGN_MAX_BINS, ALIGN_MAX_LEVELS, ALIGN_MAX_SLICES, ALIGN_MAX_SHIFT = 64, 8, 64, 1 << 20          # csrc/align.hip
+ALIGN_STATE = 8                    # fp64 words of the state block (include/mmseg_hip.h)
+ALIGN_AGGREGATE = True             # the histogram kernel's wave aggregation (DESIGN.md section 8 has the measurement)
+ALIGN_WORKSPACE_CAP = 512 << 20
+
+
+def align_params(params=None, what='align_volumes'):
+    """ALIGN_DEFAULTS overlaid with `params`, validated: max_shift_mm finite >= 0, max_slices a whole number in 0..64, bins in 2..64,
+    levels in 1..8, min_overlap in (0, 1], percentiles two numbers 0 <= lo < hi <= 100"""
+    p = dict(ALIGN_DEFAULTS)
+    unknown = sorted(set(params or {}) - set(p))
+    if unknown:
+        raise ValueError('%s: unknown key(s) %s (known: %s)' % (what, ', '.join(unknown), ', '.join(sorted(p))))
+    p.update(params or {})
+    if not _is_number(p['max_shift_mm']) or not np.isfinite(p['max_shift_mm']) or p['max_shift_mm'] < 0:
+        raise ValueError('%s: max_shift_mm must be a finite number >= 0, got %r' % (what, p['max_shift_mm']))
+    for key, low, top in (('max_slices', 0, ALIGN_MAX_SLICES), ('bins', 2, ALIGN_MAX_BINS), ('levels', 1, ALIGN_MAX_LEVELS)):
+        v = p[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not low <= v <= top:
+            raise ValueError('%s: %s must be a whole number in %d..%d, got %r' % (what, key, low, top, v))
+    if not _is_number(p['min_overlap']) or not 0 < p['min_overlap'] <= 1:
+        raise ValueError('%s: min_overlap must be a number in (0, 1] (the share of the zero shift\'s overlap a candidate must keep), '
+                         'got %r' % (what, p['min_overlap']))
+    q = p['percentiles']
+    if (not isinstance(q, (list, tuple)) or len(q) != 2 or any(not _is_number(v) or not np.isfinite(v) for v in q)
+            or not 0 <= q[0] < q[1] <= 100):
+        raise ValueError('%s: percentiles must be two numbers [lo, hi] with 0 <= lo < hi <= 100, got %r' % (what, q))
+    return dict(max_shift_mm=float(p['max_shift_mm']), max_slices=int(p['max_slices']), bins=int(p['bins']), levels=int(p['levels']),
+                min_overlap=float(p['min_overlap']), percentiles=[float(q[0]), float(q[1])])
+
+
+def align_quantise(x, resampled, knots, bins):
+    """q [S,RH,RW] uint8 on the device: the raw slices x [S,H,W] fp32 resampled to `resampled` = (RH, RW) as preprocess_images resamples
+    them, binned between knots = (lo, hi) (fp32 [2] or [1,2] on the device: preprocess_quantiles' result, per volume) into `bins` = 2..64
+    levels (csrc/align.hip; the rule is in include/mmseg_hip.h).  No host synchronisation."""
+    if x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError('align_quantise: x must be an fp32 [S,H,W] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+    S, H, W = x.shape
+    RH, RW = int(resampled[0]), int(resampled[1])
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= ALIGN_MAX_BINS:
+        raise ValueError('align_quantise: bins must be a whole number in 2..%d, got %r' % (ALIGN_MAX_BINS, bins))
+    if knots.dtype != torch.float32 or knots.numel() != 2 or knots.device != x.device:
+        raise ValueError('align_quantise: knots must be the two fp32 values (lo, hi) on %s, got %s %s' % (x.device, knots.dtype, tuple(knots.shape)))
+    if S < 1 or H < 1 or W < 1 or RH < 1 or RW < 1 or S * RH * RW >= 2 ** 31 - 1 or H * W >= 2 ** 31 - 1 or S > 65535:
+        raise ValueError('align_quantise: a volume of %d x %d x %d resampled to %d x %d is outside the kernel\'s limits' % (S, H, W, RH, RW))
+    q = _new((S, RH, RW), x, torch.uint8)
+    N.call('mmseg_align_quantise', _c(x), _c(knots), q, S, H, W, RH, RW, int(bins))
+    return q
+
+
+def _align_frames(op, qa, qb, window):
+    for name, q in (('qa', qa), ('qb', qb)):
+        if q.dim() != 3 or q.dtype != torch.uint8 or not q.is_contiguous() or min(q.shape) < 1 or q.numel() >= 2 ** 31 - 1:
+            raise ValueError('%s: %s must be a contiguous, non-empty uint8 [S,RH,RW] tensor of fewer than 2^31 - 1 bytes, got %s %s'
+                             % (op, name, q.dtype, tuple(q.shape)))
+    if qb.device != qa.device:
+        raise ValueError('%s: qa is on %s, qb on %s' % (op, qa.device, qb.device))
+    return _align_shapes(op, tuple(qa.shape), tuple(qb.shape), window)
+
+
+def _align_shapes(op, shape_a, shape_b, window):
+    geo = [int(v) for v in tuple(shape_a) + tuple(shape_b)]
+    O = (int(window), int(window)) if _is_number(window) else (int(window[0]), int(window[1]))
+    if len(geo) != 6 or min(geo) < 1 or min(O) < 1:
+        raise ValueError('%s: shapes %s and %s with a window of %s' % (op, tuple(shape_a), tuple(shape_b), O))
+    return geo + list(O)
+
+
+def _align_stage(op, stage, stride, device):
+    """(cand, state, [mode, stride, Z, Py, Px, C]) of a stage description: a sequence / int array [C,3] of (dz, dy, dx) (mode 0), or
+    ('lattice', Z, Py, Px) (mode 1), or ('refine', Z, Py, Px, state) with the fp64 [8] state block on the device (mode 2)"""
+    t = int(stride)
+    if not 1 <= t <= 1 << 16:
+        raise ValueError('%s: stride must lie in 1..65536, got %r' % (op, stride))
+    if isinstance(stage, tuple) and stage and stage[0] in ('lattice', 'refine'):
+        mode = 1 if stage[0] == 'lattice' else 2
+        Z, Py, Px = (int(v) for v in stage[1:4])
+        state = stage[4] if mode == 2 else None
+        if mode == 2 and (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.numel() != ALIGN_STATE):
+            raise ValueError('%s: a refinement stage needs the fp64 [%d] state block on the device' % (op, ALIGN_STATE))
+        C = N.call('mmseg_align_stage_candidates', mode, t, Z, Py, Px) if min(Z, Py, Px) >= 0 else 0
+        if not C:
+            raise ValueError('%s: a %s stage of %d slices x %d x %d pixels at stride %d is outside the kernels\' limits (65535 candidates)'
+                             % (op, stage[0], Z, Py, Px, t))
+        return None, state, [mode, t, Z, Py, Px, int(C)]
+    cand = np.asarray(stage.cpu() if isinstance(stage, torch.Tensor) else stage)
+    if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= cand.shape[0] <= 65535 or cand.dtype.kind not in 'iu':
+        raise ValueError('%s: candidates must be 1..65535 whole-number rows (dz, dy, dx), got %s %s' % (op, cand.dtype, cand.shape))
+    if np.abs(cand).max() > ALIGN_MAX_SHIFT:
+        raise ValueError('%s: a candidate shift beyond %d' % (op, ALIGN_MAX_SHIFT))
+    dev = torch.from_numpy(np.ascontiguousarray(cand, np.int32)).to(device)
+    return dev, None, [0, t, 0, 0, 0, int(cand.shape[0])]
+
+
+def _align_bins(op, bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= bins <= ALIGN_MAX_BINS:
+        raise ValueError('%s: bins must be a whole number in 2..%d, got %r' % (op, ALIGN_MAX_BINS, bins))
+    return int(bins)
+
+
+def align_histograms(qa, qb, window, stage, stride, bins, aggregate=None, out=None):
+    """h [C,bins,bins] int32 on the device: per candidate of `stage` (see _align_stage: a list of (dz, dy, dx), or a lattice /
+    refinement description) the joint histogram of the quantised frames qa [Sa,RHa,RWa], qb [Sb,RHb,RWb] (uint8; a byte >= bins counts as
+    bins - 1) over the overlap of the frames at `stride`, `window` = the network's input extent O or (OH, OW) that defines the zero
+    shift (csrc/align.hip; the rule is in include/mmseg_hip.h).  Exact integer counts; aggregate chooses the kernel's way of adding
+    them (None: ALIGN_AGGREGATE) and does not change them.  No host synchronisation."""
+    geo = _align_frames('align_histograms', qa, qb, window)
+    B = _align_bins('align_histograms', bins)
+    cand, state, st = _align_stage('align_histograms', stage, stride, qa.device)
+    C = st[-1]
+    if out is None:
+        out = _new((C, B, B), qa, torch.int32)
+    elif out.dtype != torch.int32 or out.numel() != C * B * B or not out.is_contiguous() or out.device != qa.device:
+        raise ValueError('align_histograms: out must be a contiguous int32 [%d,%d,%d] tensor on %s' % (C, B, B, qa.device))
+    agg = ALIGN_AGGREGATE if aggregate is None else bool(aggregate)
+    N.call('mmseg_align_histograms', qa, qb, cand, state, out, *(geo + st + [B, int(agg)]))
+    return out
+
+
+def align_scores(h, shape_a, shape_b, window, stage, stride, min_overlap, out=None):
+    """scores [C,2] fp64 on the device = (score, N) per candidate from its table in h [C,bins,bins] int32: Studholme's normalised mutual
+    information in fp64, -1 where N == 0, H(A,B) == 0 or the candidate keeps less than min_overlap of the zero shift's overlap
+    (shape_a, shape_b = the (S, RH, RW) of the two frames; the rule is in include/mmseg_hip.h)"""
+    if h.dim() != 3 or h.dtype != torch.int32 or h.shape[1] != h.shape[2] or not h.is_contiguous():
+        raise ValueError('align_scores: h must be a contiguous int32 [C,bins,bins] tensor, got %s %s' % (h.dtype, tuple(h.shape)))
+    geo = _align_shapes('align_scores', shape_a, shape_b, window)
+    B = _align_bins('align_scores', int(h.shape[1]))
+    cand, state, st = _align_stage('align_scores', stage, stride, h.device)
+    if st[-1] != h.shape[0]:
+        raise ValueError('align_scores: h holds %d tables, the stage has %d candidates' % (h.shape[0], st[-1]))
+    if not _is_number(min_overlap) or not 0 <= min_overlap <= 1:
+        raise ValueError('align_scores: min_overlap must lie in [0, 1], got %r' % (min_overlap,))
+    if out is None:
+        out = _new((st[-1], 2), h, torch.float64)
+    N.call('mmseg_align_scores', h, cand, state, out, *(geo + st + [B, float(min_overlap)]))
+    return out
+
+
+def align_select(scores, stage, stride, state=None):
+    """The stage's best candidate under the tie rule, written into the fp64 [8] state block on the device (a zeroed new one by default)
+    and returned: (dz, dy, dx), its score, the zero-shift probe's score, its N, admissible?, stages run (include/mmseg_hip.h)"""
+    if scores.dim() != 2 or scores.shape[1] != 2 or scores.dtype != torch.float64 or not scores.is_contiguous():
+        raise ValueError('align_select: scores must be a contiguous fp64 [C,2] tensor, got %s %s' % (scores.dtype, tuple(scores.shape)))
+    cand, st_state, st = _align_stage('align_select', stage, stride, scores.device)
+    if st[-1] != scores.shape[0]:
+        raise ValueError('align_select: %d scores, the stage has %d candidates' % (scores.shape[0], st[-1]))
+    if state is None:
+        state = st_state if st_state is not None else torch.zeros(ALIGN_STATE, dtype=torch.float64, device=scores.device)
+    if state.dtype != torch.float64 or state.numel() != ALIGN_STATE or (st_state is not None and state.data_ptr() != st_state.data_ptr()):
+        raise ValueError('align_select: state must be the fp64 [%d] block the refinement stage reads' % ALIGN_STATE)
+    N.call('mmseg_align_select', scores, cand, state, *st)
+    return state
+
+
+def align_search(qa, qb, window, Z, Py, Px, bins, levels, min_overlap, aggregate=None):
+    """The search of include/mmseg_hip.h over quantised frames: the lattice at stride 2^(levels-1), then refinement down to stride 1, every
+    stage enumerated, scored and selected on the device -> the fp64 [8] state block on the device.  No host synchronisation."""
+    geo = _align_frames('align_search', qa, qb, window)
+    B = _align_bins('align_search', bins)
+    state = torch.zeros(ALIGN_STATE, dtype=torch.float64, device=qa.device)
+    for s in range(int(levels) - 1, -1, -1):
+        stage = ('lattice', Z, Py, Px) if s == int(levels) - 1 else ('refine', Z, Py, Px, state)
+        C = _align_stage('align_search', stage, 1 << s, qa.device)[2][-1]
+        nbytes = N.call('mmseg_align_workspace_bytes', C, B)
+        if not nbytes or nbytes > ALIGN_WORKSPACE_CAP:
+            raise ValueError('align_search: %d candidates of %d x %d bins need %d MB of histograms (cap %d MB): raise levels, or lower '
+                             'max_shift_mm / max_slices / bins' % (C, B, B, (C * B * B * 4) >> 20, ALIGN_WORKSPACE_CAP >> 20))
+        ws = _ws('align', nbytes // 8, qa.device, torch.float64)
+        words = (C * B * B * 4 + 7) // 8
+        h = ws[:words].view(torch.int32)[:C * B * B].view(C, B, B)
+        scores = ws[words:words + 2 * C].view(C, 2)
+        align_histograms(qa, qb, geo[6:], stage, 1 << s, B, aggregate, out=h)
+        align_scores(h, geo[:3], geo[3:6], geo[6:], stage, 1 << s, min_overlap, out=scores)
+        align_select(scores, stage, 1 << s, state)
+    return state
+
+
+def align_volumes(a, res_a, b, res_b, target_resolution, input_shape, params=None):
+    """The translation that pairs the moving volume b [Sb,Hb,Wb] with the reference volume a [Sa,Ha,Wa] (fp32 raw slices on the device,
+    res_x = mm per pixel along rows and columns): ((dz, dy, dx), (score, zero-shift score, N)) -- reference slice i shows the anatomy of
+    moving slice i + dz, and the centre window of b's resampled frame moves by (dy, dx) pixels of target_resolution.  params: keys of
+    ALIGN_DEFAULTS.  Both volumes are quantised on their resampled grids between their own percentiles and the search maximises
+    Studholme's normalised mutual information (csrc/align.hip; the rule is in include/mmseg_hip.h).  One device-to-host copy, at the end."""
+    p = align_params(params)
+    tr = (float(target_resolution[0]), float(target_resolution[1]))
+    qs = []
+    for x, res in ((a, res_a), (b, res_b)):
+        if x.dim() != 3 or x.dtype != torch.float32 or min(x.shape) < 1:
+            raise ValueError('align_volumes: a volume must be a non-empty fp32 [S,H,W] tensor, got %s %s' % (x.dtype, tuple(x.shape)))
+        R = tuple(int(np.round(n * (float(r) / t))) for n, r, t in zip(x.shape[1:], res, tr))
+        if min(R) < 1:
+            raise ValueError('align_volumes: a %d x %d slice at %s mm resamples to nothing at %s mm' % (x.shape[1], x.shape[2], tuple(res), tr))
+        n = x.shape[0] * R[0] * R[1]
+        ranks = [int(np.floor((n - 1) * (q / 100.0))) for q in p['percentiles']]
+        qs.append(align_quantise(x, R, preprocess_quantiles(x, R, ranks, True), p['bins']))
+    Py, Px = (int(np.floor(p['max_shift_mm'] / t)) for t in tr)
+    state = align_search(qs[0], qs[1], input_shape[:2], p['max_slices'], Py, Px, p['bins'], p['levels'], p['min_overlap'])
+    rec = state.cpu().tolist()
+    return (int(rec[0]), int(rec[1]), int(rec[2])), (rec[3], rec[4], int(rec[5]))
+
+
 def restore_label(prob, values, raw_hw, resampled, rows, cols, order=1):
     """prob [S,OH,OW,C] fp32 (a segmentor's output on the device, organ channels first) -> uint8 grey values [S,H,W] on the raw grid
     raw_hw = (H, W) of the volume that preprocess_volume brought to [OH,OW] with `resampled` = (RH, RW) and the per-axis index maps

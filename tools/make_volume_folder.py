@@ -11,7 +11,7 @@ ones.
 
     python tools/make_volume_folder.py OUT [--volumes 4] [--size 64] [--slices 6] [--modalities t1 t2] [--masks 4] [--seed 0]
                                        [--raw_size LO HI] [--name chaos] [--unlabelled] [--slice_spacing LO HI] [--hot_voxels N]
-                                       [--bias_field STRENGTH] [--rician_noise STD]
+                                       [--bias_field STRENGTH] [--rician_noise STD] [--misalign PIXELS [--misalign_aligned]]
     python experiment.py --config dafnet_config_chaos --split 0 --data_folder OUT
 """
 import argparse
@@ -94,8 +94,32 @@ def default_splits(ids):
     return out
 
 
+def misaligned_volume(rng, align_rng, anatomy_seed, modalities, slices, size, pixels, values, aligned):
+    """One volume whose modalities are windows of ONE canvas drawn at TARGET_RESOLUTION (a raw pixel is a resampled pixel): per modality
+    (image, label, leading extra slices) and, per later modality, the truth (dz, dy, dx) in the convention of the alignment rule
+    (include/mmseg_hip.h) against the first: its slice i + dz and its centre window moved by (dy, dx) show what slice i and the centre
+    window of the first modality show.  A window's extent is size + 0..8 per axis; the first modality's is centred on the canvas, a later
+    one's is cut `offset` pixels off centre, offset from [-pixels, pixels] per axis (so |dy|, |dx| <= pixels), and carries 0..2 extra
+    leading / trailing slices (dz = the leading ones).  aligned: the same draws, but every offset is 0."""
+    margin = pixels + 4
+    canvas = size + 2 * pixels + 12
+    out, truth = [], []
+    for mod in range(len(modalities)):
+        H, W = (size + int(align_rng.randint(0, 9)) for _ in range(2))
+        off = (0, 0) if mod == 0 else tuple(int(align_rng.randint(-pixels, pixels + 1)) for _ in range(2))
+        before, after = (0, 0) if mod == 0 else (int(align_rng.randint(0, 3)), int(align_rng.randint(0, 3)))
+        if aligned:
+            off = (0, 0)
+        image, label = make_volume(rng, anatomy_seed - before, mod, before + slices + after, canvas, canvas, values)
+        y0, x0 = (margin - (n - size + 1) // 2 + o for n, o in zip((H, W), off))          # centre_start(n, size) = (n - size + 1) // 2
+        out.append((image[:, y0:y0 + H, x0:x0 + W].copy(), label[:, y0:y0 + H, x0:x0 + W].copy(), before))
+        if mod:
+            truth.append((before, -off[0], -off[1]))
+    return out, truth
+
+
 def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), masks=4, seed=0, raw_size=None, name='chaos', unlabelled=False,
-                 slice_spacing=None, hot_voxels=0, bias_field=0.0, rician_noise=0.0):
+                 slice_spacing=None, hot_voxels=0, bias_field=0.0, rician_noise=0.0, misalign=None, misalign_aligned=False):
     """unlabelled: the files carry no `label` array (scans to be segmented: experiment.py --predict_folder); everything else, the random
     draws included, is as without it.  slice_spacing = (LO, HI): every file also stores `slice_spacing`, mm between its slices, drawn
     from [LO, HI] by a generator of its own, so that every other draw is as without it.  hot_voxels = N > 0: every file is multiplied
@@ -104,7 +128,11 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
     STRENGTH > 0: every file carries a smooth multiplicative field exp(f), |f| <= STRENGTH (add_bias_field; a generator of its own), and the
     manifest gets "bias_field": {"mode": "n3"} so that the loader removes it.  rician_noise = STD > 0: every file, after all of the above,
     passes through a Rician channel of that standard deviation in grey values (add_rician_noise; a generator of its own), and the
-    manifest gets "denoise": {"mode": "nlm", "sigma": STD} so that the loader removes it."""
+    manifest gets "denoise": {"mode": "nlm", "sigma": STD} so that the loader removes it.  misalign = PIXELS >= 0: the modalities of a
+    volume are windows of one canvas at TARGET_RESOLUTION, cut off centre by up to PIXELS and with extra slices at both ends
+    (misaligned_volume; the new draws come from a generator of their own), the manifest states NO `slices` but "align": {"mode": "mi",
+    "max_shift_mm": PIXELS pixels in mm, "max_slices": 3, "bins": 16}, and the truth goes to misalignment.json ({volume: {modality: [dz, dy,
+    dx]}}).  misalign_aligned: the same canvases with every offset 0, `slices` stated and no "align" key: what alignment should arrive at."""
     if volumes < 3:
         raise ValueError('need at least 3 volumes (training, validation, test)')
     os.makedirs(out, exist_ok=True)
@@ -121,12 +149,31 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
     if not rician_noise >= 0:
         raise ValueError('rician_noise must be 0 or more, got %r' % (rician_noise,))
     noise_rng = np.random.RandomState(seed + 4000003)
+    if misalign is not None and (misalign < 0 or raw_size is not None or slice_spacing is not None or hot_voxels or bias_field or rician_noise):
+        raise ValueError('misalign must be 0 or more pixels and goes without raw_size, slice_spacing, hot_voxels, bias_field and '
+                         'rician_noise, got %r' % (misalign,))
+    align_rng = np.random.RandomState(seed + 5000003)
+    truths = {}
     values = label_values(masks)
     ids = list(range(1, volumes + 1))
     manifest = dict(name=name, modalities=list(modalities), label_values=values, target_resolution=list(TARGET_RESOLUTION),
                     input_shape=[size, size, 1], splits=default_splits(ids), volumes={})
     for v in ids:
         entry = {}
+        if misalign is not None:
+            windows, truth = misaligned_volume(rng, align_rng, 1000 * (seed + 1) * v, modalities, slices, size, misalign, values, misalign_aligned)
+            truths[str(v)] = {mod_name: list(t) for mod_name, t in zip(modalities[1:], truth)}
+            for mod_name, (image, label, before) in zip(modalities, windows):
+                fname = 'vol%02d_%s.npz' % (v, mod_name)
+                arrays = dict(image=image, resolution=np.asarray(TARGET_RESOLUTION, np.float64))
+                if not unlabelled:
+                    arrays['label'] = label
+                np.savez_compressed(os.path.join(out, fname), **arrays)
+                entry[mod_name] = {'file': fname}
+                if misalign_aligned and image.shape[0] != slices:
+                    entry[mod_name]['slices'] = [[before, before + slices]]
+            manifest['volumes'][str(v)] = entry
+            continue
         for mod, mod_name in enumerate(modalities):
             res = rng.uniform(1.2, 2.4, size=2)
             if raw_size is None:      # field of view of 0.85 .. 1.2 input extents: crop on some axes, pad on others
@@ -156,6 +203,12 @@ def write_folder(out, volumes=4, size=64, slices=6, modalities=('t1', 't2'), mas
         manifest['bias_field'] = {'mode': 'n3'}
     if rician_noise:
         manifest['denoise'] = {'mode': 'nlm', 'sigma': float(rician_noise)}
+    if misalign is not None:
+        if not misalign_aligned:
+            manifest['align'] = {'mode': 'mi', 'max_shift_mm': (misalign + 0.5) * min(TARGET_RESOLUTION), 'max_slices': 3,
+                                 'bins': 16}
+        with open(os.path.join(out, 'misalignment.json'), 'w') as f:
+            json.dump(truths, f, indent=1)
     with open(os.path.join(out, 'dataset.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
     return manifest
@@ -183,9 +236,14 @@ def main(argv=None):
     ap.add_argument('--rician_noise', type=float, default=0.0, metavar='STD',
                     help='pass every file through a Rician channel of this standard deviation in grey values, and "denoise": {"mode": "nlm", '
                          '"sigma": STD} in dataset.json (what the denoising of the loader is for)')
+    ap.add_argument('--misalign', type=int, default=None, metavar='PIXELS',
+                    help='cut the modalities of a volume from one canvas, up to PIXELS off centre and with extra slices, state no "slices" '
+                         'but "align": {"mode": "mi"} in dataset.json, and write the truth to misalignment.json (what the alignment of the '
+                         'loader is for)')
+    ap.add_argument('--misalign_aligned', action='store_true', help='with --misalign: the same canvases, offsets 0, "slices" stated, no "align"')
     a = ap.parse_args(argv)
     m = write_folder(a.out, a.volumes, a.size, a.slices, a.modalities, a.masks, a.seed, a.raw_size, a.name, a.unlabelled, a.slice_spacing,
-                     a.hot_voxels, a.bias_field, a.rician_noise)
+                     a.hot_voxels, a.bias_field, a.rician_noise, a.misalign, a.misalign_aligned)
     print('wrote %d volumes x %d modalities to %s' % (len(m['volumes']), len(m['modalities']), a.out))
 
 
