@@ -338,7 +338,10 @@ int mmseg_tps_warp_fwd(const float* vol, const float* theta, const float* Mb, fl
                        void* stream);
 long mmseg_tps_scatter_workspace_floats(int B, int H, int W, int C);
 /* acc: mmseg_tps_scatter_workspace_floats floats (8-byte aligned) -- 64-bit fixed-point accumulators of the d_vol scatter, which
- * make it independent of the order of the atomics (bitwise reproducible) */
+ * make it independent of the order of the atomics (bitwise reproducible).  Each of the four contributions of an output pixel to
+ * d_vol is rounded to a multiple of 2^-36 (error <= 2^-37) and the sum of an element is exact while it stays below 2^27 (1.34e8) in
+ * magnitude; beyond that it wraps, unchecked.  dvol or dtheta may be NULL to skip that gradient (dloc is written only when dtheta
+ * is requested); C must be 8 and H, W >= 2, as in the forward, else hipErrorInvalidValue. */
 int mmseg_tps_warp_bwd(const float* vol, const float* loc, const float* Mb, const float* dout, float* dvol, float* dtheta, float* dloc,
                        float* ws, float* acc, int B, int H, int W, int C, void* stream);
 

@@ -65,6 +65,15 @@ __global__ void tps_warp_fwd_kernel(const float* __restrict__ vol, const float* 
 // backward: d_vol is a scatter (4 taps per output pixel).  The contributions are accumulated with 64-bit INTEGER atomics in
 // fixed point (2^-36 resolution, range +-1.3e8): integer addition is associative, so the result does not depend on the order
 // in which the atomics land and the whole training step stays bitwise reproducible.  d_loc[b,p,2] = (dL/dx, dL/dy) in pixels.
+//
+// Contract of the accumulator (tests/test_tps_edges.py predicts d_vol bit for bit from it, tests/tps_ref.py:scatter_emulator):
+//   * a contribution is the fp32 product (g * wx) * wy -- two multiplications, no addition, so nothing can be contracted -- widened
+//     to fp64, scaled by 2^36 (exact) and rounded to the nearest integer, ties to even: each contribution is rounded to a multiple
+//     of 2^-36, an error of at most 2^-37;
+//   * the 64-bit two's-complement sum of those integers is exact, in any order, as long as the true sum of an element stays below
+//     2^63 / 2^36 = 2^27 (1.34e8) in magnitude; a single contribution must stay below 2^27 as well.  Beyond that the sum wraps:
+//     there is no saturation and no check;
+//   * d_vol = (float)((double)sum * 2^-36): one rounding to fp64 (exact below 2^53 counts, i.e. below 2^17 in value) and one to fp32.
 #define TPS_FX_SCALE 68719476736.0      /* 2^36 */
 template <int C>
 __global__ void tps_warp_bwd_kernel(const float* __restrict__ vol, const float* __restrict__ loc, const float* __restrict__ dout,
@@ -263,8 +272,8 @@ long mmseg_tps_scatter_workspace_floats(int B, int H, int W, int C) { return 2L 
 // (needed only when dvol != nullptr; zeroed here)
 int mmseg_tps_warp_bwd(const float* vol, const float* loc, const float* Mb, const float* dout, float* dvol, float* dtheta, float* dloc,
                        float* ws, float* acc, int B, int H, int W, int C, void* stream) {
-    if (C != 8) return (int)hipErrorInvalidValue;
-    if (dvol && (acc == nullptr || ((uintptr_t)acc & 7))) return (int)hipErrorInvalidValue;
+    if (C != 8 || H < 2 || W < 2) return (int)hipErrorInvalidValue;
+    if (dvol &&(acc == nullptr || ((uintptr_t)acc & 7))) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((H * W + 255) / 256, B);
     const long n = (long)B * H * W * C;

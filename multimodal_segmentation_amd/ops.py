@@ -1036,6 +1036,10 @@ class _TpsWarp(torch.autograd.Function):
         vol, theta = _c(vol), _c(theta)
         B, H, W, C = vol.shape
         assert theta.numel() == B * 50 and Mb.shape == (H * W, 25)
+        # the kernels read Mb as raw fp32 rows of 25: anything else would be read as garbage, so refuse it instead of converting
+        if Mb.dtype != torch.float32 or not Mb.is_contiguous() or Mb.device != vol.device:
+            raise ValueError('tps_warp: the basis Mb must be a contiguous float32 tensor on %s (got %s on %s, contiguous=%s)'
+                             % (vol.device, Mb.dtype, Mb.device, Mb.is_contiguous()))
         out = _new(vol.shape, vol)
         loc = _new((B, H * W, 2), vol)
         N.call('mmseg_tps_warp_fwd', vol, theta, Mb, out, loc, B, H, W, C)

@@ -590,6 +590,8 @@ def _tps_loc(theta, Mb, B, H, W):
 
 
 def tps_warp_fwd(vol, theta, Mb, out, loc, B, H, W, C):
+    if C != 8 or H < 2 or W < 2:
+        return 1
     l = _tps_loc(theta, Mb, B, H, W)
     if loc is not None:
         loc.copy_(l.reshape(loc.shape))
@@ -601,16 +603,20 @@ def tps_scatter_workspace_floats(B, H, W, C):
 
 
 def tps_warp_bwd(vol, loc, Mb, dout, dvol, dtheta, dloc, ws, acc, B, H, W, C):
+    if C != 8 or H < 2 or W < 2:
+        return 1
+    # in fp64, rounded once on the way out: the kernel's scatter adds exactly (fixed point), which a sum of fp32 terms does not
     with torch.enable_grad():
-        v = vol.detach().clone().reshape(B, H, W, C).requires_grad_(True)
-        l = loc.detach().clone().reshape(B, H * W, 2).requires_grad_(True)
+        v = vol.detach().double().reshape(B, H, W, C).requires_grad_(True)
+        l = loc.detach().double().reshape(B, H * W, 2).requires_grad_(True)
         o = O.resampler(v, l)
-        gv, gl = torch.autograd.grad(o, [v, l], dout.reshape(o.shape))
+        gv, gl = torch.autograd.grad(o, [v, l], dout.double().reshape(o.shape))
     if dvol is not None:
         dvol.copy_(gv.reshape(dvol.shape))
     if dtheta is not None:
+        dloc.reshape(-1)[:gl.numel()].copy_(gl.reshape(-1))   # like the kernels: d_loc is written only when d_theta is requested
         glr = torch.flip(gl * torch.tensor([W - 1, H - 1], dtype=gl.dtype), dims=[-1])   # -> (row, col) normalised
-        dtheta.copy_(torch.einsum('pj,bpk->bjk', Mb, glr).reshape(dtheta.shape))
+        dtheta.copy_(torch.einsum('pj,bpk->bjk', Mb.double(), glr).reshape(dtheta.shape))
     return 0
 
 
