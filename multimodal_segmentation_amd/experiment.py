@@ -28,6 +28,7 @@ The run folder name and the config mutations follow Experiment.get_config (exper
 pairing else 1, `<folder>/experiment_configuration.json` written before and after training (74-78, 93-97).
 """
 import argparse
+import collections
 import importlib
 import json
 import logging
@@ -154,15 +155,12 @@ def parse_arguments(argv=None):
     args = ap.parse_args(argv)
     if (args.intensity_scope or args.intensity_percentiles) and args.intensity_norm != 'window':
         ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
-    if any(getattr(args, a) is not None for a, _ in BIAS_ARGS) and args.bias_correction != 'n3':
-        ap.error('--bias_sigma_mm, --bias_levels, --bias_iterations and --bias_extent go with --bias_correction n3')
-    if any(getattr(args, a) is not None for a, _ in DENOISE_ARGS) and args.denoise != 'nlm':
-        ap.error('%s go with --denoise nlm' % ', '.join('--' + a for a, _ in DENOISE_ARGS))
-    if any(getattr(args, a) is not None for a, _ in ALIGN_ARGS) and args.align != 'mi':
-        ap.error('%s go with --align mi' % ', '.join('--' + a for a, _ in ALIGN_ARGS))
+    for cli in STAGE_CLI.values():          # `on` is None for intensity: its companions are checked above
+        if cli.on is not None and any(getattr(args, a) is not None for a, _ in cli.companions) and getattr(args, cli.flag) != cli.on:
+            ap.error('%s go with --%s %s' % (cli.listing or ', '.join('--' + a for a, _ in cli.companions), cli.flag, cli.on))
     if args.align:
         try:
-            align_override({}, args)
+            stage_override('align', {}, args)
         except ValueError as e:
             ap.error(str(e))
     if args.denoise_sigma is not None and args.denoise_sigma != 'auto':
@@ -259,175 +257,75 @@ def register_data_folders(module, args):
     return own_name
 
 
-def intensity_override(named, args):
-    """the `intensity` block of `--intensity_norm` / `--intensity_scope` / `--intensity_percentiles`, else the configuration's
-    `intensity`, else None: no override, every folder follows its own dataset.json.  Landmarks are configured in dataset.json only."""
-    from .loaders.volume_folder import check_intensity
-    block, where = named.get('intensity'), 'conf.intensity'
-    if getattr(args, 'intensity_norm', None):
-        block, where = {'mode': args.intensity_norm}, '--intensity_norm'
-        if getattr(args, 'intensity_scope', None):
-            block['scope'] = args.intensity_scope
-        if getattr(args, 'intensity_percentiles', None):
-            block['percentiles'] = list(args.intensity_percentiles)
-    if block is None:
-        return None
-    if isinstance(block, dict) and block.get('mode') == 'landmarks':
-        raise ValueError('%s: landmarks are configured in the dataset.json of a folder (tools/fit_intensity_landmarks.py), not as an '
-                         'override' % where)
-    return check_intensity(dict(block), (), where)
+CliStage = collections.namedtuple('CliStage', 'flag companions subject tail on listing modalities refused drop_none',
+                                  defaults=(None, None, None, (), ()))
+
+# The command-line side of the load-time stages, keyed and ordered like loaders/volume_folder.py's STAGES.  flag: the option that names
+# the mode; companions: (option, key of the block) pairs that go with mode `on` (listing: how the refusal words them, else comma-separated; None
+# for intensity, whose refusal parse_arguments words itself);
+# subject and tail: the two phrases of the predict warning; modalities: what an override is validated against, which knows no folder yet;
+# refused: modes an override may not name, with the reason; drop_none: keys registered only when set, so that the folder decides them.
+STAGE_CLI = collections.OrderedDict((
+    ('intensity', CliStage('intensity_norm', (('intensity_scope', 'scope'), ('intensity_percentiles', 'percentiles')),
+                           '%s is normalised by %s', 'other grey levels', modalities=(),
+                           refused=(('landmarks', 'landmarks are configured in the dataset.json of a folder '
+                                                  '(tools/fit_intensity_landmarks.py), not as an override'),))),
+    ('bias_field', CliStage('bias_correction', (('bias_sigma_mm', 'sigma_mm'), ('bias_levels', 'levels'), ('bias_iterations', 'iterations'),
+                                                ('bias_extent', 'extent')),
+                            'the bias field of %s is set to %s', 'other shading', on='n3',
+                            listing='--bias_sigma_mm, --bias_levels, --bias_iterations and --bias_extent')),
+    ('denoise', CliStage('denoise', (('denoise_sigma', 'sigma'), ('denoise_h', 'h'), ('denoise_search', 'search_radius'),
+                                     ('denoise_patch', 'patch_radius'), ('denoise_search_z', 'search_radius_z'), ('denoise_extent', 'extent'),
+                                     ('denoise_noise', 'noise')),
+                         'the denoising of %s is set to %s', 'other noise', on='nlm')),
+    ('align', CliStage('align', (('align_reference', 'reference'), ('align_max_shift_mm', 'max_shift_mm'), ('align_max_slices', 'max_slices'),
+                                 ('align_bins', 'bins'), ('align_levels', 'levels'), ('align_min_overlap', 'min_overlap')),
+                       'the alignment of %s is set to %s', 'modalities paired otherwise', on='mi', drop_none=('reference',)))))
 
 
-def register_intensity(named, args, names):
-    """Fill loaders.intensity_conf for the data set names of this run; without an override their entries are removed"""
-    from .loaders import intensity_conf
-    block = intensity_override(named, args)
-    for name in names:
-        if block is None:
-            intensity_conf.pop(name, None)
-        else:
-            intensity_conf[name] = dict(block)
-    return block
-
-
-def warn_predict_intensity(conf, folder, log):
-    """a warning when the intensity setting in force for the predict folder differs from the one the run folder records (conf.intensity;
-    a run on the synthetic volumes records none: min / max).  True when it warned."""
-    from .loaders.volume_folder import effective_intensity
-    trained, here = conf.get('intensity') or {'mode': 'minmax'}, effective_intensity(folder)
-    if here == trained:
-        return False
-    log.warning('--predict_folder: %s is normalised by %s, the run folder %s records %s: the model sees other grey levels than it was '
-                'trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
-    return True
-
-
-BIAS_ARGS = (('bias_sigma_mm', 'sigma_mm'), ('bias_levels', 'levels'), ('bias_iterations', 'iterations'), ('bias_extent', 'extent'))
-
-
-def bias_override(named, args):
-    """the `bias_field` block of `--bias_correction` and its four companions, else the configuration's `bias_field`, else None: no
+def stage_override(stage, named, args):
+    """the block of stage `stage` (a key of STAGE_CLI) from its mode option and companions, else the configuration's, else None: no
     override, every folder follows its own dataset.json"""
-    from .loaders.volume_folder import check_bias
-    block, where = named.get('bias_field'), 'conf.bias_field'
-    if getattr(args, 'bias_correction', None):
-        block, where = {'mode': args.bias_correction}, '--bias_correction'
-        for arg, key in BIAS_ARGS:
+    from .loaders.volume_folder import check_stage
+    cli = STAGE_CLI[stage]
+    block, where = named.get(stage), 'conf.%s' % stage
+    if getattr(args, cli.flag, None):
+        block, where = {'mode': getattr(args, cli.flag)}, '--' + cli.flag
+        for arg, key in cli.companions:
             if getattr(args, arg, None) is not None:
                 block[key] = getattr(args, arg)
     if block is None:
         return None
-    return check_bias(dict(block), where)
+    for mode, reason in cli.refused:
+        if isinstance(block, dict) and block.get('mode') == mode:
+            raise ValueError('%s: %s' % (where, reason))
+    return check_stage(stage, dict(block), cli.modalities, where)
 
 
-def register_bias(named, args, names):
-    """Fill loaders.bias_conf for the data set names of this run; without an override their entries are removed"""
-    from .loaders import bias_conf
-    block = bias_override(named, args)
-    for name in names:
-        if block is None:
-            bias_conf.pop(name, None)
-        else:
-            bias_conf[name] = dict(block)
-    return block
+def register_stages(named, args, names):
+    """Fill the registries of loaders.stage_conf for the data set names of this run; without an override their entries are removed"""
+    from .loaders import stage_conf
+    for stage, cli in STAGE_CLI.items():
+        block = stage_override(stage, named, args)
+        for name in names:
+            if block is None:
+                stage_conf[stage].pop(name, None)
+            else:
+                stage_conf[stage][name] = {k: v for k, v in block.items() if not (k in cli.drop_none and v is None)}
 
 
-def warn_predict_bias(conf, folder, log):
-    """a warning when the bias_field setting in force for the predict folder differs from the one the run folder records
-    (conf.bias_field; a run on the synthetic volumes records none: off).  True when it warned."""
-    from .loaders.volume_folder import effective_bias
-    trained, here = conf.get('bias_field') or {'mode': 'off'}, effective_bias(folder)
-    if here == trained:
-        return False
-    log.warning('--predict_folder: the bias field of %s is set to %s, the run folder %s records %s: the model sees other shading than it '
-                'was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
-    return True
-
-
-DENOISE_ARGS = (('denoise_sigma', 'sigma'), ('denoise_h', 'h'), ('denoise_search', 'search_radius'), ('denoise_patch', 'patch_radius'),
-                ('denoise_search_z', 'search_radius_z'), ('denoise_extent', 'extent'), ('denoise_noise', 'noise'))
-
-
-def denoise_override(named, args):
-    """the `denoise` block of `--denoise` and its companions, else the configuration's `denoise`, else None: no override, every folder
-    follows its own dataset.json"""
-    from .loaders.volume_folder import check_denoise
-    block, where = named.get('denoise'), 'conf.denoise'
-    if getattr(args, 'denoise', None):
-        block, where = {'mode': args.denoise}, '--denoise'
-        for arg, key in DENOISE_ARGS:
-            if getattr(args, arg, None) is not None:
-                block[key] = getattr(args, arg)
-    if block is None:
-        return None
-    return check_denoise(dict(block), None, where)
-
-
-def register_denoise(named, args, names):
-    """Fill loaders.denoise_conf for the data set names of this run; without an override their entries are removed"""
-    from .loaders import denoise_conf
-    block = denoise_override(named, args)
-    for name in names:
-        if block is None:
-            denoise_conf.pop(name, None)
-        else:
-            denoise_conf[name] = dict(block)
-    return block
-
-
-def warn_predict_denoise(conf, folder, log):
-    """a warning when the denoise setting in force for the predict folder differs from the one the run folder records (conf.denoise; a
-    run on the synthetic volumes records none: off).  True when it warned."""
-    from .loaders.volume_folder import effective_denoise
-    trained, here = conf.get('denoise') or {'mode': 'off'}, effective_denoise(folder)
-    if here == trained:
-        return False
-    log.warning('--predict_folder: the denoising of %s is set to %s, the run folder %s records %s: the model sees other noise than it '
-                'was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
-    return True
-
-
-ALIGN_ARGS = (('align_reference', 'reference'), ('align_max_shift_mm', 'max_shift_mm'), ('align_max_slices', 'max_slices'),
-              ('align_bins', 'bins'), ('align_levels', 'levels'), ('align_min_overlap', 'min_overlap'))
-
-
-def align_override(named, args):
-    """the `align` block of `--align` and its companions, else the configuration's `align`, else None: no override, every folder follows
-    its own dataset.json"""
-    from .loaders.volume_folder import check_align
-    block, where = named.get('align'), 'conf.align'
-    if getattr(args, 'align', None):
-        block, where = {'mode': args.align}, '--align'
-        for arg, key in ALIGN_ARGS:
-            if getattr(args, arg, None) is not None:
-                block[key] = getattr(args, arg)
-    if block is None:
-        return None
-    return check_align(dict(block), None, where)
-
-
-def register_align(named, args, names):
-    """Fill loaders.align_conf for the data set names of this run; without an override their entries are removed"""
-    from .loaders import align_conf
-    block = align_override(named, args)
-    for name in names:
-        if block is None:
-            align_conf.pop(name, None)
-        else:
-            align_conf[name] = {k: v for k, v in block.items() if not (k == 'reference' and v is None)}
-    return block
-
-
-def warn_predict_align(conf, folder, log):
-    """a warning when the align setting in force for the predict folder differs from the one the run folder records (conf.align; a run on
-    the synthetic volumes records none: off).  True when it warned."""
-    from .loaders.volume_folder import effective_align
-    trained, here = conf.get('align') or {'mode': 'off'}, effective_align(folder)
-    if here == trained:
-        return False
-    log.warning('--predict_folder: the alignment of %s is set to %s, the run folder %s records %s: the model sees modalities paired '
-                'otherwise than it was trained on' % (folder, json.dumps(here, sort_keys=True), conf.folder, json.dumps(trained, sort_keys=True)))
-    return True
+def warn_predict_stages(conf, folder, log):
+    """a warning for every stage whose setting in force for the predict folder differs from the one the run folder records (conf.<key>; a
+    run on the synthetic volumes records none: the stage's `off` block).  The keys of the stages it warned about."""
+    from .loaders.volume_folder import STAGES, effective_setting, read_manifest
+    manifest, warned = read_manifest(folder), []
+    for stage, cli in STAGE_CLI.items():
+        trained, here = conf.get(stage) or dict(STAGES[stage].off), effective_setting(folder, stage, manifest)
+        if here != trained:
+            log.warning('--predict_folder: %s, the run folder %s records %s: the model sees %s than it was trained on'
+                        % (cli.subject % (folder, json.dumps(here, sort_keys=True)), conf.folder, json.dumps(trained, sort_keys=True), cli.tail))
+            warned.append(stage)
+    return warned
 
 
 class Experiment(object):
@@ -446,17 +344,12 @@ class Experiment(object):
         if getattr(args, 'predict_folder', None):
             from .loaders.volume_folder import read_manifest
             names.add(read_manifest(args.predict_folder)['name'])
-        register_intensity(conf, args, sorted(names))      # before a loader that loads volumes is built: it reads its setting then
-        register_bias(conf, args, sorted(names))
-        register_denoise(conf, args, sorted(names))
-        register_align(conf, args, sorted(names))
+        register_stages(conf, args, sorted(names))         # before a loader that loads volumes is built: it reads its settings then
         if data_conf.get(conf.dataset_name):
             conf.data_folder = data_conf[conf.dataset_name]        # recorded in experiment_configuration.json
-            from .loaders.volume_folder import effective_align, effective_bias, effective_denoise, effective_intensity
-            conf.intensity = effective_intensity(conf.data_folder)  # the setting in force, override or dataset.json: recorded too
-            conf.bias_field = effective_bias(conf.data_folder)
-            conf.denoise = effective_denoise(conf.data_folder)
-            conf.align = effective_align(conf.data_folder)
+            from .loaders.volume_folder import effective_setting
+            for stage in STAGE_CLI:                                 # the settings in force, override or dataset.json: recorded too
+                conf[stage] = effective_setting(conf.data_folder, stage)
         conf.split = split
         conf.randomise = _flag(conf, args, 'randomise')
         conf.automatedpairing = _flag(conf, args, 'automatedpairing')
@@ -522,10 +415,7 @@ class Experiment(object):
             raise FileNotFoundError('--predict_folder: the run folder %s holds no checkpoint to predict with (train first, without '
                                     '--test)' % conf.folder)
         if dp.is_main():
-            warn_predict_intensity(conf, args.predict_folder, self.log)
-            warn_predict_bias(conf, args.predict_folder, self.log)
-            warn_predict_denoise(conf, args.predict_folder, self.log)
-            warn_predict_align(conf, args.predict_folder, self.log)
+            warn_predict_stages(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
             model = resolve('models', conf.model)(conf)
             model.build()

@@ -16,8 +16,13 @@ device (csrc/preprocess.hip).  Reading DICOM / PNG stays out of scope: a folder 
 anatomy (what chaos.py:110-240 hard-codes per subject).  After selection all modalities of a volume must hold the same number of
 slices.  S, H, W and the resolution may differ between volumes and between modalities.
 
-Per (volume, modality) the raw slices are uploaded once through pinned memory and three launches write the volume's share of the
-NHWC containers [N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map).
+Per (volume, modality) the raw slices are uploaded once through pinned memory (`_upload`: the one way from a file to device slices,
+for training, validation, testing, prediction, tiles and TTA alike) and three launches write the volume's share of the NHWC containers
+[N,H,W,M] / [N,H,W,M*num_masks]; the host only decides the geometry (resampled size, crop / pad index map).
+
+Four optional keys of dataset.json, the load-time stages, change what is loaded.  STAGES lists them with their registries, modes and
+keys; check_stage validates a block of any of them, and effective_setting gives the one in force for a folder (a registry of
+loaders.stage_conf overrides the key for a run).
 
 `intensity` (optional key of dataset.json; build-defined) chooses how grey values reach [-1, 1].  Absent or {"mode": "minmax"}: every
 slice by the extremes of its resampled frame, the reference's rule and the three launches above.  {"mode": "window", "scope":
@@ -58,6 +63,7 @@ key for a run (experiment.py --align).
 
 For whole-slice prediction (volume_predictor.py `tiles=True`; build-defined) the host also plans the tiles of a
 frame larger than input_shape (tile_axis, tile_weights, tiles_of_other) and `load_volume_tiles` writes them with the same kernels."""
+import collections
 import json
 import logging
 import os
@@ -160,7 +166,6 @@ def has_data(name):
     return bool(name) and bool(data_conf.get(name))
 
 
-INTENSITY_MODES = ('minmax', 'window', 'landmarks')
 INTENSITY_SCOPES = ('volume', 'slice')
 WINDOW_PERCENTILES = (0.5, 99.5)                                        # nnU-Net's clip
 LANDMARK_PERCENTILES = (1, 10, 20, 30, 40, 50, 60, 70, 80, 90, 99)      # Nyul and Udupa's deciles between the 1st and 99th
@@ -172,23 +177,10 @@ def quantile_ranks(n, percentiles):
     return [int(np.floor((int(n) - 1) * (float(q) / 100.0))) for q in percentiles]
 
 
-def check_intensity(block, modalities, where):
-    """The normalised form of an `intensity` block (dataset.json, conf.intensity): {'mode': 'minmax'}, or mode, scope and percentiles
-    for 'window', and additionally `standard` {modality: [y_0 .. y_{K-1}]} for 'landmarks'.  None and {} mean 'minmax'."""
-    if block is None:
-        return {'mode': 'minmax'}
-    if not isinstance(block, dict):
-        raise ValueError('%s: "intensity" must be an object, got %r' % (where, block))
-    mode = block.get('mode', 'minmax')
-    if mode not in INTENSITY_MODES:
-        raise ValueError('%s: "intensity" mode must be one of %s, got %r' % (where, ', '.join(INTENSITY_MODES), mode))
-    unknown = sorted(set(block) - {'mode', 'scope', 'percentiles', 'standard'})
-    if unknown:
-        raise ValueError('%s: "intensity" has unknown key(s) %s' % (where, ', '.join(unknown)))
-    if mode == 'minmax':
-        if set(block) - {'mode'}:
-            raise ValueError('%s: "intensity" mode minmax takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
-        return {'mode': 'minmax'}
+def _intensity_block(block, modalities, where):
+    """an `intensity` block of mode 'window' or 'landmarks': mode, scope and percentiles, and for 'landmarks' additionally `standard`
+    {modality: [y_0 .. y_{K-1}]}"""
+    mode = block['mode']
     scope = block.get('scope', 'volume')
     if scope not in INTENSITY_SCOPES:
         raise ValueError('%s: "intensity" scope must be one of %s, got %r' % (where, ', '.join(INTENSITY_SCOPES), scope))
@@ -228,40 +220,9 @@ def check_intensity(block, modalities, where):
     return out
 
 
-def effective_intensity(root, manifest=None):
-    """the normalised intensity setting of the folder `root`: the override registered in loaders.intensity_conf under a data set name
-    that loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
-    from . import data_conf, intensity_conf
-    m = read_manifest(root) if manifest is None else manifest
-    here = os.path.abspath(root)
-    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
-    for n in names:
-        if intensity_conf.get(n) is not None:
-            return check_intensity(intensity_conf[n], m['modalities'], 'loaders.intensity_conf[%r]' % n)
-    return check_intensity(m.get('intensity'), m['modalities'], os.path.join(root, MANIFEST))
-
-
-BIAS_MODES = ('off', 'n3')
-
-
-def check_bias(block, where):
-    """The normalised form of a `bias_field` block (dataset.json, conf.bias_field): {'mode': 'off'}, or {'mode': 'n3', 'sigma_mm',
-    'levels', 'iterations', 'extent'} with ops.BIAS_DEFAULTS filled in -- except `extent`, which stays None when the block names none:
-    the loader takes '3d' where the files hold a slice_spacing, else '2d'.  None and {} mean 'off'."""
-    if block is None:
-        return {'mode': 'off'}
-    if not isinstance(block, dict):
-        raise ValueError('%s: "bias_field" must be an object, got %r' % (where, block))
-    mode = block.get('mode', 'off')
-    if mode not in BIAS_MODES:
-        raise ValueError('%s: "bias_field" mode must be one of %s, got %r' % (where, ', '.join(BIAS_MODES), mode))
-    unknown = sorted(set(block) - {'mode', 'sigma_mm', 'levels', 'iterations', 'extent'})
-    if unknown:
-        raise ValueError('%s: "bias_field" has unknown key(s) %s' % (where, ', '.join(unknown)))
-    if mode == 'off':
-        if set(block) - {'mode'}:
-            raise ValueError('%s: "bias_field" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
-        return {'mode': 'off'}
+def _bias_block(block, modalities, where):
+    """a `bias_field` block of mode 'n3': 'sigma_mm', 'levels', 'iterations' and 'extent' with ops.BIAS_DEFAULTS filled in -- except
+    `extent`, which stays None when the block names none: the loader takes '3d' where the files hold a slice_spacing, else '2d'"""
     given = {k: v for k, v in block.items() if k != 'mode' and not (k == 'extent' and v is None)}
     p = ops.bias_params(given, '%s: "bias_field"' % where)
     if 'extent' not in given:
@@ -269,41 +230,10 @@ def check_bias(block, where):
     return dict(mode='n3', **p)
 
 
-def effective_bias(root, manifest=None):
-    """the normalised bias_field setting of the folder `root`: the override registered in loaders.bias_conf under a data set name that
-    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
-    from . import bias_conf, data_conf
-    m = read_manifest(root) if manifest is None else manifest
-    here = os.path.abspath(root)
-    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
-    for n in names:
-        if bias_conf.get(n) is not None:
-            return check_bias(bias_conf[n], 'loaders.bias_conf[%r]' % n)
-    return check_bias(m.get('bias_field'), os.path.join(root, MANIFEST))
-
-
-DENOISE_MODES = ('off', 'nlm')
-
-
-def check_denoise(block, modalities, where):
-    """The normalised form of a `denoise` block (dataset.json, conf.denoise): {'mode': 'off'}, or {'mode': 'nlm', 'sigma', 'h',
-    'search_radius', 'patch_radius', 'search_radius_z', 'extent', 'noise'} with ops.NLM_DEFAULTS filled in.  `sigma` is 'auto', a number
-    or {modality: number}; a mapping must name every modality of `modalities` (None: the folder is not known yet, as for a command-line
-    override).  None and {} mean 'off'."""
-    if block is None:
-        return {'mode': 'off'}
-    if not isinstance(block, dict):
-        raise ValueError('%s: "denoise" must be an object, got %r' % (where, block))
-    mode = block.get('mode', 'off')
-    if mode not in DENOISE_MODES:
-        raise ValueError('%s: "denoise" mode must be one of %s, got %r' % (where, ', '.join(DENOISE_MODES), mode))
-    unknown = sorted(set(block) - {'mode'} - set(ops.NLM_DEFAULTS))
-    if unknown:
-        raise ValueError('%s: "denoise" has unknown key(s) %s' % (where, ', '.join(unknown)))
-    if mode == 'off':
-        if set(block) - {'mode'}:
-            raise ValueError('%s: "denoise" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
-        return {'mode': 'off'}
+def _denoise_block(block, modalities, where):
+    """a `denoise` block of mode 'nlm': 'sigma', 'h', 'search_radius', 'patch_radius', 'search_radius_z', 'extent' and 'noise' with
+    ops.NLM_DEFAULTS filled in.  `sigma` is 'auto', a number or {modality: number}; a mapping must name every modality of `modalities`
+    (None: the folder is not known yet, as for a command-line override)."""
     given = {k: v for k, v in block.items() if k != 'mode' and not (k == 'search_radius_z' and v is None)}
     per_modality = given.get('sigma') if isinstance(given.get('sigma'), dict) else None
     if per_modality is not None:
@@ -327,40 +257,10 @@ def check_denoise(block, modalities, where):
     return dict(mode='nlm', **p)
 
 
-def effective_denoise(root, manifest=None):
-    """the normalised denoise setting of the folder `root`: the override registered in loaders.denoise_conf under a data set name that
-    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
-    from . import data_conf, denoise_conf
-    m = read_manifest(root) if manifest is None else manifest
-    here = os.path.abspath(root)
-    names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
-    for n in names:
-        if denoise_conf.get(n) is not None:
-            return check_denoise(denoise_conf[n], m['modalities'], 'loaders.denoise_conf[%r]' % n)
-    return check_denoise(m.get('denoise'), m['modalities'], os.path.join(root, MANIFEST))
-
-
-ALIGN_MODES = ('off', 'mi')
-
-
-def check_align(block, modalities, where):
-    """The normalised form of an `align` block (dataset.json, conf.align): {'mode': 'off'}, or {'mode': 'mi', 'reference', 'max_shift_mm',
-    'max_slices', 'bins', 'levels', 'min_overlap', 'percentiles'} with ops.ALIGN_DEFAULTS filled in.  `reference` is a modality's name;
-    None stands for the folder's first (a command-line override may not know the folder yet: modalities = None).  None and {} mean 'off'."""
-    if block is None:
-        return {'mode': 'off'}
-    if not isinstance(block, dict):
-        raise ValueError('%s: "align" must be an object, got %r' % (where, block))
-    mode = block.get('mode', 'off')
-    if mode not in ALIGN_MODES:
-        raise ValueError('%s: "align" mode must be one of %s, got %r' % (where, ', '.join(ALIGN_MODES), mode))
-    unknown = sorted(set(block) - {'mode', 'reference'} - set(ops.ALIGN_DEFAULTS))
-    if unknown:
-        raise ValueError('%s: "align" has unknown key(s) %s' % (where, ', '.join(unknown)))
-    if mode == 'off':
-        if set(block) - {'mode'}:
-            raise ValueError('%s: "align" mode off takes no other key, got %s' % (where, ', '.join(sorted(set(block) - {'mode'}))))
-        return {'mode': 'off'}
+def _align_block(block, modalities, where):
+    """an `align` block of mode 'mi': 'reference', 'max_shift_mm', 'max_slices', 'bins', 'levels', 'min_overlap' and 'percentiles' with
+    ops.ALIGN_DEFAULTS filled in.  `reference` is a modality's name; None stands for the folder's first (a command-line override may
+    not know the folder yet: modalities = None)."""
     reference = block.get('reference')
     if reference is not None and (not isinstance(reference, str) or (modalities is not None and reference not in modalities)):
         raise ValueError('%s: "align" reference must be one of the modalities%s, got %r'
@@ -371,17 +271,69 @@ def check_align(block, modalities, where):
     return dict(mode='mi', reference=reference, **p)
 
 
-def effective_align(root, manifest=None):
-    """the normalised align setting of the folder `root`: the override registered in loaders.align_conf under a data set name that
-    loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
-    from . import align_conf, data_conf
+Stage = collections.namedtuple('Stage', 'key registry off modes keys validate')
+
+# The load-time stages, in the order experiment.py registers and records them.  key: the key of dataset.json, of the configuration and of
+# the loader's attribute; registry: the override's name in loaders (loaders.stage_conf[key] is the dict); off: the block that None and {}
+# stand for (the first of `modes`), which takes no other key; keys: what a block may hold beside `mode`; validate(block, modalities,
+# where): the normalised form of a block of any other mode.
+STAGES = collections.OrderedDict((stage.key, stage) for stage in (
+    Stage('intensity', 'intensity_conf', {'mode': 'minmax'}, ('minmax', 'window', 'landmarks'), ('scope', 'percentiles', 'standard'),
+          _intensity_block),
+    Stage('bias_field', 'bias_conf', {'mode': 'off'}, ('off', 'n3'), ('sigma_mm', 'levels', 'iterations', 'extent'), _bias_block),
+    Stage('denoise', 'denoise_conf', {'mode': 'off'}, ('off', 'nlm'), tuple(ops.NLM_DEFAULTS), _denoise_block),
+    Stage('align', 'align_conf', {'mode': 'off'}, ('off', 'mi'), ('reference',) + tuple(ops.ALIGN_DEFAULTS), _align_block)))
+
+
+def check_stage(key, block, modalities, where):
+    """The normalised form of the block of stage `key` (dataset.json, conf.<key>, loaders.stage_conf[key]): the stage's `off` block, or
+    what its validator makes of a block of another mode, defaults filled in.  None and {} mean off."""
+    stage = STAGES[key]
+    off = stage.off['mode']
+    if block is None:
+        return dict(stage.off)
+    if not isinstance(block, dict):
+        raise ValueError('%s: "%s" must be an object, got %r' % (where, key, block))
+    mode = block.get('mode', off)
+    if mode not in stage.modes:
+        raise ValueError('%s: "%s" mode must be one of %s, got %r' % (where, key, ', '.join(stage.modes), mode))
+    unknown = sorted(set(block) - {'mode'} - set(stage.keys))
+    if unknown:
+        raise ValueError('%s: "%s" has unknown key(s) %s' % (where, key, ', '.join(unknown)))
+    if mode == off:
+        if set(block) - {'mode'}:
+            raise ValueError('%s: "%s" mode %s takes no other key, got %s' % (where, key, off, ', '.join(sorted(set(block) - {'mode'}))))
+        return dict(stage.off)
+    return stage.validate(block, modalities, where)
+
+
+def check_intensity(block, modalities, where):
+    return check_stage('intensity', block, modalities, where)
+
+
+def check_bias(block, where):
+    return check_stage('bias_field', block, None, where)
+
+
+def check_denoise(block, modalities, where):
+    return check_stage('denoise', block, modalities, where)
+
+
+def check_align(block, modalities, where):
+    return check_stage('align', block, modalities, where)
+
+
+def effective_setting(root, key, manifest=None):
+    """the normalised setting of stage `key` for the folder `root`: the override registered in the stage's registry under a data set
+    name that loaders.data_conf maps to this folder, or under the folder's own `name`; else its dataset.json's"""
+    from . import data_conf, stage_conf
     m = read_manifest(root) if manifest is None else manifest
     here = os.path.abspath(root)
     names = [n for n, f in data_conf.items() if f and os.path.abspath(f) == here] + [m['name']]
     for n in names:
-        if align_conf.get(n) is not None:
-            return check_align(align_conf[n], m['modalities'], 'loaders.align_conf[%r]' % n)
-    return check_align(m.get('align'), m['modalities'], os.path.join(root, MANIFEST))
+        if stage_conf[key].get(n) is not None:
+            return check_stage(key, stage_conf[key][n], m['modalities'], 'loaders.%s[%r]' % (STAGES[key].registry, n))
+    return check_stage(key, m.get(key), m['modalities'], os.path.join(root, MANIFEST))
 
 
 def read_manifest(root):
@@ -414,10 +366,8 @@ def read_manifest(root):
         for mod in m['modalities']:
             if mod not in entry or 'file' not in entry[mod]:
                 raise ValueError('%s: volume %s has no file for modality %r' % (path, v, mod))
-    check_intensity(m.get('intensity'), m['modalities'], path)
-    check_bias(m.get('bias_field'), path)
-    check_denoise(m.get('denoise'), m['modalities'], path)
-    check_align(m.get('align'), m['modalities'], path)
+    for key in STAGES:
+        check_stage(key, m.get(key), m['modalities'], path)
     return m
 
 
@@ -435,10 +385,8 @@ class VolumeFolderLoader(object):
         self.num_volumes = len(self.volumes)
         self.processed_folder = None
         self.log = log
-        self.intensity = effective_intensity(root, m)          # build-defined: {'mode': 'minmax'} is the reference's rescale
-        self.bias_field = effective_bias(root, m)              # build-defined: {'mode': 'off'} uploads the slices as they are
-        self.denoise = effective_denoise(root, m)              # build-defined: {'mode': 'off'} launches nothing
-        self.align = effective_align(root, m)                  # build-defined: {'mode': 'off'} launches nothing
+        for key in STAGES:          # build-defined: self.intensity, .bias_field, .denoise, .align; a stage's `off` block is the reference's loading
+            setattr(self, key, effective_setting(root, key, m))
         self._alignments = {}                                  # volume -> alignment()'s result
 
     # ---- splits (base_loader.py:27-32,80-89) --------------------------------------------------------------------------------
@@ -537,7 +485,7 @@ class VolumeFolderLoader(object):
     def bias_corrected(self, x, res, spacing=None, selected=None, what='volume'):
         """The raw slices x [S,H,W] of one (volume, modality) on the device, as the rest of the loader shall see them: x itself when
         bias_field is off, else a corrected copy (ops.bias_correct; the selected slices only).  The one place where this is decided:
-        preprocess, load_volume_for_prediction and upload_volume call it once per upload, before intensity_knots."""
+        `_upload` calls it once per (volume, modality), before intensity_knots."""
         setting = self.bias_field
         if setting['mode'] == 'off' or x.shape[0] == 0:
             return x
@@ -547,8 +495,8 @@ class VolumeFolderLoader(object):
 
     def denoised(self, x, modality, selected=None, what='volume'):
         """The raw slices x [S,H,W] of one (volume, modality) on the device after the folder's `denoise` setting: x itself when it is off
-        (nothing is launched), else a denoised copy (ops.nlm_denoise).  The one place where this is decided: preprocess,
-        load_volume_for_prediction and upload_volume call it once per upload, immediately before bias_corrected.  Extent 3d searches
+        (nothing is launched), else a denoised copy (ops.nlm_denoise).  The one place where this is decided: `_upload` calls
+        it once per (volume, modality), immediately before bias_corrected.  Extent 3d searches
         the neighbouring slices too and therefore needs one contiguous run of slices (no slice_spacing: the rule has no mm in it)."""
         setting = self.denoise
         if setting['mode'] == 'off' or x.shape[0] == 0:
@@ -570,8 +518,8 @@ class VolumeFolderLoader(object):
         a moving one the same run moved by its dz.  rows / cols: the (lo, kept, before) windows -- crop_pad_map's, bit for bit, for the
         reference and on every axis without a shift; tile_window(centre_start(R, O) + d, R, O) on an axis shifted by d (a plain window:
         where crop_pad_map removes ceil(surplus / 2) pixels from BOTH ends of an odd surplus and repeats the last pixel, the shifted
-        window keeps all O).  The one place where this is decided: preprocess, load_volume_for_prediction and upload_volume call it once
-        per uploaded volume, after bias_corrected and before intensity_knots; the result is cached per volume (None: not cached)."""
+        window keeps all O).  The one place where this is decided: `_upload` calls it once per volume, after bias_corrected and before
+        intensity_knots; the result is cached per volume (None: not cached)."""
         setting = self.align
         if setting['mode'] == 'off':
             return None
@@ -704,73 +652,27 @@ class VolumeFolderLoader(object):
 
     # ---- the reference's loading surface --------------------------------------------------------------------------------------
     def load_all_modalities_concatenated(self, split, split_type, downsample=1):
-        volumes = self.get_volumes_for_split(split, split_type)
-        raw, index, extras = [], [], []
-        for v in volumes:
-            per_mod, extra = [], []
-            for mod in self.modalities:
-                image, label, res, selected, spacing = self._read_file(v, mod, True)
-                per_mod.append((image, label, res) if selected is None else (image[selected], label[selected], res))
-                extra.append((spacing, selected, 'volume %s, modality %s' % (v, mod)))
-            extras.append(extra)
-            counts = [p[0].shape[0] for p in per_mod]
-            if self.align['mode'] != 'off':          # the kept run decides the count; unequal counts are what alignment is for
-                keep = (self._alignments.get(v) or self._aligned(v, per_mod, extra)[1])[0]['keep']
-                counts = [keep[1] - keep[0]]
-            elif len(set(counts)) != 1:
-                raise ValueError('volume %s: the modalities hold different numbers of slices after selection (%s); state the '
-                                 'matching ranges under "slices" in %s'
-                                 % (v, ', '.join('%s: %d' % mc for mc in zip(self.modalities, counts)), MANIFEST))
-            raw.append(per_mod)
-            index.append(np.array([v] * counts[0]))
-        index = np.concatenate(index, axis=0) if index else np.zeros((0,), np.int64)
-        images, masks = self.preprocess(raw, len(index), extras, volumes)
-        return MultimodalPairedData(images, masks, index, downsample=downsample, num_modalities=len(self.modalities))
-
-    def _aligned(self, volume, per_mod, extra):
-        """(xs, alignment, geometries): the modalities of one volume of preprocess's `raw` on the device after denoised and
-        bias_corrected, alignment()'s result for them (None when `align` is off) and their (resolution, resampled) records"""
-        device = nn.default_device()
-        xs, geos = [], []
-        for mod, (image, label, res) in enumerate(per_mod):
-            H, W = image.shape[1:]
-            RH = resampled_size(H, res[0], self.target_resolution[0])
-            RW = resampled_size(W, res[1], self.target_resolution[1])
-            if RH < 1 or RW < 1:
-                raise ValueError('a %d x %d slice at %s mm resamples to nothing at %s mm' % (H, W, res, self.target_resolution))
-            spacing, selected, what = extra[mod] if extra is not None else (None, None, 'modality %s' % self.modalities[mod])
-            x = self.denoised(nn.host_to_device(image, device, np.float32), self.modalities[mod], selected, what)
-            xs.append(self.bias_corrected(x, res, spacing, selected, what))
-            geos.append(dict(resolution=res, resampled=(RH, RW)))
-        return xs, self.alignment(volume, xs, geos), geos
-
-    def preprocess(self, raw, n, extras=None, volumes=None):
-        """raw: per volume, per modality (image, label, resolution) -> host arrays images [n,H,W,M], masks [n,H,W,M*num_masks].
-        extras: per volume, per modality (slice_spacing or None, the selected file indices or None, a name for messages): what
-        denoised and bias_corrected need beyond the resolution; without it the slices count as one run of a file without slice_spacing.
-        volumes: per volume its id, the key under which `alignment` caches (None: nothing is cached).  Under `align` a volume
-        contributes its kept run of slices, and n counts those."""
+        """every volume of the split through `_upload`, as prediction loads it; their counts of slices (under `align` the kept runs) size
+        one pair of device containers [n,OH,OW,M] / [n,OH,OW,M*num_masks], each volume's share of which ops.preprocess_volume writes per
+        modality.  One copy brings them to the host: a copy per volume and a concatenation there measured a tenth slower."""
         device = nn.default_device()
         OH, OW = self.input_shape[:2]
         M, K = len(self.modalities), self.num_masks
-        images = torch.zeros((n, OH, OW, M), dtype=torch.float32, device=device)
-        masks = torch.zeros((n, OH, OW, M * K), dtype=torch.float32, device=device)
+        volumes = self.get_volumes_for_split(split, split_type)
+        uploaded = [self._upload(v, True) for v in volumes]
+        counts = [xs[0].shape[0] for xs, _ in uploaded]
+        images = torch.zeros((sum(counts), OH, OW, M), dtype=torch.float32, device=device)
+        masks = torch.zeros((sum(counts), OH, OW, M * K), dtype=torch.float32, device=device)
         values = nn.host_to_device(np.asarray(self.label_values), device, np.int32)
         n0 = 0
-        for vol, per_mod in enumerate(raw):
-            xs, aligned, geos = self._aligned(None if volumes is None else volumes[vol], per_mod, None if extras is None else extras[vol])
-            S = per_mod[0][0].shape[0] if aligned is None else aligned[0]['keep'][1] - aligned[0]['keep'][0]
-            for mod, (image, label, res) in enumerate(per_mod):
-                RH, RW = geos[mod]['resampled']
-                x, rows, cols = xs[mod], crop_pad_map(RH, OH), crop_pad_map(RW, OW)
-                if aligned is not None:
-                    k0, k1 = aligned[mod]['keep']
-                    x, label, rows, cols = x[k0:k1], label[k0:k1], aligned[mod]['rows'], aligned[mod]['cols']
-                ops.preprocess_volume(x, nn.host_to_device(label, device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
-                                      (RH, RW), rows, cols, mod, knots=self.intensity_knots(x, (RH, RW), self.modalities[mod]))
+        for (xs, geometry), S in zip(uploaded, counts):
+            for m, (mod, x, g) in enumerate(zip(self.modalities, xs, geometry)):
+                ops.preprocess_volume(x, nn.host_to_device(g['label'], device, np.uint8), values, images[n0:n0 + S], masks[n0:n0 + S],
+                                      g['resampled'], g['rows'], g['cols'], m, knots=self.intensity_knots(x, g['resampled'], mod))
             n0 += S
-        assert n0 == n
-        return nn.to_numpy(images), nn.to_numpy(masks)
+        index = np.concatenate([np.array([v] * S) for v, S in zip(volumes, counts)], axis=0) if volumes else np.zeros((0,), np.int64)
+        return MultimodalPairedData(nn.to_numpy(images), nn.to_numpy(masks), index, downsample=downsample,
+                                    num_modalities=len(self.modalities))
 
     def load_labelled_data(self, split, split_type, modality, normalise=True, downsample=1, root_folder=None):
         """one modality by name, or 'all': the modalities stacked along the slice axis (chaos.py:57-99)"""

@@ -482,6 +482,33 @@ def test_without_the_key_nothing_changes(device, folders, tmp_path, monkeypatch)
         assert 'the modalities hold different numbers of slices after selection' in str(e.value) and 'state the matching' in str(e.value)
 
 
+def test_training_load_launches_what_prediction_launches(device, tmp_path):
+    """with denoise, bias_field and align on, a training load denoises and bias-corrects every (volume, modality) once, as prediction
+    does: the same mmseg_nlm_* and mmseg_bias_* entry points, each as often"""
+    from multimodal_segmentation_amd import _native
+    folder = str(tmp_path / 'staged')
+    R.tool().write_folder(folder, volumes=3, size=32, slices=3, seed=1)
+    _set_block(folder, {'mode': 'nlm'}, 'denoise')
+    _set_block(folder, {'mode': 'n3', 'extent': '2d', 'levels': 1, 'iterations': 1}, 'bias_field')
+    _set_block(folder, {'mode': 'mi'})
+
+    def recorded(load):
+        loader, called = VF.VolumeFolderLoader(folder), []
+        real_call = _native.call
+        _native.call = lambda name, *a: (called.append(name), real_call(name, *a))[1]
+        try:
+            load(loader)
+        finally:
+            _native.call = real_call
+        return sorted(n for n in called if n.startswith(('mmseg_nlm_', 'mmseg_bias_')))
+
+    training = recorded(lambda loader: loader.load_all_modalities_concatenated(0, 'all', 1))
+    prediction = recorded(lambda loader: [loader.load_volume_for_prediction(v) for v in loader.get_volumes_for_split(0, 'all')])
+    print('training', len(training), 'prediction', len(prediction))
+    assert [n for n in prediction if n.startswith('mmseg_nlm_')] and [n for n in prediction if n.startswith('mmseg_bias_')]
+    assert training == prediction
+
+
 def test_labels_return_to_the_file_grid(device, folders):
     """load_volume_for_prediction's record is all the way back needs: label containers written with its windows and pushed through
     mmseg_restore_label reproduce the file's own label on the file grid, inside the window"""
@@ -578,9 +605,9 @@ def test_settings_are_validated_with_the_key_named(folders, tmp_path):
     json.dump(json.load(open(os.path.join(mis, 'dataset.json'))), open(os.path.join(copy, 'dataset.json'), 'w'))
     full = dict(mode='mi', reference='t1', max_shift_mm=40.0, max_slices=4, bins=32, levels=3, min_overlap=0.5, percentiles=[0.5, 99.5])
     _set_block(copy, {'mode': 'mi'})
-    assert VF.effective_align(copy) == full
+    assert VF.effective_setting(copy, 'align') == full
     _set_block(copy, {'mode': 'mi', 'reference': 't2', 'bins': 64})
-    assert VF.effective_align(copy) == dict(full, reference='t2', bins=64)
+    assert VF.effective_setting(copy, 'align') == dict(full, reference='t2', bins=64)
     for block, word in (({'mode': 'ncc'}, 'mode'), ({'mode': 'mi', 'reference': 'ct'}, 'reference'), ({'mode': 'mi', 'bins': 65}, 'bins'),
                         ({'mode': 'mi', 'bins': 1}, 'bins'), ({'mode': 'mi', 'levels': 0}, 'levels'), ({'mode': 'mi', 'max_slices': -1}, 'max_slices'),
                         ({'mode': 'mi', 'max_shift_mm': -1}, 'max_shift_mm'), ({'mode': 'mi', 'min_overlap': 0}, 'min_overlap'),

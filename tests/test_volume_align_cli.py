@@ -69,7 +69,7 @@ def test_bad_values_are_refused_with_their_names(folder, tmp_path, monkeypatch, 
 
 
 def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, caplog):
-    from multimodal_segmentation_amd.experiment import warn_predict_align
+    from multimodal_segmentation_amd.experiment import warn_predict_stages
     from multimodal_segmentation_amd.utils.config import EasyDict
     other = str(tmp_path / 'scans')
     R.tool().write_folder(other, volumes=3, size=64, slices=2, seed=5, name='site_b', unlabelled=True, misalign=4)
@@ -77,14 +77,14 @@ def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, ca
     own = json.load(open(os.path.join(other, 'dataset.json')))['align']
     trained = dict(FULL, **{k: v for k, v in own.items() if k != 'mode'})
     with caplog.at_level(logging.WARNING):
-        assert not warn_predict_align(EasyDict(folder='run', align=trained), other, log)          # the same setting: silence
-        assert not warn_predict_align(EasyDict(folder='run'), folder, log)                        # neither records nor asks for anything
+        assert not warn_predict_stages(EasyDict(folder='run', align=trained), other, log)          # the same setting: silence
+        assert not warn_predict_stages(EasyDict(folder='run'), folder, log)                        # neither records nor asks for anything
     assert caplog.text == ''
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_align(EasyDict(folder='run'), other, log)                             # trained unaligned, predicts aligned
+        assert warn_predict_stages(EasyDict(folder='run'), other, log) == ['align']                # trained unaligned, predicts aligned
     assert '"off"' in caplog.text and '"mi"' in caplog.text and other in caplog.text and 'alignment' in caplog.text
     caplog.clear()
     loaders.align_conf['site_b'] = {'mode': 'off'}                                                # the override counts
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_align(EasyDict(folder='run', align=trained), other, log)
-        assert not warn_predict_align(EasyDict(folder='run'), other, log)
+        assert warn_predict_stages(EasyDict(folder='run', align=trained), other, log) == ['align']
+        assert not warn_predict_stages(EasyDict(folder='run'), other, log)

@@ -435,7 +435,7 @@ def test_cli_override_reaches_the_loader_and_the_recorded_configuration(folder, 
 
 def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, caplog):
     from multimodal_segmentation_amd.utils.config import EasyDict
-    from multimodal_segmentation_amd.experiment import warn_predict_bias
+    from multimodal_segmentation_amd.experiment import warn_predict_stages
     other = str(tmp_path / 'scans')
     R.tool().write_folder(other, volumes=3, size=64, slices=2, seed=5, name='site_b', unlabelled=True)
     plain = str(tmp_path / 'plain')
@@ -443,17 +443,17 @@ def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, ca
     log = logging.getLogger('test_volume_bias')
     conf = EasyDict(folder='run', bias_field=dict(mode='n3', sigma_mm=40.0, levels=3, iterations=20, extent=None))
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_bias(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['bias_field']
     assert '"off"' in caplog.text and '"n3"' in caplog.text and other in caplog.text
     caplog.clear()
     _set_block(other, {'mode': 'n3'})
     with caplog.at_level(logging.WARNING):
-        assert not warn_predict_bias(conf, other, log)
-        assert not warn_predict_bias(EasyDict(folder='run'), plain, log)          # neither records nor asks for anything
+        assert not warn_predict_stages(conf, other, log)
+        assert not warn_predict_stages(EasyDict(folder='run'), plain, log)          # neither records nor asks for anything
     assert caplog.text == ''
     loaders.bias_conf['site_b'] = {'mode': 'off'}                    # the override counts
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_bias(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['bias_field']
 
 
 def _minmax_frames(image, RH, RW):

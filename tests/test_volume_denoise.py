@@ -402,7 +402,7 @@ def test_cli_override_reaches_the_loader_and_the_recorded_configuration(folder, 
 
 def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, caplog):
     from multimodal_segmentation_amd.utils.config import EasyDict
-    from multimodal_segmentation_amd.experiment import warn_predict_denoise
+    from multimodal_segmentation_amd.experiment import warn_predict_stages
     other = str(tmp_path / 'scans')
     R.tool().write_folder(other, volumes=3, size=64, slices=2, seed=5, name='site_b', unlabelled=True)
     plain = str(tmp_path / 'plain')
@@ -411,17 +411,17 @@ def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, ca
     trained = dict(mode='nlm', search_radius=5, patch_radius=1, search_radius_z=0, h=1.0, noise='rician', sigma='auto', extent='2d')
     conf = EasyDict(folder='run', denoise=trained)
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_denoise(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['denoise']
     assert '"off"' in caplog.text and '"nlm"' in caplog.text and other in caplog.text
     caplog.clear()
     _set_block(other, {'mode': 'nlm'})
     with caplog.at_level(logging.WARNING):
-        assert not warn_predict_denoise(conf, other, log)
-        assert not warn_predict_denoise(EasyDict(folder='run'), plain, log)          # neither records nor asks for anything
+        assert not warn_predict_stages(conf, other, log)
+        assert not warn_predict_stages(EasyDict(folder='run'), plain, log)          # neither records nor asks for anything
     assert caplog.text == ''
     loaders.denoise_conf['site_b'] = {'mode': 'off'}                 # the override counts
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_denoise(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['denoise']
 
 
 def test_loader_denoises_before_it_corrects_the_bias(device, folder):

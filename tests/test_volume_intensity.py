@@ -613,23 +613,23 @@ def test_override_applies_to_the_loaded_arrays(standin, folder, tmp_path, monkey
 
 def test_predict_folder_with_another_setting_logs_a_warning(folder, tmp_path, caplog):
     from multimodal_segmentation_amd.utils.config import EasyDict
-    from multimodal_segmentation_amd.experiment import warn_predict_intensity
+    from multimodal_segmentation_amd.experiment import warn_predict_stages
     other = str(tmp_path / 'scans')
     R.tool().write_folder(other, volumes=3, size=64, slices=2, seed=5, name='site_b', unlabelled=True)
     log = logging.getLogger('test_volume_intensity')
     conf = EasyDict(folder='run', intensity={'mode': 'window', 'scope': 'volume', 'percentiles': [0.5, 99.5]})
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_intensity(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['intensity']
     assert 'minmax' in caplog.text and 'window' in caplog.text and other in caplog.text
     caplog.clear()
     _set_intensity(other, {'mode': 'window'})
     with caplog.at_level(logging.WARNING):
-        assert not warn_predict_intensity(conf, other, log)
-        assert not warn_predict_intensity(EasyDict(folder='run'), folder, log)          # neither records nor asks for anything
+        assert not warn_predict_stages(conf, other, log)
+        assert not warn_predict_stages(EasyDict(folder='run'), folder, log)          # neither records nor asks for anything
     assert caplog.text == ''
     loaders.intensity_conf['site_b'] = {'mode': 'minmax'}                                # the override counts
     with caplog.at_level(logging.WARNING):
-        assert warn_predict_intensity(conf, other, log)
+        assert warn_predict_stages(conf, other, log) == ['intensity']
 
 
 # ---- the example folder -----------------------------------------------------------------------------------------------------------------
