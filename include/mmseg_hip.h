@@ -784,6 +784,47 @@ int mmseg_blend_tiles(const float* prob, const int* rows, const int* cols, const
  * synchronisation, allocation or copy. */
 int mmseg_merge_views(const float* prob, const double* back, float* out, int V, int N, int OH, int OW, int C, int K, void* stream);
 
+/* ---- several models and views, their mean, its uncertainty and its calibration (csrc/postprocess.hip; build-defined, the rule is in
+ * INTEGRATION.md section 5).  Common to the five entry points: a bad argument or a null pointer is refused (hipErrorInvalidValue, nothing is
+ * launched); no host synchronisation, allocation or copy; two runs are bitwise equal; no kernel waits for another block; N == 0, S == 0
+ * or n == 0 does nothing.
+ * mmseg_members_accumulate: prob [V*N,OH,OW,C] fp32, the output of ONE model for V views of N slices, view-major, the K organ channels
+ * first; back [V,6] fp64 on the device as for mmseg_merge_views (a plain model: V = 1 and the identity 1 0 0 0 1 0).  sum [N,OH,OW,K] and
+ * aux [N,OH,OW,2] = (sum of h, cnt) fp32 are the accumulators: with first != 0 they count as 0 and are never read, otherwise the call
+ * continues from them, so that several models stream through one pair of buffers.  Per pixel and covering view, in ascending v, with the
+ * coverage test and the sample q_k of mmseg_merge_views: sum_k += q_k; rest = max(0, 1 - (((q_0 + q_1) + ..) + q_(K-1)));
+ * h = t(q_0) + .. + t(q_(K-1)) + t(rest) added from 0 in that order, t(x) = x > 0 ? -x * logf(x) : 0; aux_0 += h; aux_1 += 1.  fp32
+ * without contraction.  1 <= V <= 16, 1 <= K <= min(C, 16), extents >= 1, N * OH * OW < 2^29, prob below 2^31 bytes; the three buffers
+ * must not alias. */
+int mmseg_members_accumulate(const float* prob, const double* back, float* sum, float* aux, int first, int V, int N, int OH, int OW, int C,
+                             int K, void* stream);
+/* In place.  cnt = aux_1.  sum becomes the mean map: p_k = cnt == 1 ? sum_k : cnt == 0 ? 0 : sum_k / cnt (so one model's mean is
+ * mmseg_merge_views's map bit for bit).  rest and Hraw = sum of t over the mean's K + 1 probabilities by the expressions above;
+ * E = cnt == 1 ? aux_0 : aux_0 / cnt; inv = (float)(1 / ln(K + 1)).  aux becomes (H, I): H = min(1, Hraw * inv), the predictive entropy,
+ * and I = max(0, Hraw - E) * inv, the mutual information between the label and the member (the part of H that is disagreement between
+ * members), both as shares of ln(K + 1).  cnt == 0: mean 0, H = 0, I = 0.  One member gives I == 0 bit for bit. */
+int mmseg_members_finish(float* sum, float* aux, int N, int OH, int OW, int K, void* stream);
+/* planes [S,OH,OW,U] fp32, 1 <= U <= 4: plane 0 <= u < U goes to out [S,H,W] uint8, every byte written.  Geometry, taps and the bilinear
+ * expression are those of mmseg_restore_label.  A pixel that was cropped away gets 0; inside the window the sample v becomes
+ * level = (unsigned char)(min(max(v, 0), 1) * 255 + 0.5f) in fp32 without contraction. */
+int mmseg_restore_map(const float* planes, unsigned char* out, int S, int H, int W, int RH, int RW, int OH, int OW, int lo_r, int kept_r,
+                      int before_r, int lo_c, int kept_c, int before_c, int U, int u, int order, void* stream);
+/* The reliability table of a map against a label volume.  prob [S,OH,OW,C] fp32, truth [S,H,W] uint8, values [K] int32 on the device,
+ * 2 <= B <= 64, S * H * W < 2^31 - 1.  For every raw pixel inside the window (the others are skipped) and every organ k: p is sampled as
+ * mmseg_restore_label samples it, y = truth == values[k], b = min(B - 1, (int)(p * (float)B)) in fp32 (and at least 0).
+ * bins [K,B,2] int32 = (n, positives) per organ and bin: zeroed on the stream, integer atomics.  sums [K,B+2] fp64, every element written:
+ * per organ the sum of p in each bin, then the sum of (p - y)^2 (fp64 from the fp32 p), then the sum of -logf(max(y ? p : 1 - p, 1e-6))
+ * (fp32 terms).  Every sum is taken in one fixed order (per block over its pixels in ascending order, then over the blocks): no
+ * floating-point atomics.  ws: the bytes the query returns (0 for arguments that the call would refuse). */
+long mmseg_calibration_table_workspace_bytes(int S, int H, int W, int K, int B);
+int mmseg_calibration_table(const float* prob, const unsigned char* truth, const int* values, int* bins, double* sums, double* ws, int S,
+                            int H, int W, int RH, int RW, int OH, int OW, int lo_r, int kept_r, int before_r, int lo_c, int kept_c,
+                            int before_c, int C, int K, int B, int order, void* stream);
+/* pred, truth [n] uint8, levels [U,n] uint8 (1 <= U <= 4, n < 2^31 - 1) -> out [2,1+U] int64, zeroed on the stream: row 0 covers the
+ * pixels with pred == truth, row 1 the others; a row holds their number and, per plane, the sum of their levels.  Integers only. */
+int mmseg_uncertainty_by_error(const unsigned char* pred, const unsigned char* truth, const unsigned char* levels, long long* out, long n,
+                               int U, void* stream);
+
 /* ---- maps refined against the image: a windowed mean-field CRF (csrc/crf.hip; build-defined, the rule is in INTEGRATION.md section 5) ----
  * prob [N,H,W,C] fp32: a segmentor's output on the network grid, the K organ channels first.  image [N,H,W,1] fp32: the slices the network
  * saw, in [-1, 1] (finite).  out [N,H,W,K] fp32, every element written: the organ channels of Q^T.  L = K + 1 labels: the K organs and

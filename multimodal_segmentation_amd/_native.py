@@ -20,7 +20,7 @@ SOURCES = ('conv.hip', 'pointwise.hip', 'norm.hip', 'act16.hip', 'dense.hip', 't
 
 _CTYPES = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'void*': ctypes.c_void_p,
            'const float*': ctypes.c_void_p, 'float*': ctypes.c_void_p, 'const int*': ctypes.c_void_p, 'int*': ctypes.c_void_p, 'const void*': ctypes.c_void_p,
-           'const long long*': ctypes.c_void_p, 'const double*': ctypes.c_void_p, 'const unsigned char*': ctypes.c_void_p,
+           'const long long*': ctypes.c_void_p, 'long long*': ctypes.c_void_p, 'const double*': ctypes.c_void_p, 'const unsigned char*': ctypes.c_void_p,
            'unsigned char*': ctypes.c_void_p, 'double': ctypes.c_double, 'double*': ctypes.c_void_p}
 
 

@@ -80,6 +80,19 @@
 //   mean over the views that cover it of the view's map sampled bilinearly at back[v] (r, c), an fp64 2 x 3 matrix per view.  A gather
 //   like the blend: one thread per output element, the views in ascending order, two runs bitwise equal; a pixel that one view covers
 //   is that view's sample, and an integer coordinate (every flip and right-angle turn) is a tap, copied.
+//
+// Several models and views, their mean, its uncertainty and its calibration (build-defined; the rule is in INTEGRATION.md section 5 and the
+// header).
+// mmseg_members_accumulate: the merge with state: one model's V views of N slices are added, per pixel, into sum [N,OH,OW,K] and aux
+//   [N,OH,OW,2] = (sum of the views' entropies over the K organs and the rest, their number), so that any number of models stream through
+//   one pair of buffers.  mmseg_members_finish, in place: the mean (merge_views's rule, so one model's mean is its merged map bit for bit),
+//   H = the entropy of the mean and I = H - the mean entropy of the members (mutual information), as shares of ln(K + 1).  A thread owns
+//   a pixel on both paths: the entropy needs a pixel's channels in one place and in one order.
+// mmseg_restore_map: mmseg_restore_label's geometry and taps with a grey level in place of the 0.5 rule: one plane of [S,OH,OW,U] -> uint8.
+// mmseg_calibration_table: per organ and confidence bin the pixel counts (integer atomics) and the fp64 sums a reliability diagram, ECE,
+//   Brier score and NLL are made of; tiles of 256 pixels staged in LDS, every table entry summed by the one thread that owns it, in a
+//   fixed order, then over the blocks in a fixed order: no floating-point atomics, two runs bitwise equal.
+// mmseg_uncertainty_by_error: counts and level sums of the uncertainty planes over the correctly and the wrongly labelled pixels; integers.
 #include "common.hpp"
 #include <math.h>
 
@@ -371,6 +384,333 @@ __global__ void __launch_bounds__(PO_BLOCK) po_overlap_kernel(const unsigned cha
         int v = 0;
         for (int w = 0; w < PO_BLOCK / 64; ++w) v += red[w][threadIdx.x];
         if (v) atomicAdd(counts + (size_t)s * K * 3 + threadIdx.x, v);
+    }
+}
+
+// ---- several models and views of a slice: the mean map, its entropy and the members' disagreement -------------------------------------------
+// t(x) = -x ln x, 0 for x <= 0 (and for a NaN)
+__device__ __forceinline__ float po_xlogx(float x) {
+#pragma clang fp contract(off)
+    return x > 0.f ? -x * logf(x) : 0.f;
+}
+
+// the entropy, in nats, of the K organ probabilities q and of rest = max(0, 1 - (((q0 + q1) + ..) + q[K-1])): the terms added from 0 in
+// ascending k, the rest last.  One body for the accumulation and for the finish, so that the entropy of a single member's map and the
+// entropy of its mean are the same instructions on the same bits.  Inlined into fully unrolled callers: q stays in registers.
+__device__ __forceinline__ float po_entropy(const float (&q)[PO_MAXVALUES], int K) {
+#pragma clang fp contract(off)
+    float total = q[0], h = 0.f;
+#pragma unroll
+    for (int k = 0; k < PO_MAXVALUES; ++k)
+        if (k < K) {
+            if (k > 0) total = total + q[k];
+            h = h + po_xlogx(q[k]);
+        }
+    return h + po_xlogx(fmaxf(0.f, 1.f - total));
+}
+
+// Both paths: a thread owns one PIXEL (the entropy needs all of a pixel's channels in one place, in a fixed order of addition).  VEC4: K == 4,
+// C % 4 == 0, prob and sum 16-byte aligned: one 16-byte load per tap, one 16-byte load and store of the sums.  Otherwise K scalar loads per
+// tap at a stride of C floats between neighbouring lanes (a wave still reads whole cache lines: its 64 pixels are contiguous) and K scalar
+// stores at a stride of K floats.  The K accumulators and the K samples of a view live in registers: every loop over k is unrolled to
+// PO_MAXVALUES with `k < K` as a uniform branch.  Grid-stride over the N * OH * OW < 2^29 pixels.  Coverage and sample: po_merge_kernel's.
+template <bool VEC4>
+__global__ void __launch_bounds__(PO_BLOCK) po_members_kernel(const float* __restrict__ prob, const double* __restrict__ back,
+                                                              float* __restrict__ sum, float* __restrict__ aux, int first, int V, int N,
+                                                              int OH, int OW, int C, int K, int pixels) {
+#pragma clang fp contract(off)
+    __shared__ double mb[MV_MAXVIEWS * 6];
+    if (threadIdx.x < V * 6) mb[threadIdx.x] = back[threadIdx.x];
+    __syncthreads();
+    const int plane = OH * OW;
+    const double hr = (double)(OH - 1), hc = (double)(OW - 1);
+    for (int e = blockIdx.x * PO_BLOCK + threadIdx.x; e < pixels; e += gridDim.x * PO_BLOCK) {
+        const int s = e / plane, p = e - s * plane;
+        const int r = p / OW, c = p - r * OW;
+        float acc[PO_MAXVALUES], q[PO_MAXVALUES];
+#pragma unroll
+        for (int k = 0; k < PO_MAXVALUES; ++k) acc[k] = q[k] = 0.f;
+        float sh = 0.f, cnt = 0.f;
+        if (!first) {
+            if constexpr (VEC4) {
+                const f32x4 a = reinterpret_cast<const f32x4*>(sum)[e];
+                acc[0] = a[0], acc[1] = a[1], acc[2] = a[2], acc[3] = a[3];
+            } else {
+#pragma unroll
+                for (int k = 0; k < PO_MAXVALUES; ++k)
+                    if (k < K) acc[k] = sum[(size_t)e * K + k];
+            }
+            sh = aux[2 * (size_t)e];
+            cnt = aux[2 * (size_t)e + 1];
+        }
+        for (int v = 0; v < V; ++v) {
+            const double* b = mb + 6 * v;
+            const double sr = (b[0] * r + b[1] * c) + b[2], sc = (b[3] * r + b[4] * c) + b[5];
+            if (!(sr >= 0.0 && sr <= hr && sc >= 0.0 && sc <= hc)) continue;
+            int r0, r1, c0, c1;
+            float fy, fx;
+            mv_axis(sr, OH, r0, r1, fy);
+            mv_axis(sc, OW, c0, c1, fx);
+            const float* src = prob + ((size_t)v * N + s) * plane * C;
+            if constexpr (VEC4) {
+                const f32x4 x = mv_sample<f32x4>(src, OW, C, r0, r1, c0, c1, fy, fx);
+                q[0] = x[0], q[1] = x[1], q[2] = x[2], q[3] = x[3];
+            } else {
+#pragma unroll
+                for (int k = 0; k < PO_MAXVALUES; ++k)
+                    if (k < K) q[k] = mv_sample<float>(src + k, OW, C, r0, r1, c0, c1, fy, fx);
+            }
+#pragma unroll
+            for (int k = 0; k < PO_MAXVALUES; ++k)
+                if (k < (VEC4 ? 4 : K)) acc[k] = acc[k] + q[k];
+            sh = sh + po_entropy(q, VEC4 ? 4 : K);
+            cnt = cnt + 1.f;
+        }
+        if constexpr (VEC4) {
+            reinterpret_cast<f32x4*>(sum)[e] = f32x4{acc[0], acc[1], acc[2], acc[3]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < PO_MAXVALUES; ++k)
+                if (k < K) sum[(size_t)e * K + k] = acc[k];
+        }
+        aux[2 * (size_t)e] = sh;
+        aux[2 * (size_t)e + 1] = cnt;
+    }
+}
+
+// in place: sum -> the mean map, aux (sum of the members' entropies, their number) -> (H, I); inv = (float)(1 / ln(K + 1))
+template <bool VEC4>
+__global__ void __launch_bounds__(PO_BLOCK) po_members_finish_kernel(float* __restrict__ sum, float* __restrict__ aux, int K, float inv,
+                                                                     int pixels) {
+#pragma clang fp contract(off)
+    for (int e = blockIdx.x * PO_BLOCK + threadIdx.x; e < pixels; e += gridDim.x * PO_BLOCK) {
+        float q[PO_MAXVALUES];
+#pragma unroll
+        for (int k = 0; k < PO_MAXVALUES; ++k) q[k] = 0.f;
+        const float sh = aux[2 * (size_t)e], cnt = aux[2 * (size_t)e + 1];
+        if constexpr (VEC4) {
+            const f32x4 a = reinterpret_cast<const f32x4*>(sum)[e];
+            q[0] = a[0], q[1] = a[1], q[2] = a[2], q[3] = a[3];
+        } else {
+#pragma unroll
+            for (int k = 0; k < PO_MAXVALUES; ++k)
+                if (k < K) q[k] = sum[(size_t)e * K + k];
+        }
+#pragma unroll
+        for (int k = 0; k < PO_MAXVALUES; ++k)
+            if (k < (VEC4 ? 4 : K)) q[k] = cnt == 1.f ? q[k] : cnt == 0.f ? 0.f : q[k] / cnt;
+        const float raw = po_entropy(q, VEC4 ? 4 : K);
+        const float mean = cnt == 1.f ? sh : sh / cnt;
+        const bool none = cnt == 0.f;
+        if constexpr (VEC4) {
+            reinterpret_cast<f32x4*>(sum)[e] = f32x4{q[0], q[1], q[2], q[3]};
+        } else {
+#pragma unroll
+            for (int k = 0; k < PO_MAXVALUES; ++k)
+                if (k < K) sum[(size_t)e * K + k] = q[k];
+        }
+        aux[2 * (size_t)e] = none ? 0.f : fminf(1.f, raw * inv);
+        aux[2 * (size_t)e + 1] = none ? 0.f : fmaxf(0.f, raw - mean) * inv;
+    }
+}
+
+// plane u of one raw pixel of a [OH,OW,U] fp32 container as a grey level: 0 outside the window, else the sample (restore_label's taps and
+// po_mix) limited to [0, 1], times 255, rounded half up
+__device__ __forceinline__ unsigned po_level(const float* __restrict__ src, int OW, int U, int u, po_tap ty, po_tap tx, int order) {
+#pragma clang fp contract(off)
+    if (!(ty.in && tx.in)) return 0u;
+    float v = src[((size_t)ty.i0 * OW + tx.i0) * U + u];
+    if (order != 0)
+        v = po_mix(v, src[((size_t)ty.i0 * OW + tx.i1) * U + u], src[((size_t)ty.i1 * OW + tx.i0) * U + u],
+                   src[((size_t)ty.i1 * OW + tx.i1) * U + u], ty.f, tx.f);
+    return (unsigned)(unsigned char)(fminf(fmaxf(v, 0.f), 1.f) * 255.f + 0.5f);
+}
+
+// grid (nblk, S), block PO_BLOCK, as po_restore_kernel.  PACK: a lane owns 4 adjacent columns (W % 4 == 0, out 4-byte aligned), one dword.
+template <bool PACK>
+__global__ void __launch_bounds__(PO_BLOCK) po_restore_map_kernel(const float* __restrict__ planes, unsigned char* __restrict__ out, int H,
+                                                                  int W, int RH, int RW, double ry, double rx, int OH, int OW, po_axis ar,
+                                                                  po_axis ac, int U, int u, int order) {
+    const int s = blockIdx.y;
+    const float* src = planes + (size_t)s * OH * OW * U;
+    unsigned char* dst = out + (size_t)s * H * W;
+    if constexpr (PACK) {
+        const int W4 = W >> 2, n = H * W4;
+        for (int e = blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += gridDim.x * PO_BLOCK) {
+            const int r = e / W4, c = (e - r * W4) << 2;
+            const po_tap ty = po_axis_tap(r, ry, RH, ar, order);
+            unsigned word = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) word |= po_level(src, OW, U, u, ty, po_axis_tap(c + j, rx, RW, ac, order), order) << (8 * j);
+            reinterpret_cast<unsigned*>(dst)[e] = word;
+        }
+    } else {
+        const int n = H * W;
+        for (int e = blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += gridDim.x * PO_BLOCK) {
+            const int r = e / W, c = e - r * W;
+            dst[e] = (unsigned char)po_level(src, OW, U, u, po_axis_tap(r, ry, RH, ar, order), po_axis_tap(c, rx, RW, ac, order), order);
+        }
+    }
+}
+
+// ---- the reliability table of a probability map against a label volume ----------------------------------------------------------------------------
+#define CT_MAXBINS 64
+#define CT_MAXBLK 1024         // blocks, and so partial tables that po_calibration_final_kernel adds
+#define CT_SKIP 255            // code of a pixel outside the window; otherwise bin | (y << 7), bin < 64
+#define CT_MAXOWN ((PO_MAXVALUES * (CT_MAXBINS + 2) + PO_BLOCK - 1) / PO_BLOCK)          // entries of the table per thread
+
+// A block takes tiles of PO_BLOCK consecutive raw pixels of [S,H,W] in grid-stride order.  Per tile every thread samples the K organ
+// channels of its pixel (restore_label's taps and po_mix) and stages p, the nll term and a code (bin, y, or CT_SKIP) in LDS; then thread
+// t OWNS the entries t, t + PO_BLOCK, .. of the [K][B+2] table and walks the tile's PO_BLOCK staged pixels in ascending order, adding
+// the ones of its organ (and bin).  So every entry is a sum in one fixed order (tiles ascending, pixels ascending), in fp64, whatever the
+// scheduling: no floating-point atomics.  The owners of bin entries count (n, positives) on the way and add them to `bins` with one
+// integer atomic each at the end.  part [gridDim.x][K * (B + 2)].  LDS: K * PO_BLOCK * 9 bytes, dynamic.
+__global__ void __launch_bounds__(PO_BLOCK) po_calibration_kernel(const float* __restrict__ prob, const unsigned char* __restrict__ truth,
+                                                                  const int* __restrict__ values, int* __restrict__ bins,
+                                                                  double* __restrict__ part, long n, int H, int W, int RH, int RW, double ry,
+                                                                  double rx, int OH, int OW, po_axis ar, po_axis ac, int C, int K, int B,
+                                                                  int order) {
+#pragma clang fp contract(off)
+    extern __shared__ float ct_lds[];
+    float* sp = ct_lds;                                                       // [K][PO_BLOCK]
+    float* sl = ct_lds + (size_t)K * PO_BLOCK;                                // [K][PO_BLOCK]
+    unsigned char* sc = reinterpret_cast<unsigned char*>(sl + (size_t)K * PO_BLOCK);          // [K][PO_BLOCK]
+    __shared__ int vals[PO_MAXVALUES];
+    if (threadIdx.x < K) vals[threadIdx.x] = values[threadIdx.x];
+    const int entries = K * (B + 2), plane = H * W;
+    double acc[CT_MAXOWN];
+    int cn[CT_MAXOWN], cy[CT_MAXOWN];
+#pragma unroll
+    for (int j = 0; j < CT_MAXOWN; ++j) acc[j] = 0.0, cn[j] = cy[j] = 0;
+    __syncthreads();
+    for (long base = (long)blockIdx.x * PO_BLOCK; base < n; base += (long)gridDim.x * PO_BLOCK) {
+        const long e = base + threadIdx.x;
+        bool in = false;
+        po_tap ty, tx;
+        const float* src = prob;
+        int tv = 0;
+        if (e < n) {
+            const int s = (int)(e / plane), p = (int)(e - (long)s * plane);
+            const int r = p / W, c = p - r * W;
+            ty = po_axis_tap(r, ry, RH, ar, order);
+            tx = po_axis_tap(c, rx, RW, ac, order);
+            in = ty.in && tx.in;
+            src = prob + (size_t)s * OH * OW * C;
+            tv = truth[e];
+        }
+        for (int k = 0; k < K; ++k) {
+            unsigned char code = CT_SKIP;
+            float p = 0.f, nll = 0.f;
+            if (in) {
+                p = src[((size_t)ty.i0 * OW + tx.i0) * C + k];
+                if (order != 0)
+                    p = po_mix(p, src[((size_t)ty.i0 * OW + tx.i1) * C + k], src[((size_t)ty.i1 * OW + tx.i0) * C + k],
+                               src[((size_t)ty.i1 * OW + tx.i1) * C + k], ty.f, tx.f);
+                const bool y = tv == vals[k];
+                const int b = min(B - 1, max(0, (int)(p * (float)B)));          // the lower limit only matters for a p outside [0, 1]
+                nll = -logf(fmaxf(y ? p : 1.f - p, 1e-6f));
+                code = (unsigned char)(b | (y ? 128 : 0));
+            }
+            sp[k * PO_BLOCK + threadIdx.x] = p;
+            sl[k * PO_BLOCK + threadIdx.x] = nll;
+            sc[k * PO_BLOCK + threadIdx.x] = code;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < CT_MAXOWN; ++j) {
+            const int entry = j * PO_BLOCK + threadIdx.x;
+            if (entry < entries) {
+                const int k = entry / (B + 2), b = entry - k * (B + 2);
+                const float* pk = sp + k * PO_BLOCK;
+                const float* lk = sl + k * PO_BLOCK;
+                const unsigned char* ck = sc + k * PO_BLOCK;
+                if (b < B) {
+                    for (int i = 0; i < PO_BLOCK; ++i) {
+                        const int code = ck[i];
+                        if ((code & 127) == b && code != CT_SKIP) {
+                            acc[j] += (double)pk[i];
+                            cn[j] += 1;
+                            cy[j] += code >> 7;
+                        }
+                    }
+                } else if (b == B) {
+                    for (int i = 0; i < PO_BLOCK; ++i) {
+                        const int code = ck[i];
+                        if (code != CT_SKIP) {
+                            const double d = (double)pk[i] - (double)(code >> 7);
+                            acc[j] += d * d;
+                        }
+                    }
+                } else {
+                    for (int i = 0; i < PO_BLOCK; ++i)
+                        if (ck[i] != CT_SKIP) acc[j] += (double)lk[i];
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < CT_MAXOWN; ++j) {
+        const int entry = j * PO_BLOCK + threadIdx.x;
+        if (entry < entries) {
+            part[(size_t)blockIdx.x * entries + entry] = acc[j];
+            const int k = entry / (B + 2), b = entry - k * (B + 2);
+            if (b < B && cn[j]) {
+                atomicAdd(bins + ((size_t)k * B + b) * 2, cn[j]);
+                if (cy[j]) atomicAdd(bins + ((size_t)k * B + b) * 2 + 1, cy[j]);
+            }
+        }
+    }
+}
+
+// sums [entries] = the partial tables added in ascending block order, one thread per entry
+__global__ void __launch_bounds__(PO_BLOCK) po_calibration_final_kernel(const double* __restrict__ part, int nblk, int entries,
+                                                                        double* __restrict__ sums) {
+    const int entry = blockIdx.x * PO_BLOCK + threadIdx.x;
+    if (entry >= entries) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += part[(size_t)b * entries + entry];
+    sums[entry] = s;
+}
+
+// ---- the levels of the uncertainty planes over the correctly and the wrongly labelled pixels -----------------------------------------------------
+#define UE_MAXPLANES 4
+
+// out [2][1 + U] += (count, sum of levels per plane) of this block's grid-stride share, row = pred != truth.  A thread visits at most
+// 2^31 / (PO_MAXBLK * PO_BLOCK) = 2^15 pixels, so its 32-bit sums stay below 2^23; the block's sums are 64-bit.
+__global__ void __launch_bounds__(PO_BLOCK) po_uncertainty_error_kernel(const unsigned char* __restrict__ pred,
+                                                                        const unsigned char* __restrict__ truth,
+                                                                        const unsigned char* __restrict__ levels,
+                                                                        unsigned long long* __restrict__ out, long n, int U) {
+    __shared__ unsigned red[PO_BLOCK / 64][2 * (1 + UE_MAXPLANES)];
+    unsigned c[2 * (1 + UE_MAXPLANES)];
+#pragma unroll
+    for (int j = 0; j < 2 * (1 + UE_MAXPLANES); ++j) c[j] = 0u;
+    for (long e = (long)blockIdx.x * PO_BLOCK + threadIdx.x; e < n; e += (long)gridDim.x * PO_BLOCK) {
+        const unsigned wrong = pred[e] != truth[e];
+        c[0] += 1u - wrong;
+        c[1 + UE_MAXPLANES] += wrong;
+#pragma unroll
+        for (int u = 0; u < UE_MAXPLANES; ++u)
+            if (u < U) {
+                const unsigned l = levels[(size_t)u * n + e];
+                c[1 + u] += wrong ? 0u : l;
+                c[2 + UE_MAXPLANES + u] += wrong ? l : 0u;
+            }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 2 * (1 + UE_MAXPLANES); ++j) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c[j] += __shfl_xor(c[j], o, 64);          // a wave's sum: below 64 * 2^23
+        if (lane == 0) red[wid][j] = c[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * (1 + UE_MAXPLANES)) {
+        const int row = threadIdx.x / (1 + UE_MAXPLANES), col = threadIdx.x - row * (1 + UE_MAXPLANES);
+        unsigned long long v = 0ull;
+        for (int w = 0; w < PO_BLOCK / 64; ++w) v += red[w][threadIdx.x];
+        if (col <= U && v) atomicAdd(out + (size_t)row * (1 + U) + col, v);
     }
 }
 
@@ -1466,6 +1806,114 @@ int mmseg_merge_views(const float* prob, const double* back, float* out, int V, 
     const hipStream_t st = (hipStream_t)stream;
     if (vec4) hipLaunchKernelGGL(po_merge_kernel<true>, grid, block, 0, st, prob, back, out, V, N, OH, OW, C, K, total, true);
     else hipLaunchKernelGGL(po_merge_kernel<false>, grid, block, 0, st, prob, back, out, V, N, OH, OW, C, K, total, total < 0x7fffffffL);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// N * OH * OW of a member map, or -1 for a shape that the member kernels refuse (2^29 pixels or more; taken factor by factor)
+static long po_member_pixels(int N, int OH, int OW) {
+    if (N < 0 || OH < 1 || OW < 1) return -1;
+    long pixels = N;
+    for (const int f : {OH, OW}) {
+        pixels *= f;
+        if (pixels >= (1L << 29)) return -1;
+    }
+    return pixels;
+}
+
+// prob [V*N,OH,OW,C] fp32, back [V,6] fp64 (device), sum [N,OH,OW,K] and aux [N,OH,OW,2] fp32: read unless first != 0, every element
+// written.  One launch; no atomics, nothing allocated or synchronised.
+int mmseg_members_accumulate(const float* prob, const double* back, float* sum, float* aux, int first, int V, int N, int OH, int OW, int C,
+                             int K, void* stream) {
+    if (N == 0) return 0;
+    const long pixels = po_member_pixels(N, OH, OW);
+    if (!prob || !back || !sum || !aux || prob == sum || prob == aux || sum == aux || pixels < 0 || V < 1 || V > MV_MAXVIEWS || C < 1 ||
+        K < 1 || K > C || K > PO_MAXVALUES || (long)sizeof(float) * pixels * V >= 0x80000000L ||
+        (long)sizeof(float) * pixels * V * C >= 0x80000000L)          // bytes of prob; the first product bounds the second below 2^62
+        return (int)hipErrorInvalidValue;
+    const bool vec4 = K == 4 && (C & 3) == 0 && ((uintptr_t)prob & 15) == 0 && ((uintptr_t)sum & 15) == 0;
+    const dim3 grid(po_grid(pixels, PO_SURF_MAXBLK)), block(PO_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec4) hipLaunchKernelGGL(po_members_kernel<true>, grid, block, 0, st, prob, back, sum, aux, first, V, N, OH, OW, C, K, (int)pixels);
+    else hipLaunchKernelGGL(po_members_kernel<false>, grid, block, 0, st, prob, back, sum, aux, first, V, N, OH, OW, C, K, (int)pixels);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// sum [N,OH,OW,K] -> the mean map, aux [N,OH,OW,2] -> (H, I), in place.  One launch.
+int mmseg_members_finish(float* sum, float* aux, int N, int OH, int OW, int K, void* stream) {
+    if (N == 0) return 0;
+    const long pixels = po_member_pixels(N, OH, OW);
+    if (!sum || !aux || sum == aux || pixels < 0 || K < 1 || K > PO_MAXVALUES) return (int)hipErrorInvalidValue;
+    const bool vec4 = K == 4 && ((uintptr_t)sum & 15) == 0;
+    const float inv = (float)(1.0 / log((double)(K + 1)));
+    const dim3 grid(po_grid(pixels, PO_SURF_MAXBLK)), block(PO_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    if (vec4) hipLaunchKernelGGL(po_members_finish_kernel<true>, grid, block, 0, st, sum, aux, K, inv, (int)pixels);
+    else hipLaunchKernelGGL(po_members_finish_kernel<false>, grid, block, 0, st, sum, aux, K, inv, (int)pixels);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// planes [S,OH,OW,U] fp32, out [S,H,W] uint8: every byte is written
+int mmseg_restore_map(const float* planes, unsigned char* out, int S, int H, int W, int RH, int RW, int OH, int OW, int lo_r, int kept_r,
+                      int before_r, int lo_c, int kept_c, int before_c, int U, int u, int order, void* stream) {
+    if (S <= 0) return 0;
+    if (!planes || !out || !po_geometry_ok(S, H, W, RH, RW, OH, OW) || U < 1 || U > UE_MAXPLANES || u < 0 || u >= U ||
+        (order != 0 && order != 1) || !po_axis_ok(lo_r, kept_r, before_r, RH, OH) || !po_axis_ok(lo_c, kept_c, before_c, RW, OW))
+        return (int)hipErrorInvalidValue;
+    const bool pack = (W & 3) == 0 && ((uintptr_t)out & 3) == 0;
+    const dim3 grid(po_grid(pack ? (long)H * (W >> 2) : (long)H * W, PO_MAXBLK), S), block(PO_BLOCK);
+    const po_axis ar = {lo_r, kept_r, before_r}, ac = {lo_c, kept_c, before_c};
+    const double ry = (double)RH / (double)H, rx = (double)RW / (double)W;
+    const hipStream_t st = (hipStream_t)stream;
+    if (pack) hipLaunchKernelGGL(po_restore_map_kernel<true>, grid, block, 0, st, planes, out, H, W, RH, RW, ry, rx, OH, OW, ar, ac, U, u, order);
+    else hipLaunchKernelGGL(po_restore_map_kernel<false>, grid, block, 0, st, planes, out, H, W, RH, RW, ry, rx, OH, OW, ar, ac, U, u, order);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+static bool po_calibration_ok(int S, int H, int W, int RH, int RW, int OH, int OW, int C, int K, int B) {
+    return S >= 1 && po_geometry_ok(S, H, W, RH, RW, OH, OW) && (long)S * H * W < 0x7fffffffL && C >= 1 && K >= 1 && K <= C &&
+           K <= PO_MAXVALUES && B >= 2 && B <= CT_MAXBINS;
+}
+
+// bytes of ws for mmseg_calibration_table: one partial [K][B+2] fp64 table per block; 0 for arguments that it would refuse
+long mmseg_calibration_table_workspace_bytes(int S, int H, int W, int K, int B) {
+    if (!po_calibration_ok(S, H, W, 1, 1, 1, 1, K, K, B)) return 0;
+    return (long)sizeof(double) * po_grid((long)S * H * W, CT_MAXBLK) * K * (B + 2);
+}
+
+// prob [S,OH,OW,C] fp32, truth [S,H,W] uint8, values [K] int32 (device) -> bins [K,B,2] int32 (zeroed here, on the stream), sums [K,B+2]
+// fp64, every element written.  ws: mmseg_calibration_table_workspace_bytes bytes.  One memset and two launches.
+int mmseg_calibration_table(const float* prob, const unsigned char* truth, const int* values, int* bins, double* sums, double* ws, int S,
+                            int H, int W, int RH, int RW, int OH, int OW, int lo_r, int kept_r, int before_r, int lo_c, int kept_c,
+                            int before_c, int C, int K, int B, int order, void* stream) {
+    if (S == 0) return 0;
+    if (!prob || !truth || !values || !bins || !sums || !ws || !po_calibration_ok(S, H, W, RH, RW, OH, OW, C, K, B) ||
+        (order != 0 && order != 1) || !po_axis_ok(lo_r, kept_r, before_r, RH, OH) || !po_axis_ok(lo_c, kept_c, before_c, RW, OW))
+        return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t rc = hipMemsetAsync(bins, 0, sizeof(int) * 2 * (size_t)K * B, st);
+    if (rc != hipSuccess) return (int)rc;
+    const long n = (long)S * H * W;
+    const int nblk = (int)po_grid(n, CT_MAXBLK), entries = K * (B + 2);
+    const po_axis ar = {lo_r, kept_r, before_r}, ac = {lo_c, kept_c, before_c};
+    double* part = ws;
+    hipLaunchKernelGGL(po_calibration_kernel, dim3(nblk), dim3(PO_BLOCK), (size_t)K * PO_BLOCK * 9, st, prob, truth, values, bins, part, n, H,
+                       W, RH, RW, (double)RH / (double)H, (double)RW / (double)W, OH, OW, ar, ac, C, K, B, order);
+    hipLaunchKernelGGL(po_calibration_final_kernel, dim3((entries + PO_BLOCK - 1) / PO_BLOCK), dim3(PO_BLOCK), 0, st, part, nblk, entries,
+                       sums);
+    return MMSEG_CHECK_LAUNCH();
+}
+
+// pred, truth [n] uint8, levels [U,n] uint8 -> out [2,1+U] int64 (zeroed here, on the stream): per row (pred == truth, pred != truth) the
+// number of pixels and the sum of every plane's levels over them
+int mmseg_uncertainty_by_error(const unsigned char* pred, const unsigned char* truth, const unsigned char* levels, long long* out, long n,
+                               int U, void* stream) {
+    if (n == 0) return 0;
+    if (!pred || !truth || !levels || !out || n < 0 || n >= 0x7fffffffL || U < 1 || U > UE_MAXPLANES) return (int)hipErrorInvalidValue;
+    const hipStream_t st = (hipStream_t)stream;
+    const hipError_t rc = hipMemsetAsync(out, 0, sizeof(long long) * 2 * (size_t)(1 + U), st);
+    if (rc != hipSuccess) return (int)rc;
+    hipLaunchKernelGGL(po_uncertainty_error_kernel, dim3(po_grid(n, PO_MAXBLK)), dim3(PO_BLOCK), 0, st, pred, truth, levels,
+                       reinterpret_cast<unsigned long long*>(out), n, U);
     return MMSEG_CHECK_LAUNCH();
 }
 

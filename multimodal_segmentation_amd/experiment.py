@@ -16,6 +16,7 @@
                          [--predict_robust true|false] [--predict_percentile Q] [--predict_tolerance MM]
                          [--predict_tiles true|false] [--predict_tile_overlap PIXELS] [--predict_tta LIST]
                          [--predict_crf SPEC]
+                         [--predict_ensemble RUN[,RUN...]] [--predict_uncertainty true|false] [--predict_calibration_bins B]
 
 `--data_folder` (build-defined, like `conf.data_folder`) names a folder of exported volumes (loaders/volume_folder.py); without it
 every configuration trains and tests on the synthetic volumes.  `--intensity_norm` and its two companions (build-defined, like
@@ -152,6 +153,15 @@ def parse_arguments(argv=None):
                          'none, default, or key=value,... over the defaults radius=5,iterations=5,w_a=4,theta_alpha=3,theta_beta=0.1,'
                          'w_s=1,theta_gamma=1.5, which are untuned starting values (tools/crf_sweep.py scores a grid of settings; '
                          'results_crf_<modality>.csv)')
+    ap.add_argument('--predict_ensemble', default=None, metavar='RUN[,RUN...]',
+                    help='further run folders (at most 7, e.g. the other splits of a cross-validation) whose checkpoints predict '
+                         'together with this run: the mean of the models, its entropy and their disagreement '
+                         '(<out>/uncertainty/, results_calibration_, reliability_ and results_uncertainty_<modality>.csv)')
+    ap.add_argument('--predict_uncertainty', type=true_or_false, default=False, metavar='true|false',
+                    help='write the uncertainty and calibration files of --predict_ensemble for this run alone (with --predict_tta '
+                         'the views are the members)')
+    ap.add_argument('--predict_calibration_bins', type=int, default=10, metavar='B',
+                    help='bins of the reliability table of --predict_ensemble / --predict_uncertainty, 2 to 64')
     args = ap.parse_args(argv)
     if (args.intensity_scope or args.intensity_percentiles) and args.intensity_norm != 'window':
         ap.error('--intensity_scope and --intensity_percentiles go with --intensity_norm window')
@@ -328,6 +338,46 @@ def warn_predict_stages(conf, folder, log):
     return warned
 
 
+MEMBER_KEYS = ('model', 'input_shape', 'num_masks', 'modality')          # what a member of --predict_ensemble must share with the run
+
+
+def ensemble_folders(text):
+    """--predict_ensemble RUN[,RUN...] -> the folders; None or '' -> []"""
+    from .volume_predictor import MAX_MEMBERS
+    if text is None or not str(text).strip():
+        return []
+    folders = [f.strip() for f in str(text).split(',')]
+    if not all(folders) or len(folders) > MAX_MEMBERS:
+        raise ValueError('--predict_ensemble takes 1 to %d run folders RUN[,RUN...], got %r' % (MAX_MEMBERS, text))
+    return folders
+
+
+def member_conf(conf, folder):
+    """the configuration a member of --predict_ensemble is built on: a copy of `conf` whose folder is that run.  The run must hold a
+    checkpoint (FileNotFoundError), and what its experiment_configuration.json records of MEMBER_KEYS must be the run's (ValueError);
+    a run folder without that file is taken at its word."""
+    from . import volume_predictor
+    if volume_predictor.checkpoint_of(folder) is None:
+        raise FileNotFoundError('--predict_ensemble: the run folder %s holds no checkpoint to predict with' % folder)
+    member = EasyDict(dict(conf.items()))
+    member.folder = folder
+    theirs = member_record(folder)
+    for key in MEMBER_KEYS:
+        if key in theirs and key in conf and json.loads(json.dumps(conf[key], default=_jsonable)) != theirs[key]:
+            raise ValueError('--predict_ensemble: the run folder %s records %s = %r, this run has %r: the members of an ensemble '
+                             'share model, input_shape, num_masks and modalities' % (folder, key, theirs[key], conf[key]))
+    return member
+
+
+def member_record(folder):
+    """what the experiment_configuration.json of a run folder records, {} without one"""
+    recorded = os.path.join(folder, 'experiment_configuration.json')
+    if not os.path.isfile(recorded):
+        return {}
+    with open(recorded) as f:
+        return json.load(f)
+
+
 class Experiment(object):
     def __init__(self):
         self.log = None
@@ -417,9 +467,21 @@ class Experiment(object):
         if dp.is_main():
             warn_predict_stages(conf, args.predict_folder, self.log)
             out = args.predict_out or os.path.join(conf.folder, 'predictions_%s' % read_manifest(args.predict_folder)['name'])
+            members = []
+            for folder in ensemble_folders(getattr(args, 'predict_ensemble', None)):
+                theirs = member_conf(conf, folder)
+                record = member_record(folder)          # the stages the member was trained under are the ones its folder records
+                warn_predict_stages(EasyDict(dict(theirs.items(), **{s: record[s] for s in STAGE_CLI if s in record})),
+                                    args.predict_folder, self.log)
+                members.append(theirs)
             model = resolve('models', conf.model)(conf)
             model.build()
-            VolumePredictor(model, conf).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
+            for i, theirs in enumerate(members):
+                members[i] = resolve('models', conf.model)(theirs)
+                members[i].build()
+            VolumePredictor(model, conf, members).run(args.predict_folder, out, mode=args.predict_mode, order=args.predict_order,
+                                              uncertainty=bool(getattr(args, 'predict_uncertainty', False)),
+                                              calibration_bins=getattr(args, 'predict_calibration_bins', 10),
                                               surface=getattr(args, 'predict_surface', True),
                                               components={'largest': 'largest'}.get(getattr(args, 'predict_components', 'none')),
                                               connectivity=getattr(args, 'predict_connectivity', 6), robust=robust_of(args),
@@ -450,6 +512,11 @@ class Experiment(object):
         if getattr(args, 'predict_crf', 'none') not in (None, 'none'):          # and so is this
             from .volume_predictor import check_crf
             check_crf(args.predict_crf)
+        if getattr(args, 'predict_ensemble', None) or getattr(args, 'predict_calibration_bins', 10) != 10:          # and these
+            from .volume_predictor import check_calibration_bins
+            check_calibration_bins(getattr(args, 'predict_calibration_bins', 10))
+            for folder in ensemble_folders(getattr(args, 'predict_ensemble', None)):
+                member_conf(conf, folder)
         if getattr(args, 'predict_folder', None) and args.test:
             from .volume_predictor import checkpoint_of
             if checkpoint_of(conf.folder) is None:          # before the test pass evaluates an untrained model

@@ -2753,6 +2753,113 @@ def merge_views(prob, back, N_, K):
     return out
 
 
+IDENTITY_VIEW = ((1.0, 0.0, 0.0, 0.0, 1.0, 0.0),)          # `back` of a model that predicts every slice once
+MAX_PLANES = 4          # csrc/postprocess.hip
+MAX_CALIBRATION_BINS = 64
+
+
+def members_accumulate(prob, back, N_, K, state=None):
+    """One member of an ensemble.  prob [V*N,OH,OW,C] fp32 on the device: ONE model's output for V views of N slices, as for merge_views
+    (back [V,6] fp64; IDENTITY_VIEW for a plain model) -> state = (sum [N,OH,OW,K], aux [N,OH,OW,2]) fp32 (csrc/postprocess.hip): per
+    pixel the sum of the covering views' samples, the sum of their entropies and their number.  state=None starts from 0 in new
+    buffers; otherwise the call continues from `state`, in place, and returns it: one call per model, any number of models.
+    members_finish turns the state into the mean map and the uncertainty planes.  No gradient."""
+    n, K = int(N_), int(K)
+    b = back if isinstance(back, torch.Tensor) else torch.as_tensor(back, dtype=torch.float64)
+    if b.dim() != 2 or b.dtype != torch.float64 or b.shape[1] != 6 or not 1 <= b.shape[0] <= MAX_VIEWS:
+        raise ValueError('members_accumulate: expected a [1..%d, 6] float64 table of views, got %s %s' % (MAX_VIEWS, tuple(b.shape), b.dtype))
+    if prob.dim() != 4 or prob.dtype != torch.float32 or n < 0 or not 1 <= K <= min(16, prob.shape[3]):
+        raise ValueError('members_accumulate: prob %s %s, N = %d, K = %d' % (tuple(prob.shape), prob.dtype, n, K))
+    V, (M, OH, OW, C) = b.shape[0], prob.shape
+    if M != V * n:
+        raise ValueError('members_accumulate: prob %s does not hold %d views of %d slices' % (tuple(prob.shape), V, n))
+    if prob.numel() * 4 >= 2 ** 31:
+        raise ValueError('members_accumulate: prob %s holds 2^31 bytes or more' % (tuple(prob.shape),))
+    if state is None:
+        total, aux = _new((n, OH, OW, K), prob), _new((n, OH, OW, 2), prob)
+    else:
+        total, aux = state
+        for t, last in ((total, K), (aux, 2)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n, OH, OW, last) or not t.is_contiguous()
+                    or t.device != prob.device):
+                raise ValueError('members_accumulate: the state does not belong to %d slices of %d x %d with K = %d' % (n, OH, OW, K))
+    if n:
+        N.call('mmseg_members_accumulate', _c(prob), _c(b.to(prob.device)), total, aux, int(state is None), V, n, OH, OW, C, K)
+    return total, aux
+
+
+def members_finish(state):
+    """state = (sum, aux) of members_accumulate -> (mean [N,OH,OW,K], planes [N,OH,OW,2]) fp32, IN PLACE (the same two tensors): the mean
+    over every covering view of every member (one member: merge_views's map bit for bit), and per pixel (H, I) in [0, 1]: the entropy
+    of the mean over the K organs and the rest, and the mutual information (H minus the mean of the members' entropies), both divided
+    by ln(K + 1).  A pixel that nothing covers gets 0 everywhere.  A state is finished once."""
+    total, aux = state
+    if (not isinstance(total, torch.Tensor) or not isinstance(aux, torch.Tensor) or total.dim() != 4 or total.dtype != torch.float32
+            or aux.dtype != torch.float32 or not 1 <= total.shape[3] <= 16 or tuple(aux.shape) != tuple(total.shape[:3]) + (2,)
+            or not total.is_contiguous() or not aux.is_contiguous() or aux.device != total.device):
+        raise ValueError('members_finish: expected the (sum [N,OH,OW,K], aux [N,OH,OW,2]) fp32 pair of members_accumulate')
+    n, OH, OW, K = total.shape
+    if n:
+        N.call('mmseg_members_finish', total, aux, n, OH, OW, K)
+    return total, aux
+
+
+def restore_map(planes, u, raw_hw, resampled, rows, cols, order=1):
+    """planes [S,OH,OW,U] fp32 on the device (U <= 4 maps with values in [0, 1], such as the planes of members_finish) -> plane u as
+    uint8 levels [S,H,W] on the raw grid, level = round(255 * value), by the geometry and the taps of restore_label
+    (csrc/postprocess.hip); pixels that were cropped away get 0.  No gradient."""
+    H, W = int(raw_hw[0]), int(raw_hw[1])
+    RH, RW = int(resampled[0]), int(resampled[1])
+    if (planes.dim() != 4 or planes.dtype != torch.float32 or not 1 <= planes.shape[3] <= MAX_PLANES or not 0 <= int(u) < planes.shape[3]
+            or order not in (0, 1) or H < 1 or W < 1):
+        raise ValueError('restore_map: planes %s %s, plane %r, raw size %s, order %r' % (tuple(planes.shape), planes.dtype, u, (H, W), order))
+    S, OH, OW, U = planes.shape
+    geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    out = _new((S, H, W), planes, torch.uint8)
+    N.call('mmseg_restore_map', _c(planes), out, S, H, W, RH, RW, OH, OW, *(geo + [U, int(u), int(order)]))
+    return out
+
+
+def calibration_table(prob, truth, values, resampled, rows, cols, bins=10, order=1):
+    """prob [S,OH,OW,C] fp32 and truth [S,H,W] uint8 on the device, values [K] int32 -> (counts int32 [K,B,2], sums fp64 [K,B+2])
+    (csrc/postprocess.hip): every organ channel is sampled at every raw pixel inside the window exactly as restore_label samples it and
+    falls into bin min(B - 1, int(p * B)); counts = (pixels, pixels whose truth is values[k]) per bin; sums = the sum of p per bin, then
+    the sum of (p - y)^2 and of -log(max(p of what is true, 1e-6)).  ECE, MCE, the Brier score and the NLL follow on the host
+    (volume_predictor.calibration_scores).  Integer counts and fixed-order fp64 sums: two runs are bitwise equal."""
+    B, K = int(bins), int(values.numel())
+    RH, RW = int(resampled[0]), int(resampled[1])
+    if (prob.dim() != 4 or prob.dtype != torch.float32 or truth.dim() != 3 or truth.dtype != torch.uint8 or truth.shape[0] != prob.shape[0]
+            or values.dtype != torch.int32 or not 1 <= K <= min(16, prob.shape[3]) or not 2 <= B <= MAX_CALIBRATION_BINS
+            or order not in (0, 1) or min(truth.shape[1:]) < 1):
+        raise ValueError('calibration_table: prob %s %s, truth %s %s, values %s %s, bins %r, order %r'
+                         % (tuple(prob.shape), prob.dtype, tuple(truth.shape), truth.dtype, tuple(values.shape), values.dtype, bins, order))
+    S, OH, OW, C = prob.shape
+    H, W = truth.shape[1:]
+    geo = [int(v) for v in tuple(rows) + tuple(cols)]
+    counts = torch.zeros((K, B, 2), dtype=torch.int32, device=prob.device)
+    sums = torch.zeros((K, B + 2), dtype=torch.float64, device=prob.device)
+    if S:
+        ws = _ws('calibration', (N.call('mmseg_calibration_table_workspace_bytes', S, H, W, K, B) + 7) // 8, prob.device, torch.float64)
+        N.call('mmseg_calibration_table', _c(prob), _c(truth), values, counts, sums, ws, S, H, W, RH, RW, OH, OW, *(geo + [C, K, B, int(order)]))
+    return counts, sums
+
+
+def uncertainty_by_error(pred, truth, levels):
+    """pred, truth uint8 of one shape and levels uint8 [U, that shape] (U <= 4 planes of restore_map) on the device -> int64 [2,1+U]
+    (csrc/postprocess.hip): row 0 over the pixels with pred == truth, row 1 over the others; a row holds the number of pixels and per
+    plane the sum of their levels.  sum / (255 * count) is the mean uncertainty where the labels are right, or wrong."""
+    if (pred.dtype != torch.uint8 or truth.dtype != torch.uint8 or levels.dtype != torch.uint8 or tuple(truth.shape) != tuple(pred.shape)
+            or levels.dim() != pred.dim() + 1 or not 1 <= levels.shape[0] <= MAX_PLANES or tuple(levels.shape[1:]) != tuple(pred.shape)
+            or pred.numel() >= 2 ** 31 - 1):
+        raise ValueError('uncertainty_by_error: pred %s %s, truth %s %s, levels %s %s'
+                         % (tuple(pred.shape), pred.dtype, tuple(truth.shape), truth.dtype, tuple(levels.shape), levels.dtype))
+    U, n = levels.shape[0], pred.numel()
+    out = torch.zeros((2, 1 + U), dtype=torch.int64, device=pred.device)
+    if n:
+        N.call('mmseg_uncertainty_by_error', _c(pred), _c(truth), _c(levels), out, n, U)
+    return out
+
+
 # the parameters of crf_refine, in the order of the entry point; the defaults are starting values that nobody has tuned
 CrfParams = collections.namedtuple('CrfParams', ('radius', 'iterations', 'w_a', 'theta_alpha', 'theta_beta', 'w_s', 'theta_gamma'))
 CRF_DEFAULTS = CrfParams(radius=5, iterations=5, w_a=4.0, theta_alpha=3.0, theta_beta=0.1, w_s=1.0, theta_gamma=1.5)

@@ -62,6 +62,27 @@ view's probability map back and averages them: ops.augment_gather makes the V*N 
 predict_mask runs over them in batches, ops.merge_views merges the maps on the device, and the way back goes on from the merged map.
 With tiles=True the views act on the tile containers, and the merged tiles are blended.  predictions.json then carries `tta`.
 
+members=[further models] of VolumePredictor and uncertainty=True of run (build-defined, off by default; the rule is in INTEGRATION.md
+section 5) predict with several models together, as the folds of a cross-validation are used, and keep what a mean throws away.  Every
+model (the run folder's first, then the list) predicts the volume, under every view with tta; ops.members_accumulate adds each model's
+maps into one pair of buffers and ops.members_finish leaves the mean map over all models and views and two planes in [0, 1]: the
+entropy H of the mean over the organs and the rest, and the mutual information I, the part of H that is disagreement between the
+members.  The way back goes on from the mean: crf (on the mean), restore_label, smoothing, filter, filling.  The planes are those
+BEFORE the crf; with tiles=True the tiles' planes are blended like the maps (ops.blend_tiles), and a blend of entropies only
+approximates the entropy of the blend.  One model alone and uncertainty=True gives the same labels as without, I == 0, and H.
+    <out>/uncertainty/<file name>.npz      entropy, mutual_information [S_file,H,W] uint8 (level / 255; ops.restore_map, 1 byte per pixel
+                                           down each), resolution and, where the file carries it, slice_spacing
+    <out>/results_calibration_<modality>.csv   where the files carry a `label`: per volume and organ ECE, MCE, Brier score, NLL and the
+                                           number of pixels, from ops.calibration_table with calibration_bins bins on the map that the
+                                           labels come from (after the crf if it is on).  EVERY raw pixel inside the window counts, so
+                                           the scores are dominated by the background
+    <out>/reliability_<modality>.csv       per organ and bin, summed over the volumes: pixels, mean confidence, observed frequency; for
+                                           anyone who wants another convention than the one above
+    <out>/results_uncertainty_<modality>.csv   per volume the mean entropy and mutual information over the correctly and over the wrongly
+                                           labelled pixels of the selected slices (ops.uncertainty_by_error), on the final prediction,
+                                           after every filter
+predictions.json then carries `ensemble` (the members' run folders), `uncertainty` and `calibration_bins`.
+
 Dice is costs.dice's formula applied to pixel counts (ops.label_overlap): per slice (2 I + 1e-12) / (P + T + 1e-12), the joint score
 from the counts summed over the organs, then the mean over the selected slices.
 
@@ -448,15 +469,81 @@ def write_robust_results(path, rows, num_masks):
     _write_table(path, rows, ('HD', 'NSD'), num_masks, '%.3f', True)
 
 
+MAX_MEMBERS = 7          # further models beside the run folder's own
+CALIBRATION_NAMES = ('ECE', 'MCE', 'Brier', 'NLL', 'N')
+
+
+def check_calibration_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= ops.MAX_CALIBRATION_BINS:
+        raise ValueError('calibration_bins (--predict_calibration_bins) must be a whole number in [2, %d], got %r'
+                         % (ops.MAX_CALIBRATION_BINS, bins))
+    return int(bins)
+
+
+def calibration_scores(counts, sums):
+    """counts [K,B,2] = (n, positives) and sums [K,B+2] of ops.calibration_table (host arrays) -> [K,5] = ECE, MCE, Brier, NLL, n per
+    organ: over the bins that hold a pixel, gap_b = |positives_b / n_b - (sum of p)_b / n_b|; ECE = sum of n_b / n * gap_b, MCE = the
+    largest gap; Brier and NLL are their sums over n.  An organ without a pixel inside the window gets nan."""
+    counts, sums = np.asarray(counts, np.float64), np.asarray(sums, np.float64)
+    K, B = counts.shape[:2]
+    out = np.full((K, 5), np.nan)
+    for k in range(K):
+        n_b, positives = counts[k, :, 0], counts[k, :, 1]
+        n = n_b.sum()
+        out[k, 4] = n
+        if n > 0:
+            held = n_b > 0
+            gap = np.abs(positives[held] / n_b[held] - sums[k, :B][held] / n_b[held])
+            out[k, :4] = np.sum(n_b[held] / n * gap), gap.max(), sums[k, B] / n, sums[k, B + 1] / n
+    return out
+
+
+def uncertainty_means(table):
+    """table [2,3] int64 of ops.uncertainty_by_error on (entropy, mutual information) -> [2,3] = (pixels, mean H, mean I) over the correctly
+    and over the wrongly labelled pixels; the means are nan where there is no such pixel"""
+    t = np.asarray(table, np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.concatenate([t[:, :1], t[:, 1:] / (255.0 * t[:, :1])], axis=1)
+
+
+def write_calibration_results(path, rows, num_masks):
+    """rows: (volume, [K,5]) -> Vol, ECE0, MCE0, Brier0, NLL0, N0, ECE1, ..."""
+    with open(path, 'w') as f:
+        f.write(', '.join(['Vol'] + ['%s%d' % (name, k) for k in range(num_masks) for name in CALIBRATION_NAMES]) + '\n')
+        for vol, table in rows:
+            f.write(', '.join([str(vol)] + ['%.6f, %.6f, %.6f, %.6f, %d' % (r[0], r[1], r[2], r[3], int(r[4])) for r in table]) + '\n')
+
+
+def write_uncertainty_results(path, rows, num_masks):
+    """rows: (volume, [2,3]) -> Vol, NCorrect, EntropyCorrect, MICorrect, NWrong, EntropyWrong, MIWrong"""
+    with open(path, 'w') as f:
+        f.write(', '.join(['Vol'] + [name + which for which in ('Correct', 'Wrong') for name in ('N', 'Entropy', 'MI')]) + '\n')
+        for vol, table in rows:
+            f.write(', '.join([str(vol)] + ['%d, %.6f, %.6f' % (int(r[0]), r[1], r[2]) for r in table]) + '\n')
+
+
+def write_reliability(path, counts, sums):
+    """counts [K,B,2] and sums [K,B+2] summed over the volumes -> Organ, Bin, Lo, Hi, N, Confidence, Frequency (nan in an empty bin)"""
+    K, B = counts.shape[:2]
+    with open(path, 'w') as f:
+        f.write('Organ, Bin, Lo, Hi, N, Confidence, Frequency\n')
+        for k in range(K):
+            for b in range(B):
+                n = int(counts[k, b, 0])
+                conf, freq = (sums[k, b] / n, counts[k, b, 1] / float(n)) if n else (float('nan'), float('nan'))
+                f.write('%d, %d, %.6f, %.6f, %d, %.6f, %.6f\n' % (k, b, b / float(B), (b + 1) / float(B), n, conf, freq))
+
+
 class ScoreSheet(object):
     """the rows of one run's results_<kind>_<modality>.csv files: rows[kind][m] holds those of modality m; `scores` is score_volume's"""
     WRITERS = (('native', write_results), ('surface', write_surface_results), ('robust', write_robust_results),
                ('components', write_component_results), ('holes', write_hole_results), ('smooth', write_smooth_results),
-               ('crf', write_crf_results))
+               ('crf', write_crf_results), ('calibration', write_calibration_results), ('uncertainty', write_uncertainty_results))
 
     def __init__(self, modalities, num_masks, in_mm):
         self.modalities, self.num_masks, self.in_mm = list(modalities), num_masks, in_mm
         self.rows = {kind: [[] for _ in self.modalities] for kind, _ in self.WRITERS}
+        self.reliability = {}          # modality index -> (counts, sums) of the calibration tables, summed over the volumes
 
     def add(self, m, volume, scores, geometry):
         modality, (joint, per_organ, in_mm, robust) = self.modalities[m], scores
@@ -486,8 +573,20 @@ class ScoreSheet(object):
         after, before, both = nn.to_numpy(counts).astype(np.int64).sum(axis=0).T
         self.rows['crf'][m].append((volume, np.stack([before, before - both, after - both], axis=1)))
 
+    def add_calibration(self, m, volume, counts, sums):
+        """the table of ops.calibration_table, on the host: a row of scores, and the table is added to the modality's reliability table"""
+        counts, sums = np.asarray(counts, np.int64), np.asarray(sums, np.float64)
+        self.rows['calibration'][m].append((volume, calibration_scores(counts, sums)))
+        held = self.reliability.get(m)
+        self.reliability[m] = (counts, sums) if held is None else (held[0] + counts, held[1] + sums)
+
+    def add_uncertainty(self, m, volume, table):
+        self.rows['uncertainty'][m].append((volume, uncertainty_means(nn.to_numpy(table))))
+
     def write(self, out_folder):
         """one file per kind and modality that has rows"""
+        for m, (counts, sums) in sorted(self.reliability.items()):
+            write_reliability(os.path.join(out_folder, 'reliability_%s.csv' % self.modalities[m]), counts, sums)
         for kind, writer in self.WRITERS:
             for m, name in enumerate(self.modalities):
                 if self.rows[kind][m]:
@@ -553,14 +652,25 @@ def score_folder(pred_folder, data_folder, out_folder=None, surface=True, compon
 
 
 class VolumePredictor(object):
-    def __init__(self, model, conf):
+    def __init__(self, model, conf, members=None):
+        """members: further models that predict together with `model` (an ensemble; at most MAX_MEMBERS), built for the same
+        modalities, input_shape and organs"""
         self.model, self.conf = model, conf
+        self.members = list(members or ())
+        if len(self.members) > MAX_MEMBERS:
+            raise ValueError('members (--predict_ensemble): %d further models, at most %d' % (len(self.members), MAX_MEMBERS))
+        for member in self.members:
+            if len(member.modalities) != len(model.modalities):
+                raise ValueError('members (--predict_ensemble): a member is built for %d modalities, the model for %d'
+                                 % (len(member.modalities), len(model.modalities)))
 
-    def predict_volume(self, modality_index, mode, images):
-        """predict_mask over the slices of one volume in batches of conf.batch_size: device tensors in, one device tensor out"""
+    def predict_volume(self, modality_index, mode, images, model=None):
+        """predict_mask of `model` (default: the run folder's) over the slices of one volume in batches of conf.batch_size: device tensors
+        in, one device tensor out"""
+        model = self.model if model is None else model
         S = images[0].shape[0]
         step = max(1, int(self.conf.get('batch_size', S) or S))
-        parts = [self.model.predict_mask(modality_index, mode, [x[i:i + step] for x in images]) for i in range(0, S, step)]
+        parts = [model.predict_mask(modality_index, mode, [x[i:i + step] for x in images]) for i in range(0, S, step)]
         parts = [p if isinstance(p, torch.Tensor) else nn.host_to_device(p, images[0].device) for p in parts]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
@@ -575,29 +685,54 @@ class VolumePredictor(object):
                              % (len(views.tokens), N, tuple(prob.shape)))
         return ops.merge_views(prob, views.back, N, int(self.conf.num_masks))
 
-    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded, views=None, crf=None):
+    def predict_members(self, modality_index, mode, images, views=None):
+        """(mean map [N,OH,OW,K], planes [N,OH,OW,2] = (H, I)) of the N slices of `images` over the run folder's model and every member,
+        in that order, each under every view of `views` (check_tta's; None: every slice once): one predict_volume and one
+        ops.members_accumulate per model into one pair of buffers, then ops.members_finish."""
+        N, K = int(images[0].shape[0]), int(self.conf.num_masks)
+        shown = images if views is None else views_in(images, views)
+        back = ops.IDENTITY_VIEW if views is None else views.back
+        state = None
+        for model in [self.model] + self.members:
+            prob = self.predict_volume(modality_index, mode, shown, model)
+            if prob.numel() * 4 >= 2 ** 31:
+                raise ValueError('members (--predict_ensemble): the maps of %d views of %d slices, %s, hold 2^31 bytes or more'
+                                 % (len(back), N, tuple(prob.shape)))
+            state = ops.members_accumulate(prob, back, N, K, state)
+        return ops.members_finish(state)
+
+    def predict_tiled(self, loader, volume, m, mode, overlap, uploaded, views=None, crf=None, ensemble=False):
         """the blended probability map [S,RH,RW,K] of modality m on its whole resampled frame: the tiles are loaded
         (loader.load_volume_tiles), predicted as one batch of TR*TC*S slices and blended (ops.blend_tiles).  overlap = (rows, columns);
         uploaded: loader.upload_volume(volume).  With views (check_tta's) every tile is predicted under each view, turned about its own
         centre, and merged (predict_views) before the blend, which then sees the K organ channels alone.  With crf (check_crf's) every
         tile's map is refined against the tile's image of modality m (ops.crf_refine) before the blend, and the result is the pair
-        (blend of the refined tiles, blend of the tiles as predicted)."""
+        (blend of the refined tiles, blend of the tiles as predicted).  With ensemble every tile's map is the members' mean
+        (predict_members), and the blend of the tiles' planes (H, I) [S,RH,RW,2] is appended to whatever the call returns otherwise: an
+        approximation, since the entropy of a blend is not the blend of the entropies."""
         images, geometry, plan = loader.load_volume_tiles(volume, m, overlap, uploaded)
         rows, cols = plan[m]
         OH, OW = loader.input_shape[:2]
-        prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
+        planes = None
+        if ensemble:
+            prob, planes = self.predict_members(m, mode, images, views)
+        else:
+            prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
         S = images[m].shape[0] // (len(rows) * len(cols))
 
-        def blend(p):
-            return ops.blend_tiles(p, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'],
-                                   loader.num_masks)
+        def blend(p, channels=loader.num_masks):
+            return ops.blend_tiles(p, rows, cols, tile_weights(rows, OH), tile_weights(cols, OW), S, geometry[m]['resampled'], channels)
+        extra = () if planes is None else (blend(planes, 2),)
         if crf is None:
-            return blend(prob)
-        return blend(ops.crf_refine(prob, images[m], loader.num_masks, crf)), blend(prob)
+            return blend(prob) if planes is None else (blend(prob),) + extra
+        return (blend(ops.crf_refine(prob, images[m], loader.num_masks, crf)), blend(prob)) + extra
 
     def run(self, folder, out_folder, volumes=None, mode='simple', order=1, surface=True, components=None, connectivity=6, robust=None,
-            fill_holes=None, tiles=False, tile_overlap=None, tta=None, smooth=None, smooth_radius=None, smooth_extent='2d', crf=None):
+            fill_holes=None, tiles=False, tile_overlap=None, tta=None, smooth=None, smooth_radius=None, smooth_extent='2d', crf=None,
+            uncertainty=False, calibration_bins=10):
         crf = check_crf(crf)
+        calibration_bins = check_calibration_bins(calibration_bins)
+        ensemble = bool(self.members) or bool(uncertainty)          # off: the path below is the one without the option, launch for launch
         check_components(components, connectivity)
         check_fill_holes(fill_holes)
         smooth_radius = check_smooth(smooth, smooth_radius, smooth_extent)
@@ -639,13 +774,18 @@ class VolumePredictor(object):
                 if tiles and len(rows) * len(cols) > 1:
                     RH, RW = geo['resampled']
                     window = ((RH, RW), (0, RH, 0), (0, RW, 0))
-                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded, views, crf)
+                    prob = self.predict_tiled(loader, v, m, mode, overlap, uploaded, views, crf, ensemble)
+                    if ensemble:
+                        prob, planes = (prob[0], prob[1]) if crf is None else (prob[:2], prob[2])
                     prob, unrefined = prob if crf is not None else (prob, None)
                 else:          # one tile: the centre window of crop_pad_map, the path without the option
                     if images is None:
                         images, _ = loader.load_volume_for_prediction(v)
                     window = (geo['resampled'], geo['rows'], geo['cols'])
-                    prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
+                    if ensemble:
+                        prob, planes = self.predict_members(m, mode, images, views)
+                    else:
+                        prob = self.predict_volume(m, mode, images) if views is None else self.predict_views(m, mode, images, views)
                     if crf is not None:          # against the slices as the network saw them, unturned
                         prob, unrefined = ops.crf_refine(prob, images[m], loader.num_masks, crf), prob
                 pred = ops.restore_label(prob, values, geo['raw_shape'][1:], window[0], window[1], window[2], order)
@@ -661,13 +801,26 @@ class VolumePredictor(object):
                 if fill_holes:
                     pred, stats = _fill_holes(pred, values, geo, fill_holes)
                     sheet.add_holes(m, v, stats)
-                if geo['label'] is not None:
-                    scores = score_volume(pred, nn.host_to_device(geo['label'], device, np.uint8), values, geo, surface, robust)
+                truth = None if geo['label'] is None else nn.host_to_device(geo['label'], device, np.uint8)
+                if truth is not None:
+                    scores = score_volume(pred, truth, values, geo, surface, robust)
                     sheet.add(m, v, scores, geo)
                 label = np.zeros(geo['raw_shape'], np.uint8)
                 label[geo['slices']] = pred.cpu().numpy()
                 extra = {} if geo['slice_spacing'] is None else dict(slice_spacing=float(geo['slice_spacing']))
                 np.savez_compressed(os.path.join(out_folder, geo['file']), label=label, resolution=geo['resolution'], **extra)
+                if ensemble:
+                    levels = torch.stack([ops.restore_map(planes, u, geo['raw_shape'][1:], window[0], window[1], window[2], order)
+                                          for u in (0, 1)])
+                    if truth is not None:          # the map that the labels come from; the prediction after every filter
+                        table = ops.calibration_table(prob, truth, values, window[0], window[1], window[2], calibration_bins, order)
+                        sheet.add_calibration(m, v, nn.to_numpy(table[0]), nn.to_numpy(table[1]))
+                        sheet.add_uncertainty(m, v, ops.uncertainty_by_error(pred, truth, levels))
+                    on_grid = np.zeros((2,) + tuple(geo['raw_shape']), np.uint8)
+                    on_grid[:, geo['slices']] = levels.cpu().numpy()
+                    os.makedirs(os.path.join(out_folder, 'uncertainty'), exist_ok=True)
+                    np.savez_compressed(os.path.join(out_folder, 'uncertainty', geo['file']), entropy=on_grid[0],
+                                        mutual_information=on_grid[1], resolution=geo['resolution'], **extra)
                 files[geo['file']] = dict(volume=v, modality=loader.modalities[m], slices=geo['slices'], **extra)
                 if origins is not None:
                     files[geo['file']]['tile_origins'] = origins
@@ -688,6 +841,9 @@ class VolumePredictor(object):
             settings.update(tta=list(views.tokens))
         if crf is not None:
             settings.update(crf=dict(crf._asdict()))
+        if ensemble:
+            folders = [self.conf.get('folder')] + [(getattr(member, 'conf', None) or {}).get('folder') for member in self.members]
+            settings.update(ensemble=folders, uncertainty=bool(uncertainty), calibration_bins=calibration_bins)
         with open(os.path.join(out_folder, 'predictions.json'), 'w') as f:
             json.dump(settings, f, indent=1)
         return sheet.by_name('native')
